@@ -364,6 +364,37 @@ def timed_loop(step_fn, a, dp):
     return dp.max_over_ranks(dt) if dp else dt
 
 
+DUMP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(path, model, images):
+    """--dump-outputs DIR: what the last timed step handed its caller, one DIR/<name>.npy each: `images` (the generated batch), `log_<key>` (every
+    logged loss / score, float64) and `weights_<net>` (each network's flat parameters after the optimiser step), all in float32 otherwise.  An array
+    over its even share of DUMP_BYTES is written as a fixed sample: a flat vector of the elements at the sorted positions that
+    torch.randperm(numel, generator seeded 0)[:share] picks, so two runs or two builds with the same arguments write the same positions."""
+    import numpy as np
+    arrays = {'images': images}
+    arrays.update(('log_' + re.sub(r'\W', '_', k), v) for k, v in model.get_current_log().items())
+    for attr in ('netG', 'netD_target', 'netD_source', 'netD'):
+        net = getattr(model, attr, None)
+        if net is not None:
+            arrays['weights_' + attr] = net.params.flat
+    n_big = sum(1 for v in arrays.values() if torch.is_tensor(v))
+    share = (DUMP_BYTES - 4096 * len(arrays)) // (4 * n_big)   # float32 elements per tensor (4 kB per file kept for the .npy header and the scalars)
+    os.makedirs(path, exist_ok=True)
+    for name, v in arrays.items():
+        if torch.is_tensor(v):
+            v = v.detach()
+            if v.numel() > share:
+                idx = torch.randperm(v.numel(), generator=torch.Generator().manual_seed(0))[:share].sort().values
+                v = v.reshape(-1)[idx.to(v.device)]
+            arr = v.float().cpu().numpy()
+        else:
+            arr = np.asarray([v], dtype=np.float64)
+        np.save(os.path.join(path, name + '.npy'), arr)
+    log('outputs of the last timed step written to %s (%d arrays)' % (path, len(arrays)))
+
+
 def bench_dsn(a, dp, as_secondary=False):
     """second hot path: one DSN iteration = G fwd, D fwd on [fake; real], losses, D wgrad, G bwd, 2x Adam"""
     from dasr_amd.dsn_model import DSNModel
@@ -394,6 +425,8 @@ def bench_dsn(a, dp, as_secondary=False):
            'generator_tflops': round(ips * tf, 1)}
     if not as_secondary:
         out['log'] = m.get_current_log()
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, m, m.fake)
     if rank == 0:
         out['roofline'] = secondary_roofline(lambda: m.iteration(hr, bic, real), 1, 'dsn_lpips' if a.per_type == 'LPIPS' else 'dsn_vgg')
     else:
@@ -439,6 +472,8 @@ def bench_srn(a, dp, dasr, as_secondary=False):
     logd = model.get_current_log()
     loss = logd.get('l_pix', logd.get('loss/l_g_pix'))
     log('timed steps done: %.2f ms/step' % (dt / a.steps * 1e3))
+    if a.dump_outputs and rank == 0 and not as_secondary:
+        dump_outputs(a.dump_outputs, model, model.fake_H)
     ips = batch * world * a.steps / dt
     full = (a.nf == 64 and a.nb == 23 and s == 128)
     out = {'metric': 'SR train images/sec (4x, 128->512)', 'value': round(ips, 3), 'unit': 'images/s', 'n_gpus': world,
@@ -567,6 +602,8 @@ def main():
     ap.add_argument('--fs', type=str, default='wavelet', choices=['wavelet', 'gau', 'avg_pool'])
     ap.add_argument('--fea', type=str, default='l1', choices=['l1', 'LPIPS'], help="--model dasr: feature_criterion (l1 = VGG19-54 features, BASELINE configs[2]; LPIPS = the shipped train_DASR.json criterion)")
     ap.add_argument('--per-type', dest='per_type', type=str, default='VGG', choices=['VGG', 'LPIPS'], help='--model dsn: perceptual term')
+    ap.add_argument('--dump-outputs', metavar='DIR', default='',
+                    help='write what the last timed step computed (generated images, logged losses, updated weights) as DIR/<name>.npy, 64 MB at most')
     a = ap.parse_args()
     dp = setup_dist(a)
     rank = dp.rank if dp else 0
