@@ -41,6 +41,11 @@ class WgradReducePart(C.Structure):
                 ('tap0', c_i32), ('ntaps_total', c_i32), ('bias_nsplit', c_i32), ('reserved_', c_i32)]
 
 
+class ResblockParams(C.Structure):
+    _fields_ = [('x16', Tensor), ('x32', Tensor), ('w0', c_vp), ('b0', c_vp), ('w1', c_vp), ('b1', c_vp),
+                ('y32', Tensor), ('y16', Tensor), ('h', Tensor), ('N', c_i32), ('H', c_i32), ('W', c_i32), ('res_scale', c_f32), ('slope', c_f32)]
+
+
 class PackSeg(C.Structure):
     _fields_ = [('src_off', c_i64), ('src_cout', c_i32), ('src_cin', c_i32), ('cin_start', c_i32), ('cin_len', c_i32),
                 ('src_c0', c_i32), ('transpose', c_i32)]
@@ -73,12 +78,14 @@ OP_CONV_CHAIN = 48
 OP_RDB_CHAIN = 49
 OP_BNORM_JVP, OP_BNORM_SECOND = 50, 51   # --wgan with BatchNorm discriminators (round 6)
 OP_PRELU_FINAL = 52
+OP_RESBLOCK = 53   # fused residual block of SRResNet (ABI 21)
 
 _SIGS = {
     'dasr_conv': [C.POINTER(ConvParams), c_vp],
     'dasr_conv_chain': [c_vp, C.POINTER(ConvParams), c_vp, c_i32, c_vp, c_vp, c_vp],
     'dasr_rdb_chain': [c_vp, C.POINTER(ConvParams), c_i32, c_vp, c_vp, c_vp],
     'dasr_conv_naive': [C.POINTER(ConvParams), c_vp, c_vp],
+    'dasr_resblock': [C.POINTER(ResblockParams), c_vp],
     'dasr_set_tuning': [c_i32, c_i32],
     'dasr_wgrad': [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp],
     'dasr_wgrad_set_mode': [c_i32],
@@ -161,7 +168,7 @@ _BENCH_SIGS = {
 }
 BENCH_LIB_PATH = os.path.join(HERE, 'libdasr_bench.so')
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 _lib = None
 _bench = None
 

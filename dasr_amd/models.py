@@ -193,9 +193,25 @@ class BaseModel:
 
 
 def _define_G(opt, device, rdb_prec=None):
-    """networks.py:83-147 restricted to the hot-path generator (RRDB_net, upconv)."""
+    """networks.py:83-147 restricted to the hot-path generators (RRDB_net, sr_resnet)."""
     g = opt['network_G']
     which = g['which_model_G']
+    if which == 'sr_resnet':   # networks.py:88-91: SRResNet(act_type 'relu', upsample_mode 'pixelshuffle'), init_weights(kaiming, 0.1)
+        from .srresnet import SRResNetHIP, srresnet_param_spec
+        if opt['model'] in ('DASR', 'DASR_FS_ESRGAN_patchGAN'):
+            raise NotImplementedError('sr_resnet as the generator of model {:s} is not implemented: on the DASR step the res.0 weight gradients of its '
+                                      'residual blocks sit 1.1-1.4e-2 from an fp64 evaluation with the bf16 and with the f16-storage trunk, outside the '
+                                      '1e-2 gradient tolerance (DESIGN.md §8); the reference builds it through define_G (networks.py:88-91)'.format(opt['model']))
+        # trunk storage (SRResNetHIP trunk_prec): DASR_RDB_PREC, else bf16
+        prec = rdb_prec
+        net = SRResNetHIP(in_nc=g['in_nc'], out_nc=g['out_nc'], nf=g['nf'], nb=g['nb'], upscale=g['scale'], device=device, norm_type=g['norm_type'],
+                          mode=g['mode'], trunk_prec=prec)
+        if opt['is_train']:
+            logger.info('Initialization method [kaiming]')
+            net.load_state_dict(kaiming_state_dict(srresnet_param_spec(g['in_nc'], g['out_nc'], g['nf'], g['nb']), 0.1))
+        else:
+            net.repack()
+        return net
     if which not in ('RRDB_net', 'RRDB_mask'):
         raise NotImplementedError('Generator model [{:s}] not recognized'.format(which))
     # `upsample_mode` is an extension of the option surface: the reference's define_G hard-wires 'upconv' (networks.py:96-99) although

@@ -38,6 +38,8 @@ def rrdbnet_param_spec(in_nc, out_nc, nf, nb, upsample_mode='upconv'):
 
 
 class RRDBNetHIP:
+    act_slope = SLOPE   # negative slope of the activations of the HR tail (LeakyReLU 0.2; SRResNetHIP: ReLU)
+
     def __init__(self, in_nc=3, out_nc=3, nf=64, nb=23, upscale=4, device='cuda', rdb_prec=None, stream_prec=3, upsample_mode='upconv'):
         assert upscale == 4 and nf % 32 == 0 and in_nc <= 16 and out_nc <= 16
         if upsample_mode not in ('upconv', 'pixelshuffle'):
@@ -86,8 +88,12 @@ class RRDBNetHIP:
         return (self.params.off(key), cout, cin, 0, cin, 0, 0)
 
     def _register_packs(self):
+        self._register_stream_packs()
+        self._register_trunk_packs()
+
+    def _register_stream_packs(self):
+        """fea_conv, LR_conv and the HR tail (what RRDBNet and SRResNet share, at the same state_dict keys)"""
         nf, P, sp = self.nf, self.params, self.stream_prec
-        mt_nf = 2 if (nf >= 64 and self.rdb_prec in (1, 2)) else 1
         # HR tail (the two upconvs, HR_conv0, HR_conv1: 7.6 % of the FLOPs but a fifth of the step in split-bf16): f16 operands, ONE
         # MFMA pass.  Measured on the oracle with emulated operand rounding (oracle/precision_probe.py, nf64 nb23): SR output 2.4e-5,
         # HR-tail weight gradients 5e-4 normwise -- the tolerances are 1e-3 / 1e-2.  fea_conv and LR_conv feed the residual stream of
@@ -132,6 +138,10 @@ class RRDBNetHIP:
                     self.pk[(name, py, px)] = self.pack.add(nf, nf, 4, hmt, hp, [self._seg_fwd(key, nf, nf)], tapmap=[0, 0, 0, 0], src_ntaps=9, tapmasks=fw)
                     self.pk[(name + '_b', py, px)] = self.pack.add(nf, nf, 4, hmt, hp, [(P.off(key), nf, nf, 0, nf, 0, 1)], tapmap=[0, 0, 0, 0], src_ntaps=9,
                                                                    tapmasks=bw)
+
+    def _register_trunk_packs(self):
+        nf, P = self.nf, self.params
+        mt_nf = 2 if (nf >= 64 and self.rdb_prec in (1, 2)) else 1
         # dense blocks
         for i in range(self.nb):
             for r in (1, 2, 3):
@@ -235,8 +245,11 @@ class RRDBNetHIP:
         dense-block weight gradients are then NOT part of the plan's backward list but of store.phase (one launch over the whole batch)."""
         key = (N, h, w, replica, id(store) if store is not None else 0, n0)
         if key not in self.plans:
-            self.plans[key] = _Plan(self, N, h, w, replica, store=store, n0=n0)
+            self.plans[key] = self._make_plan(N, h, w, replica, store=store, n0=n0)
         return self.plans[key]
+
+    def _make_plan(self, *args, **kw):
+        return _Plan(self, *args, **kw)
 
     # dense-block weight gradients run as a separate phase AFTER the data-gradient chain (TrunkStore.phase): grouped launches over the whole batch
     # with the chip to themselves, instead of one launch per RRDB interleaved with (and, under two sub-batch streams, competing with) the
@@ -271,7 +284,7 @@ class RRDBNetHIP:
         if p is None:
             while len(cache) >= self.INFER_CACHE:
                 cache.popitem(last=False)
-            p = _Plan(self, N, h, w, inference=True)
+            p = self._make_plan(N, h, w, inference=True)
         cache[key] = p
         p.set_input(x)
         p.fwd.run()
@@ -653,6 +666,14 @@ class _Plan:
                     ops.keep.append(ch)
                 ops.add(body[-1])
             self.chain = self.chains[0]
+        self._build_tail_forward(ops, X)
+
+    def _build_tail_forward(self, ops, X):
+        """LR_conv + global skip (t0 = fea + LR_conv(X)) and the HR tail behind the trunk output X; sets self.fwd"""
+        net, N, h, w = self.net, self.N, self.h, self.w
+        nf, nb, P, pack, pk = net.nf, net.nb, net.params, net.pack, net.pk
+        H2, W2, H4, W4 = 2 * h, 2 * w, 4 * h, 4 * w
+        sl = net.act_slope
         self.x_last = X
         lrb = 'model.1.sub.%d.bias' % nb
         if net.hr_f16s:
@@ -661,7 +682,7 @@ class _Plan:
             ops.tag(1)
             if net.ps:   # pixelshuffle_block (block.py:838-851): conv nf -> 4 nf, PixelShuffle(2), LeakyReLU (applied before the shuffle: it is elementwise)
                 for name, bkey, src, pre, dst, hi, wi in (('up1', 'model.2.bias', self.t0h, self.ps1, self.u1, h, w), ('up2', 'model.5.bias', self.u1, self.ps2, self.u2, H2, W2)):
-                    ops.add(conv_op(pack, pk[name], src.view(), False, nf, hi, wi, hi, wi, N, bias=P.ptr(bkey), act=1, out_bf16=pre.view(), out16_f16=1))
+                    ops.add(conv_op(pack, pk[name], src.view(), False, nf, hi, wi, hi, wi, N, bias=P.ptr(bkey), act=1, slope=sl, out_bf16=pre.view(), out16_f16=1))
                     o = Op()
                     o.op = _lib.OP_PIXSHUF
                     o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.t[1] = pre.view(), N, 4 * nf, hi, wi, dst.view()
@@ -669,7 +690,7 @@ class _Plan:
             for name, bkey, src, dst, hi, wi in (() if net.ps else (('up1', 'model.3.bias', self.t0h, self.u1, h, w), ('up2', 'model.6.bias', self.u1, self.u2, H2, W2))):
                 ops.add(conv_op(pack, pk[name], src.view(), False, nf, hi, wi, 2 * hi, 2 * wi, N, bias=P.ptr(bkey), ups=1, act=1, out_bf16=dst.view(),
                                 out16_f16=1))
-            ops.add(conv_op(pack, pk['hr0'], self.u2.view(), False, nf, H4, W4, H4, W4, N, bias=P.ptr('model.8.bias'), act=1, out_bf16=self.h0.view(),
+            ops.add(conv_op(pack, pk['hr0'], self.u2.view(), False, nf, H4, W4, H4, W4, N, bias=P.ptr('model.8.bias'), act=1, slope=sl, out_bf16=self.h0.view(),
                             out16_f16=1))
             ops.add(conv_op(pack, pk['hr1'], self.h0.view(), False, nf, H4, W4, H4, W4, N, bias=P.ptr('model.10.bias'), out_f32=self.sr.view()))
             o = Op()
@@ -756,9 +777,9 @@ class _Plan:
         share for each of k concurrent sub-batch replicas"""
         return 256 // max(1, getattr(self.net, 'concurrent_replicas', 1))
 
-    def _wg3(self, ops, conv_key, g, inp, cout, cin, Hin, Win, Hout, Wout, ups=0):
-        """weight gradient of one 3x3 conv on f16 tensors (g pre-scaled by gscale) with the 12-wave kernel: one part per 64-channel block of
-        the input x up to three 32-oc tiles"""
+    def _wg3(self, ops, conv_key, g, inp, cout, cin, Hin, Win, Hout, Wout, ups=0, f16=True, g_scale=None):
+        """weight gradient of one 3x3 conv on f16 tensors (g pre-scaled by g_scale, default the plan's gscale; f16=False: bf16 tensors, unscaled)
+        with the 12-wave kernel: one part per 64-channel block of the input x up to three 32-oc tiles"""
         P, N = self.net.params, self.N
         grp = WgradGroup3()
         octs = list(range(0, cout, 32))
@@ -770,7 +791,8 @@ class _Plan:
                               oc0=oc0, c0=c0, n_ctiles=min(2, ceil_div(blk, 32))) for oc0 in sub]
                 grp.add_block(g.view(sub[0]), min(2 * len(sub), g.planes - sub[0] // 16), inp.view(c0), ceil_div(blk, 16), ceil_div(blk, 32),
                               Hin, Win, Hout, Wout, N, tiles, want_bias=(c0 == 0), ups=ups)
-        grp.f16, grp.g_scale = True, self.gscale
+        if f16:
+            grp.f16, grp.g_scale = True, self.gscale if g_scale is None else g_scale
         grp.flops = 2.0 * N * Hout * Wout * 9 * cin * cout
         grp.finalize(self.ws, self.net.device, target_wgs=self._wg3_target(len(grp.parts)))
         for o in grp.ops(self.grad.data_ptr()):
@@ -784,12 +806,13 @@ class _Plan:
         nf, pack, pk, gs = net.nf, net.pack, net.pk, self.gscale
         H2, W2, H4, W4 = 2 * h, 2 * w, 4 * h, 4 * w
         g_h0, g_u2, g_up2, g_u1, g_up1 = self.g4a, self.g4b, self.g4a, self.g2a, self.g2b
+        sl = net.act_slope
 
         def downsum(src, hl, wl, mask, dst_f32, dst_f16, out_scale):
             o = Op()
             o.op = _lib.OP_DOWNSUM_F16
             o.t[0], o.i[0], o.i[1], o.i[2], o.i[3] = src.view(), N, nf, hl, wl
-            o.t[1], o.f[0], o.f[1] = (mask.view() if mask is not None else NULL_T), SLOPE, out_scale
+            o.t[1], o.f[0], o.f[1] = (mask.view() if mask is not None else NULL_T), sl, out_scale
             o.t[2], o.t[3] = (dst_f32.view() if dst_f32 is not None else NULL_T), (dst_f16.view() if dst_f16 is not None else NULL_T)
             ops.add(o)
 
@@ -799,11 +822,11 @@ class _Plan:
         ops.add(o)
         # HR_conv1
         self._wg3(ops, 'model.10.', self.g_sr16, self.h0, net.out_nc, nf, H4, W4, H4, W4)
-        ops.add(conv_op(pack, pk['hr1_b'], self.g_sr16.view(), False, 16, H4, W4, H4, W4, N, mask=self.h0.view(), mask_f32=0, out_bf16=g_h0.view(),
+        ops.add(conv_op(pack, pk['hr1_b'], self.g_sr16.view(), False, 16, H4, W4, H4, W4, N, mask=self.h0.view(), mask_f32=0, slope=sl, out_bf16=g_h0.view(),
                         out16_f16=1))
         # HR_conv0
         self._wg3(ops, 'model.8.', g_h0, self.u2, nf, nf, H4, W4, H4, W4)
-        ops.add(conv_op(pack, pk['hr0_b'], g_h0.view(), False, nf, H4, W4, H4, W4, N, mask=self.u2.view(), mask_f32=0, out_bf16=g_u2.view(), out16_f16=1))
+        ops.add(conv_op(pack, pk['hr0_b'], g_h0.view(), False, nf, H4, W4, H4, W4, N, mask=self.u2.view(), mask_f32=0, slope=sl, out_bf16=g_u2.view(), out16_f16=1))
         if net.ps:
             # PixelShuffle upsamplers: un-shuffle the gradient (+ LeakyReLU' of the activated conv output), then a plain conv nf -> 4 nf backward
             # (g_u2 already carries the LeakyReLU' of u2: HR_conv0's data-gradient applied it as its mask; g_u1 comes out of a plain conv)
@@ -811,7 +834,7 @@ class _Plan:
                                                                           ('model.2.', 'up1', g_u1, self.ps1, self.g_ps1, self.t0h, None, h, w, True)):
                 o = Op()
                 o.op = _lib.OP_PIXUNSHUF
-                o.t[0], o.t[1], o.f[0], o.i[0], o.i[1], o.i[2], o.i[3], o.t[2] = (g_hi.view(), pre.view() if pre is not None else NULL_T, SLOPE, N, 4 * nf,
+                o.t[0], o.t[1], o.f[0], o.i[0], o.i[1], o.i[2], o.i[3], o.t[2] = (g_hi.view(), pre.view() if pre is not None else NULL_T, sl, N, 4 * nf,
                                                                                   hl, wl, g_pre.view())
                 ops.add(o)
                 self._wg3(ops, key, g_pre, src, 4 * nf, nf, hl, wl, hl, wl)

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define DASR_ABI_VERSION 20
+#define DASR_ABI_VERSION 21
 #define DASR_EINVAL (-22)
 #define DASR_ECAPTURE (-16)   /* a launch needed a device allocation (the scratch row of a deterministic grid sum, first use per accumulator and stream) while its stream was being captured */
 
@@ -122,6 +122,28 @@ int dasr_conv_chain(const dasr_conv_params* dev_layers, const dasr_conv_params* 
  * resident). */
 int dasr_rdb_chain(const dasr_conv_params* dev_layers, const dasr_conv_params* host_layers, int32_t nlayers, uint32_t* dev_flags, int32_t* dev_err,
                    void* stream);
+/* ---- fused residual block (ABI 21, csrc/resblock.hip) -----------------------------------------------
+ * Replaces ResNetBlock in mode CNA (codes/SRN/models/modules/block.py:221-251: conv0 -> ReLU -> conv1, x + res_scale * res) of SRResNet
+ * (architecture.py:18-48) in ONE launch: y = x + res_scale * (conv1(act(conv0(x) + b0)) + b1) for nf = 64, 3x3, stride 1, zero padding.
+ * Operands are the bf16 shadow x16 (MFMA operands) and the fp32 stream x32 (the skip); the outputs are the fp32 stream y32 and its bf16 shadow
+ * y16; w0 / w1 are packed as the forward dasr_conv of the same conv (dasr_pack_weights: cout 64, cin 64, 9 taps, mt 2, prec 1).  A workgroup
+ * computes h = bf16(act(conv0 + b0)) for its 16 x 16 output tile plus a one-pixel halo into LDS (halo pixels outside the image are ZERO: conv1's
+ * zero padding of h), then conv1 from there.  The MFMA shape and k order are those of dasr_conv, so h, y32 and y16 are bit-identical to the
+ * two-launch composition dasr_conv(act = 1, slope) -> h, dasr_conv(res1 = x32, alpha = res_scale, beta1 = 1) -> y32 / y16.
+ * h.p != NULL (training): the interior of h (bf16, 64 channels) is also stored -- the ReLU mask of conv0's data gradient and the input of
+ * conv1's weight gradient; NULL (inference): not.  act: `slope` as dasr_conv's act = 1 (0: ReLU).  All tensors NC16HW16, 64 channels, N x H x W. */
+typedef struct {
+    dasr_tensor x16;  dasr_tensor x32;      /* block input: bf16 shadow, fp32 stream */
+    const void* w0;  const float* b0;       /* conv0 (res.0): packed bf16 weights, bias [64] */
+    const void* w1;  const float* b1;       /* conv1 (res.2) */
+    dasr_tensor y32;  dasr_tensor y16;      /* block output: fp32 stream, bf16 shadow.  y32, y16 and h must not overlap each other or an input
+                                             * (a tile reads its neighbours' input halo): DASR_EINVAL */
+    dasr_tensor h;                          /* bf16 h = act(conv0(x) + b0), training only (p == NULL: not stored) */
+    int32_t N, H, W;
+    float res_scale, slope;
+} dasr_resblock_params;
+int dasr_resblock(const dasr_resblock_params* p, void* stream);
+
 /* kernel-variant knobs for A/B runs (bench.py --sweep / --tune); defaults are the tuned choice.
  * key 1 / 2: dense-block conv with Cout = 32 / 64: 12 = LDS-DMA kernel (default for Cout 32), 13 = its 8-wave 32x32-tile form (Cout 64 default: chosen per launch when the 4-wave grid has <= 256 workgroups), 0 = first-generation register-staged kernel,
  *            1 double-buffered LDS, 4/5 8x32 tiles, 6 4x32 tiles, 8/9 row reuse, 10/11 register-staged pipeline;
@@ -457,7 +479,8 @@ enum { DASR_OP_CONV = 1, DASR_OP_WGRAD = 2, DASR_OP_WGRAD_REDUCE = 3, DASR_OP_PA
        /* --wgan with BatchNorm discriminators (round 6).  JVP: t[0] x, t[1] t, i[0..3] N C H W, i[4] group, f[0] slope, p[0] gamma, p[1] beta, p[2] stats, t[2] out.
         * SECOND: t[0] x, t[1] t, t[2] ga, i[0..4] as above, f[0] slope, p[0..2] as above, t[3] out, i[5] accumulate, p[3] dgamma, f[1] pscale */
        DASR_OP_BNORM_JVP = 50, DASR_OP_BNORM_SECOND = 51,
-       DASR_OP_PRELU_FINAL = 52   /* dasr_prelu_final: p[0] partial, i[0] nblocks, l[0] stride, i[1] count, p[1] slopes, p[2] dsts, f[0] scale */ };
+       DASR_OP_PRELU_FINAL = 52,  /* dasr_prelu_final: p[0] partial, i[0] nblocks, l[0] stride, i[1] count, p[1] slopes, p[2] dsts, f[0] scale */
+       DASR_OP_RESBLOCK = 53      /* dasr_resblock: p[0] host dasr_resblock_params (kept alive by the plan) */ };
 
 typedef struct {
     int32_t op;  int32_t i[8];  float f[4];  int64_t l[4];  void* p[4];  dasr_tensor t[5];
