@@ -216,7 +216,7 @@ def lib():
             fn.restype = c_vp if name == 'dasr_event_create' else c_i32
         if L.dasr_abi_version() != ABI_VERSION:
             raise DasrHipError('libdasr_hip.so ABI %d != binding ABI %d; rebuild' % (L.dasr_abi_version(), ABI_VERSION))
-        for kv in [x for x in os.environ.get('DASR_TUNE', '').split(',') if x]:   # A/B of kernel variants without code changes: DASR_TUNE="1=14,2=12"
+        for kv in [x for x in os.environ.get('DASR_TUNE', '').split(',') if x]:   # A/B of kernel variants without code changes: DASR_TUNE="2=12"
             k, v = kv.split('=')
             if L.dasr_set_tuning(int(k), int(v)) != 0:
                 raise DasrHipError('DASR_TUNE: bad tuning key/value %r' % kv)

@@ -38,16 +38,13 @@ def build_bench(force=False, verbose=False):
     return BENCH_LIB
 
 
-def build(force=False, verbose=False, trace=False, ablate=False):
+def build(force=False, verbose=False, trace=False):
     """trace=True: instrumented copy (libdasr_hip_trace.so, -DDASR_TRACE: per-workgroup s_memtime stamps in conv_kernel) for
-    scripts/micro_conv.py; ablate=True: libdasr_hip_ablate.so (-DDASR_BENCH: the wrong-result ablation instantiations of the dense conv /
-    weight-gradient kernels, timing experiments only).  Neither is loaded by the product path unless DASR_HIP_LIB points at it."""
+    scripts/micro_conv.py; not loaded by the product path unless DASR_HIP_LIB points at it."""
     global LIB
     if trace:
         LIB = os.path.join(HERE, 'libdasr_hip_trace.so')
-    if ablate:
-        LIB = os.path.join(HERE, 'libdasr_hip_ablate.so')
-    if not force and not trace and not ablate and not _stale():
+    if not force and not trace and not _stale():
         return LIB
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     objs = []
@@ -57,8 +54,8 @@ def build(force=False, verbose=False, trace=False, ablate=False):
         path = os.path.join(CSRC, src)
         if not os.path.exists(path):
             continue
-        obj = os.path.join(HERE, 'build', src.replace('.hip', '_trace.o' if trace else ('_ablate.o' if ablate else '.o')))
-        cmd = [hipcc, '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-c', path, '-o', obj] + (['-DDASR_TRACE'] if trace else []) + (['-DDASR_BENCH'] if ablate else [])
+        obj = os.path.join(HERE, 'build', src.replace('.hip', '_trace.o' if trace else '.o'))
+        cmd = [hipcc, '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-c', path, '-o', obj] + (['-DDASR_TRACE'] if trace else [])
         procs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
         objs.append(obj)
     for cmd, p in procs:
@@ -77,4 +74,4 @@ if __name__ == '__main__':
     if '--bench' in sys.argv:
         print(build_bench(force='--force' in sys.argv, verbose=True))
     else:
-        print(build(force='--force' in sys.argv, verbose=True, trace='--trace' in sys.argv, ablate='--ablate' in sys.argv))
+        print(build(force='--force' in sys.argv, verbose=True, trace='--trace' in sys.argv))

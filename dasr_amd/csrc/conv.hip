@@ -11,11 +11,10 @@
 // prec 3 ("split bf16"): x = hi + lo with hi = bf16(x), lo = bf16(x - hi); hi*hi + hi*lo + lo*hi
 // gives ~2^-17 relative operand error with three bf16 MFMAs (16x faster than the f32 MFMA).
 #include "common.h"
-#include <type_traits>
 
 namespace {
 
-template <int PREC, bool IN_F32, int MT, int KH, int STRIDE, int NT_, int KS = 1, bool DBUF = false>
+template <int PREC, bool IN_F32, int MT, int KH, int STRIDE, int NT_, int KS = 1>
 struct Cfg {
     static constexpr int NT = NT_;
     static constexpr int RPT = STRIDE == 1 ? 1 : 2;    // output rows per n-tile
@@ -29,8 +28,7 @@ struct Cfg {
     static constexpr int ACT_BYTES = IH * IW * PIXB;
     static constexpr int W_BYTES = KS * NTAPS * MT * 1024;
     static constexpr int NARR = PREC >= 3 ? 2 : 1;
-    static constexpr int BUF_BYTES = NARR * (ACT_BYTES + W_BYTES);
-    static constexpr int LDS_BYTES = (DBUF ? 2 : 1) * BUF_BYTES;
+    static constexpr int LDS_BYTES = NARR * (ACT_BYTES + W_BYTES);
     // staging pieces (16 B of global memory each)
     static constexpr int PPP16 = IN_F32 ? 4 : 2;  // pieces per pixel per 16-channel plane
     static constexpr int PPP = PPP16 * KS;        // pieces per pixel
@@ -46,10 +44,6 @@ struct Cfg {
 constexpr unsigned OOB = 0x80000000u;
 constexpr int RSRC_FLAGS = 0x00020000;
 constexpr int RSRC_RANGE = 0x7fffffff;
-
-#ifndef CHV
-#define CHV 0
-#endif
 
 #ifdef DASR_TRACE
 __device__ unsigned long long* g_trace = nullptr;  // [grid][16]: s_memrealtime at entry, then s_memtime stamps
@@ -105,9 +99,6 @@ __device__ __forceinline__ void mask_prefetch(const dasr_conv_params& p, MaskPre
 // the f32-tensor convs sc1 measured flat or worse (DSN iteration +10 %), so they keep plain stores (profiles/r03_conv_ablation.txt section 5)
 template <bool SC1>
 __device__ __forceinline__ void st128(u32x4 v, __amdgpu_buffer_rsrc_t r, unsigned off) {
-#if defined(IS_ABL) && (IS_ABL & 32)   // (timing experiment: the epilogues' arithmetic without their stores -- out-of-range offsets are dropped by the hardware)
-    off |= OOB;
-#endif
     if constexpr (SC1) __builtin_amdgcn_raw_buffer_store_b128(v, r, off, 0, 16);
     else __builtin_amdgcn_raw_buffer_store_b128(v, r, off, 0, 0);
 }
@@ -118,10 +109,7 @@ __device__ __forceinline__ void st128(u32x4 v, __amdgpu_buffer_rsrc_t r, unsigne
 // barrier of the main loop, in a region no DMA touches) -- no hand-over barrier here
 // CONST_SLOPE: the caller guarantees p.slope_ptr == nullptr (the chained launches validate it): without it hipcc turns `slope_ptr ? *slope_ptr : slope` into an
 // unconditional vector load from a selected address, and its `s_waitcnt vmcnt(0)` drains every LDS-DMA request in flight (rdb_is_kernel: the weights of the next three steps)
-// BMODE / BH (rdb_is_kernel: a conv's flag waits for the acknowledgement of its stores, and the neighbours need only the tile's border): 1 = only the border pixels of the
-// BH x 32-pixel tile are computed and stored (everything else is out of range: no loads, no stores), 2 = the 16-bit output skips the border pixels (already stored by a
-// BMODE 1 call), everything else is complete.  0 = plain.
-template <bool IN_F32, int MT, int NT, int STRIDE, int EPI, int F16OUT = -1, bool PRE = false, bool FSC1 = false, bool BIAS_STAGED = false, bool CONST_SLOPE = false, int BMODE = 0, int BH = 16,
+template <bool IN_F32, int MT, int NT, int STRIDE, int EPI, int F16OUT = -1, bool PRE = false, bool FSC1 = false, bool BIAS_STAGED = false, bool CONST_SLOPE = false,
           bool PACC = false>
 __device__ __forceinline__ void conv_epilogue(const dasr_conv_params& p, f32x16 (&acc)[MT][NT], char* smem, float bias_reg, int tid, int mg, int n,
                                               int oy0, int ox0, const MaskPre<NT * MT>* pre = nullptr) {
@@ -152,7 +140,7 @@ __device__ __forceinline__ void conv_epilogue(const dasr_conv_params& p, f32x16 
     // writes ONE partial per workgroup to p.prelu_part[blockIdx.x]; dasr_prelu_final sums them in a fixed order and divides by a^2 (the layout of dasr_prelu_grad's
     // partials, whose two passes over h and dL/dz this replaces).  PACC: the caller (conv_glds_kernel) instantiates the epilogue twice and takes this one when
     // p.prelu_part is set -- the HR-tail launches of the same kernel run the plain code.
-    constexpr bool PACC_OK = PACC && EPI == 68 && MT == 2 && !IN_F32 && !FSC1 && !PRE && BMODE == 0;
+    constexpr bool PACC_OK = PACC && EPI == 68 && MT == 2 && !IN_F32 && !FSC1 && !PRE;
     static_assert(!PACC || PACC_OK, "the slope-gradient partials exist for the 64-channel mask-only epilogue of the LDS-DMA kernel");
     constexpr bool pacc_on = PACC_OK;
     float pacc = 0.f;
@@ -163,11 +151,7 @@ __device__ __forceinline__ void conv_epilogue(const dasr_conv_params& p, f32x16 
     const __amdgpu_buffer_rsrc_t rob = make_rsrc((bf16_t*)p.out_bf16.p + (size_t)n * p.out_bf16.n_stride);
     const unsigned mask_cb = (unsigned)p.mask.cb_stride, r1_cb = (unsigned)p.res1.cb_stride, r2_cb = (unsigned)p.res2.cb_stride;
     const unsigned of_cb = (unsigned)p.out_f32.cb_stride, ob_cb = (unsigned)p.out_bf16.cb_stride;
-#ifdef IS_PLAIN_ST   // (timing experiment of round 6: what do the write-through stores of the chained epilogues cost?)
-    constexpr bool SC1 = !FSC1 && (MT == 1 && !IN_F32 && F16OUT == 0);
-#else
     constexpr bool SC1 = FSC1 || (MT == 1 && !IN_F32 && F16OUT == 0);   // bf16 dense-block convs with Cout = 32 (st128); FSC1: every store of a chained layer (conv_chain_kernel)
-#endif
     // split 16-bit output: the remainder goes lo_pl planes further (wave-uniform; 0 = plain).  The specialised bf16 epilogues (dense blocks) do not
     // carry the branch: classify_epi sends a bf16 split output to the generic epilogue
     const unsigned lo_pl = (G || F16OUT != 0) ? (unsigned)p.out16_lo : 0u;
@@ -210,8 +194,7 @@ __device__ __forceinline__ void conv_epilogue(const dasr_conv_params& p, f32x16 
             c = nn & 15;
         }
         const int oy = oy0 + r, ox = ox0 + c;
-        bool pv = (oy < p.Hout) & (ox < p.Wout);
-        if constexpr (BMODE == 1) pv &= (r == 0) | (r == BH - 1) | (c == 0) | (c == 31);
+        const bool pv = (oy < p.Hout) & (ox < p.Wout);
         const unsigned pixel = (unsigned)((oy * ostr + p.out_oy) * owid + ox * ostr + p.out_ox) * 16u;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -425,13 +408,8 @@ __device__ __forceinline__ void conv_epilogue(const dasr_conv_params& p, f32x16 
                     u32x4 oa = {__float_as_uint(v[2 * pr][0]), __float_as_uint(v[2 * pr][1]), __float_as_uint(v[2 * pr][2]), __float_as_uint(v[2 * pr][3])};
                     u32x4 ob = {__float_as_uint(v[2 * pr + 1][0]), __float_as_uint(v[2 * pr + 1][1]), __float_as_uint(v[2 * pr + 1][2]), __float_as_uint(v[2 * pr + 1][3])};
                     rows_swap(oa, ob);
-#ifdef IS_F32_PLAIN   // (timing experiment of round 6)
-                    constexpr bool SCF = SC1 && !FSC1;
-#else
-                    constexpr bool SCF = SC1;
-#endif
-                    st128<SCF>(oa, rof, e32[0] != OOB ? (cbv[2 * pr] * of_cb + e32[0]) * 4u : OOB);
-                    st128<SCF>(ob, rof, e32[1] != OOB ? (cbv[2 * pr] * of_cb + e32[1]) * 4u : OOB);
+                    st128<SC1>(oa, rof, e32[0] != OOB ? (cbv[2 * pr] * of_cb + e32[0]) * 4u : OOB);
+                    st128<SC1>(ob, rof, e32[1] != OOB ? (cbv[2 * pr] * of_cb + e32[1]) * 4u : OOB);
                 }
             } else if (has_f32) {
 #pragma unroll
@@ -455,12 +433,7 @@ __device__ __forceinline__ void conv_epilogue(const dasr_conv_params& p, f32x16 
                     const auto r0 = __builtin_amdgcn_permlane32_swap(a[0], b[0], false, false);
                     const auto r1 = __builtin_amdgcn_permlane32_swap(a[1], b[1], false, false);
                     const u32x4 o = {r0[0], r1[0], r0[1], r1[1]};   // lanes 0-31: channels 0-7 of the plane, lanes 32-63: channels 8-15
-                    bool keep = true;
-                    if constexpr (BMODE == 2) {
-                        const int rl = wave * NT + nt;
-                        keep = !((rl == 0) | (rl == BH - 1) | (nn == 0) | (nn == 31));
-                    }
-                    st128<SC1>(o, rob, (eo[2 * pr] != OOB && keep) ? (cbv[2 * pr] * ob_cb + eo[2 * pr] + 4u * kh2) * 2u : OOB);
+                    st128<SC1>(o, rob, eo[2 * pr] != OOB ? (cbv[2 * pr] * ob_cb + eo[2 * pr] + 4u * kh2) * 2u : OOB);
                     if (lo_pl) {   // remainder plane: lo = round16(value - hi)
                         bf16x4 la, lb;
 #pragma unroll
@@ -526,11 +499,9 @@ __device__ __forceinline__ void conv_epilogue(const dasr_conv_params& p, f32x16 
 
 template <int PREC, bool IN_F32, int MT, int KH, int STRIDE, int NT, int KS, bool DBUF, int MODE, int EPI>
 __global__ __launch_bounds__(256, 2) void conv_kernel(const dasr_conv_params p) {
-    constexpr bool RU = MODE == 1, PIPE = MODE == 2;  // PIPE requires DBUF (two LDS buffers)
-    static_assert(!PIPE || (DBUF && PREC == 1 && !IN_F32), "pipelined main loop: bf16 dense-block convs, double-buffered LDS");
-    using C = Cfg<PREC, IN_F32, MT, KH, STRIDE, NT, KS, DBUF>;
+    using C = Cfg<PREC, IN_F32, MT, KH, STRIDE, NT, KS>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    // buffer b: [act_hi | act_lo (prec 3) | w_hi | w_lo (prec 3)]; one 16 B dummy slot after the buffers
+    // LDS: [act_hi | act_lo (prec 3) | w_hi | w_lo (prec 3)]; one 16 B dummy slot behind
     constexpr int ACT_LO = C::ACT_BYTES, W_HI = C::NARR * C::ACT_BYTES, W_LO = W_HI + C::W_BYTES;
     constexpr int DUMMY = C::LDS_BYTES;
 
@@ -602,20 +573,6 @@ __global__ __launch_bounds__(256, 2) void conv_kernel(const dasr_conv_params p) 
 
     u32x4 areg[C::AR];
     u32x4 wreg[C::WR * C::NARR];
-    u32x4 areg2[PIPE ? C::AR : 1], wreg2[PIPE ? C::WR : 1];  // second staging set of the pipelined main loop
-    auto load_set = [&](int ck, u32x4* ar, u32x4* wr) {
-        const unsigned so = (unsigned)ck * in_chunk_bytes, wo = (unsigned)ck * w_chunk_bytes;
-#pragma unroll
-        for (int r = 0; r < C::AR; ++r) ar[r] = __builtin_amdgcn_raw_buffer_load_b128(rin, goff[r], so, 0);
-#pragma unroll
-        for (int r = 0; r < C::WR; ++r) wr[r] = __builtin_amdgcn_raw_buffer_load_b128(rw, woff[r], wo, 0);
-    };
-    // one 16-byte piece of a staged chunk -> LDS (bf16 input): piece i < AR: activations, else weights
-    auto store_piece = [&](char* buf, const u32x4* ar, const u32x4* wr, int i) {
-        if (i < C::AR) *(u32x4*)(buf + loff[i]) = ar[i];
-        else *(u32x4*)(buf + W_HI + wloff[i - C::AR]) = wr[i - C::AR];
-    };
-
     auto load_chunk = [&](int ck) {
         const unsigned so = (unsigned)ck * in_chunk_bytes;
 #pragma unroll
@@ -689,34 +646,6 @@ __global__ __launch_bounds__(256, 2) void conv_kernel(const dasr_conv_params p) 
         const char* act_lo = buf + ACT_LO;
         const char* w_hi = buf + W_HI;
         const char* w_lo = buf + W_LO;
-        if constexpr (RU) {
-            // row reuse (3x3 stride 1, bf16): a wave's NT output rows need NT+2 input rows per kx; each row fragment is read from LDS
-            // once and feeds the MFMAs of the three ky taps -> 3*(NT+2+3*MT) instead of 9*(NT+MT) ds_read_b128 per chunk
-            static_assert(!RU || (KH == 3 && STRIDE == 1 && PREC == 1), "row reuse: 3x3 stride-1 bf16 only");
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx) {
-                    bf16x8 brow[NT + 2], a[3][MT];
-#pragma unroll
-                    for (int rr = 0; rr < NT + 2; ++rr) brow[rr] = *(const bf16x8*)(act_hi + boff[0] + (rr * C::IW + kx) * C::PIXB + ks * 32);
-#pragma unroll
-                    for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                        for (int mi = 0; mi < MT; ++mi)
-                            a[ky][mi] = *(const bf16x8*)(w_hi + ((ks * 9 + ky * 3 + kx) * MT + mi) * 1024 + aoff);
-#pragma unroll
-                    for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                        for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-                            for (int nt = 0; nt < NT; ++nt)
-                                acc[mi][nt] = mfma16<PREC == 2 || PREC == 4>(a[ky][mi], brow[nt + ky], acc[mi][nt]);
-                }
-            }
-            return;
-        }
-        if constexpr (PIPE) return;  // (PIPE uses compute_store below)
         if constexpr ((PREC == 1 && !IN_F32) || (PREC == 2 && MT == 1)) {
             // software pipeline over taps: the fragments of tap t+1 are requested from LDS before the MFMAs of tap t are issued
             // (two register sets), so an MFMA never waits on a ds_read issued just ahead of it (hipcc's own schedule reads
@@ -813,94 +742,22 @@ __global__ __launch_bounds__(256, 2) void conv_kernel(const dasr_conv_params p) 
         }
     };
 
-    // pipelined main loop: MFMAs of tap t | LDS fragment reads of tap t+1 | ds_write of one staged piece of chunk k+1, all in one
-    // instruction stream; global loads run two chunks ahead (two register sets), so neither their latency nor the LDS fill is exposed:
-    // one barrier per chunk
-    auto compute_store = [&](const char* buf, char* nbuf, const u32x4* ar, const u32x4* wr) {
-        constexpr int TOT = KS * C::NTAPS, NP = C::AR + C::WR;
-        const char* act_hi = buf;
-        const char* w_hi = buf + W_HI;
-        bf16x8 fa[2][MT], fb[2][NT];
-        auto ldfrag = [&](int idx, int set) {
-            const int ks = idx / C::NTAPS, t = idx - ks * C::NTAPS;
-            const int ky = t / KH, kx = t - ky * KH;
-            const int toff = (ky * C::IW + kx) * C::PIXB + ks * 32;
-#pragma unroll
-            for (int mi = 0; mi < MT; ++mi) fa[set][mi] = *(const bf16x8*)(w_hi + ((ks * C::NTAPS + t) * MT + mi) * 1024 + aoff);
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) fb[set][nt] = *(const bf16x8*)(act_hi + boff[nt] + toff);
-        };
-        ldfrag(0, 0);
-#pragma unroll
-        for (int idx = 0; idx < TOT; ++idx) {
-            if (idx + 1 < TOT) ldfrag(idx + 1, (idx + 1) & 1);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-                    acc[mi][nt] = mfma16<PREC == 2 || PREC == 4>(fa[idx & 1][mi], fb[idx & 1][nt], acc[mi][nt]);
-            // the NP staged pieces of the next chunk are spread over the taps
-#pragma unroll
-            for (int i = idx * NP / TOT; i < (idx + 1) * NP / TOT; ++i) store_piece(nbuf, ar, wr, i);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-
-    if constexpr (PIPE) {
-        load_set(0, areg, wreg);
-        if (nchunks > 1) load_set(1, areg2, wreg2);
-        TRACE_STAMP(1);
-#pragma unroll
-        for (int i = 0; i < C::AR + C::WR; ++i) store_piece(smem, areg, wreg, i);
-        __syncthreads();
-        TRACE_STAMP(2);
-        char* b0 = smem;
-        char* b1 = smem + C::BUF_BYTES;
-        for (int ck = 0; ck < nchunks; ck += 2) {
-            // even chunk: compute b0, fill b1 from set 2 (chunk ck+1), fetch chunk ck+2 into set 1
-            if (ck + 2 < nchunks) load_set(ck + 2, areg, wreg);
-            compute_store(b0, b1, areg2, wreg2);
-            __syncthreads();
-            if (ck + 1 >= nchunks) break;
-            if (ck + 3 < nchunks) load_set(ck + 3, areg2, wreg2);
-            compute_store(b1, b0, areg, wreg);
-            __syncthreads();
-        }
-        TRACE_STAMP(3);
-    } else {
     load_chunk(0);
     TRACE_STAMP(1);
-    if constexpr (DBUF) {
-        // one barrier per chunk: chunk ck+1 is fetched to registers before, and written to the other LDS
-        // buffer after, the MFMAs of chunk ck
+    for (int ck = 0; ck < nchunks; ++ck) {
+        if (ck == 2) TRACE_STAMP(8);
         store_chunk(smem);
+        if (ck == 2) TRACE_STAMP(9);
         __syncthreads();
-        for (int ck = 0; ck < nchunks; ++ck) {
-            char* cur = smem + (ck & 1) * C::BUF_BYTES;
-            char* nxt = smem + ((ck + 1) & 1) * C::BUF_BYTES;
-            if (ck + 1 < nchunks) load_chunk(ck + 1);
-            compute(cur);
-            if (ck + 1 < nchunks) store_chunk(nxt);
-            __syncthreads();
-        }
-    } else {
-        for (int ck = 0; ck < nchunks; ++ck) {
-            if (ck == 2) TRACE_STAMP(8);
-            store_chunk(smem);
-            if (ck == 2) TRACE_STAMP(9);
-            __syncthreads();
-            if (ck == 0) TRACE_STAMP(2);
-            if (ck == 2) TRACE_STAMP(10);
-            if (ck + 1 < nchunks) load_chunk(ck + 1);
-            if (ck == 2) TRACE_STAMP(11);
-            compute(smem);
-            if (ck == 0) TRACE_STAMP(3);
-            if (ck == 2) TRACE_STAMP(12);
-            __syncthreads();
-            if (ck == 2) TRACE_STAMP(13);
-        }
-    }
+        if (ck == 0) TRACE_STAMP(2);
+        if (ck == 2) TRACE_STAMP(10);
+        if (ck + 1 < nchunks) load_chunk(ck + 1);
+        if (ck == 2) TRACE_STAMP(11);
+        compute(smem);
+        if (ck == 0) TRACE_STAMP(3);
+        if (ck == 2) TRACE_STAMP(12);
+        __syncthreads();
+        if (ck == 2) TRACE_STAMP(13);
     }
     TRACE_STAMP(4);
     if constexpr (PREC == 2 || PREC == 4) {
@@ -947,9 +804,6 @@ struct GCfg {
     static constexpr int W_BYTES = WPIECE * 16;
     static constexpr int BUF_BYTES = ACT_BYTES + W_BYTES;
     static constexpr int LDS_BYTES = 2 * BUF_BYTES;
-    // RING: three activation images + two weight images (the activations are requested TWO chunks ahead, the weights one)
-    static constexpr int RING_W_OFF = 3 * ACT_BYTES, RING_LDS_BYTES = 3 * ACT_BYTES + 2 * W_BYTES;
-    static constexpr int FLAG_OFF = RING_LDS_BYTES, FLAG_BYTES = 32;   // RING = 3: done[4] (16-byte aligned), landed
 };
 
 // one 16-byte-per-lane DMA piece of chunk ck: piece i < AR activations, else weights; the LDS base is wave-uniform.
@@ -970,76 +824,16 @@ __device__ __forceinline__ void glds_dma_piece(int i, int ck, char* buf, __amdgp
     }
 }
 
-// one 1-KiB LDS-DMA instruction of the loader wave (a free function: hipcc drops the host-side kernel handle when the builtin sits in the body of
-// a __global__ template behind `if constexpr` / in a lambda)
-__device__ __forceinline__ void glds_dma_1k(__amdgpu_buffer_rsrc_t rs, char* lds_dst, unsigned voff, unsigned soff) {
-    typedef __attribute__((address_space(3))) void* lds_ptr;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr)lds_dst, 16, voff, soff, 0, 0);
-}
-
-// LDS flag words of the barrier-free form (RING = 3): read / written through inline assembly so that neither the compiler's alias analysis nor its
-// waitcnt pass are involved; the "memory" clobber pins the compute waves' fragment reads on the right side of a poll / publish
-__device__ __forceinline__ int lds_peek(unsigned addr) {
-    int v;
-    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr) : "memory");
-    return __builtin_amdgcn_readfirstlane(v);
-}
-__device__ __forceinline__ void lds_poke(unsigned addr, int v) { asm volatile("ds_write_b32 %0, %1" : : "v"(addr), "v"(v) : "memory"); }
-__device__ __forceinline__ void lds_poke_nc(unsigned addr, int v) { asm volatile("ds_write_b32 %0, %1" : : "v"(addr), "v"(v)); }
-__device__ __forceinline__ int lds_peek_min4_nc(unsigned addr) {   // min of four consecutive words (the loader's view of the compute waves' progress)
-    u32x4 v;
-    asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr));
-    const int a = (int)v[0] < (int)v[1] ? (int)v[0] : (int)v[1], b = (int)v[2] < (int)v[3] ? (int)v[2] : (int)v[3];
-    return __builtin_amdgcn_readfirstlane(a < b ? a : b);
-}
-
-// RING form: activation piece i of chunk ck into the activation image at `abase`; weight piece r of chunk ck into the weight image at `wbase`
-template <int MT, int NW>
-__device__ __forceinline__ void glds_dma_act(int i, int ck, char* abase, __amdgpu_buffer_rsrc_t rin, const unsigned* goff, unsigned in_chunk_bytes, int wave) {
-    using C = GCfg<MT, NW>;
-    typedef __attribute__((address_space(3))) void* lds_ptr;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rin, (lds_ptr)(abase + (i * C::NTH + wave * 64) * 16), 16, goff[i], (unsigned)ck * in_chunk_bytes, 0, 0);
-}
-template <int MT, int NW>
-__device__ __forceinline__ void glds_dma_w(int r, int ck, char* wbase, __amdgpu_buffer_rsrc_t rw, int wave, int tid) {
-    using C = GCfg<MT, NW>;
-    typedef __attribute__((address_space(3))) void* lds_ptr;
-    if (r * C::NTH + wave * 64 < C::WPIECE)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr)(wbase + (r * C::NTH + wave * 64) * 16), 16, (unsigned)(tid + r * C::NTH) * 16u, (unsigned)ck * (9u * MT * 1024u), 0, 0);
-}
-
-// ABL (micro-benchmarks only, results are wrong; instantiated with ABL != 0 only under -DDASR_BENCH = libdasr_hip_ablate.so): bit 0 no DMA inside the main loop, bit 1 no fragment reads inside the main loop
-// (stale registers), bit 2 no vmcnt wait / barrier per chunk, bit 3 no MFMAs: what each component costs per chunk (guide: ablate, don't guess)
 // F16: the 16-bit activations and packed weights are f16 (HR tail of the generator in f16 storage): v_mfma_f32_32x32x16_f16.
 // p.ups: nearest x2 up-sampling folded into the DMA source addresses (upconv_blcok, block.py:854-861): each lane fetches the 16 bytes of
 // low-resolution pixel (y >> 1, x >> 1); the four duplicates come from L2.
-// RING = 1 / 2 / 3 (round 3, dasr_set_tuning key 1 = 15 / 16 / 17): three restructurings of the load path, built against the per-chunk ablation of
-// the step (profiles/r03_conv_ablation.txt), all parity-green and ALL MEASURED FLAT OR SLOWER than the default (RING = 0) -- kept as selectable,
-// tested variants and as the record of what does not limit this kernel (not the depth of the prefetch, not the DMA issue slots of the MFMA waves,
-// not the chunk barrier itself; the L2 -> LDS volume per MFMA is what is paid).
-// The hypothesis of RING = 1: with two chunk buffers a workgroup can request chunk k + 1 only while it multiplies chunk k (0.6 - 1.2 us) and the
-// round trip under load is ~2 us, so every chunk ends waiting.  RING keeps THREE activation images and two weight images in LDS (78 KB: still
-// two workgroups per CU): the activations of chunk k + 2
-// and the weights of chunk k + 1 are requested during chunk k, the wait that ends chunk k is a COUNTED vmcnt (the pieces of chunk k + 2 stay in
-// flight across the barrier) and the barrier is a raw s_barrier (__syncthreads() would drain vmcnt).
-// RING = 2: RING plus ONE LOADER WAVE per workgroup (wave NW): after the prologue it alone issues the LDS-DMA (the 9 weight instructions of chunk
-// k + 1, then the 20 activation instructions of chunk k + 2) and waits for it; the four compute waves only read fragments and multiply.  Measured
-// motivation (profiles/r03_conv_ablation.txt): with the DMA in the compute waves the chunk barrier costs 2.8 us per launch (the waves stall
-// unevenly while issuing into a busy memory pipe and then wait for each other), without DMA the same barrier costs nothing.
-// RING = 3: RING = 2 WITHOUT the chunk barrier.  Two flag words in LDS replace it: the loader publishes `landed` = index of the newest chunk that is
-// complete in LDS, every compute wave publishes done[w] = number of chunks it has finished reading; a compute wave starts chunk k when
-// landed >= k, the loader overwrites the images of chunk k - 1 when min(done) >= k.  The waves of a workgroup may drift up to two chunks apart:
-// what the barrier cost (each wave shares its SIMD with a wave of ANOTHER workgroup in another phase, so the four waves never take the same time
-// for a chunk, and a barrier per chunk pays the maximum every time) averages out.
+// ABL, RING: always 0 (launch_glds pins them; they stay in the signature because the kernel's printed name keys profiles/pmc_*.json).
 template <int MT, int EPI, int NW, int ABL = 0, bool F16 = false, int RING = 0>
-__global__ __launch_bounds__((NW + (RING >= 2 ? 1 : 0)) * 64, RING >= 2 ? 3 : (NW == 4 ? 2 : 1)) void conv_glds_kernel(const dasr_conv_params p) {
+__global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv_glds_kernel(const dasr_conv_params p) {
     using C = GCfg<MT, NW>;
     constexpr int NT = C::NT;
-    constexpr bool LW = RING >= 2, FLAGS = RING == 3;
-    static_assert(!FLAGS || NW == 4, "done[] is read as one 16-byte word");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const bool is_loader = LW && wave == NW;
 #ifdef DASR_TRACE
     if (g_trace && threadIdx.x == 0) g_trace[(size_t)blockIdx.x * 16 + 15] = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -1098,105 +892,15 @@ __global__ __launch_bounds__((NW + (RING >= 2 ? 1 : 0)) * 64, RING >= 2 ? 3 : (N
         const int us = (a_remap >> 8) & 1;   // nearest x2: the conv runs on the (2 Hin) x (2 Win) grid, the source pixel is (gy >> 1, gx >> 1)
         const bool ok = (pp < C::NPIX) & (gy >= 0) & (gy < (a_Hin << us)) & (gx >= 0) & (gx < (a_Win << us));  // bitwise: keeps the prologue one basic block
         goff[r] = ok ? (unsigned)((((gy >> us) * a_Win + (gx >> us)) * 16 + 8 * h) * 2) : OOB;
-        // ABL bit 6: every workgroup reads its activations from the first 256 KB of image 0's planes (cache-resident after the first touch): the
-        // instruction stream, the LDS-DMA count and the output traffic are unchanged, the fabric (MALL / HBM) read traffic is gone
-        if constexpr ((ABL & 64) != 0) goff[r] = ok ? (goff[r] & 0x3ffffu) : OOB;
     }
-    const __amdgpu_buffer_rsrc_t rin = make_rsrc((const bf16_t*)a_in + ((ABL & 64) ? (size_t)0 : (size_t)n * a_nstr));
+    const __amdgpu_buffer_rsrc_t rin = make_rsrc((const bf16_t*)a_in + (size_t)n * a_nstr);
     const unsigned in_chunk_bytes = (unsigned)(a_cbstr * 2);
     const __amdgpu_buffer_rsrc_t rw = make_rsrc((const bf16_t*)a_w + (size_t)mg * nchunks * 9 * MT * 512);
     constexpr int NP = C::AR + C::WR;
-    static_assert(!RING || (C::AR <= 15), "counted vmcnt");
     // chunk 0 is requested before the fragment addresses and accumulators are set up: the DMA round trip overlaps that ALU work
-    if constexpr (RING != 0) {   // issue order = landing order the counted waits rely on: act(0), w(0), act(1)
-        if (!is_loader) {
 #pragma unroll
-            for (int i = 0; i < C::AR; ++i) glds_dma_act<MT, NW>(i, 0, smem, rin, goff, in_chunk_bytes, wave);
-#pragma unroll
-            for (int r = 0; r < C::WR; ++r) glds_dma_w<MT, NW>(r, 0, smem + C::RING_W_OFF, rw, wave, tid);
-            if (nchunks > 1 && !FLAGS) {   // (FLAGS: the loader requests chunk 1 as well, `landed` is then its business alone)
-#pragma unroll
-                for (int i = 0; i < C::AR; ++i) glds_dma_act<MT, NW>(i, 1, smem + C::ACT_BYTES, rin, goff, in_chunk_bytes, wave);
-            }
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < NP; ++i) glds_dma_piece<MT, NW>(i, rot, smem, rin, rw, goff, in_chunk_bytes, wave, tid, rot);
-    }
+    for (int i = 0; i < NP; ++i) glds_dma_piece<MT, NW>(i, rot, smem, rin, rw, goff, in_chunk_bytes, wave, tid, rot);
     TRACE_STAMP(1);
-    if constexpr (LW) {
-        if (is_loader) {
-            // ---- loader wave: every DMA instruction after the prologue.  Activation instruction j (0 .. AR*NW-1) fills LDS bytes [1024 j, 1024 j + 1024) of an
-            // activation image (pieces q = 64 j + lane), weight instruction j (0 .. 9 MT - 1) bytes [1024 j, ...) of a weight image
-            constexpr int NA = C::AR * NW, NWI = C::WPIECE / 64;
-            static_assert(C::WPIECE % 64 == 0 && NA + NWI + NA <= 63, "vmcnt is a 6-bit counter");
-            unsigned lgoff[NA];
-#pragma unroll
-            for (int j = 0; j < NA; ++j) {
-                const int q = lane + 64 * j;
-                const int pp = q >> 1, h = (q & 1) ^ ((pp >> 3) & 1);
-                const int iy = pp / C::IW, ix = pp - iy * C::IW;
-                const int gy = iy0 + iy, gx = ix0 + ix;
-                const int us = (a_remap >> 8) & 1;
-                const bool ok = (pp < C::NPIX) & (gy >= 0) & (gy < (a_Hin << us)) & (gx >= 0) & (gx < (a_Win << us));
-                lgoff[j] = ok ? (unsigned)((((gy >> us) * a_Win + (gx >> us)) * 16 + 8 * h) * 2) : OOB;
-            }
-            constexpr int WAIT_A = 0x0F70 | (NA & 15) | ((NA >> 4) << 14);   // s_waitcnt vmcnt(NA)
-            if constexpr (FLAGS) {
-                const unsigned flags = (unsigned)(size_t)(DASR_LDS char*)smem + C::FLAG_OFF;
-                __builtin_amdgcn_s_setprio(3);   // a late request stalls four waves, a late MFMA one
-                lds_poke_nc(flags + 4 * (lane & 7), 0);   // done[0..3] = 0, landed = 0 (chunk 0: the prologue barrier), three spare words
-                if (nchunks > 1) {
-#pragma unroll
-                    for (int j = 0; j < NA; ++j) glds_dma_1k(rin, smem + C::ACT_BYTES + j * 1024, lgoff[j], in_chunk_bytes);
-                }
-                asm volatile("s_waitcnt lgkmcnt(0)");
-                __builtin_amdgcn_s_barrier();   // chunk 0 (requested by the compute waves) is in LDS, the flags are initialised
-                int aslot = 0;
-                for (int ck = 0; ck + 1 < nchunks; ++ck) {
-                    char* nwbuf = smem + C::RING_W_OFF + ((ck + 1) & 1) * C::W_BYTES;
-                    char* nabuf = smem + (aslot == 0 ? 2 : aslot - 1) * C::ACT_BYTES;
-                    const bool more2 = ck + 2 < nchunks;
-                    // the weight image of chunk ck + 1 and the activation image of chunk ck + 2 were last read for chunk ck - 1
-                    while (ck > 0 && lds_peek_min4_nc(flags) < ck) __builtin_amdgcn_s_sleep(1);
-#pragma unroll
-                    for (int j = 0; j < NWI; ++j) glds_dma_1k(rw, nwbuf + j * 1024, (unsigned)(lane + 64 * j) * 16u, (unsigned)(ck + 1) * (9u * MT * 1024u));
-                    if (more2) {
-#pragma unroll
-                        for (int j = 0; j < NA; ++j) glds_dma_1k(rin, nabuf + j * 1024, lgoff[j], (unsigned)(ck + 2) * in_chunk_bytes);
-                        __builtin_amdgcn_s_waitcnt(WAIT_A);   // the weights of chunk ck + 1 and (requested a chunk ago) its activations have landed
-                    } else {
-                        __builtin_amdgcn_s_waitcnt(0x0F70);
-                    }
-                    lds_poke_nc(flags + 16, ck + 1);   // landed = ck + 1
-                    aslot = aslot == 2 ? 0 : aslot + 1;
-                }
-                __builtin_amdgcn_s_barrier();   // pairs with the compute waves' barrier in front of the epilogue (which reuses LDS)
-                return;
-            }
-            __builtin_amdgcn_s_barrier();   // chunk 0 (requested by the compute waves) is in LDS
-            int aslot = 0;
-            for (int ck = 0; ck < nchunks; ++ck) {
-                char* nwbuf = smem + C::RING_W_OFF + ((ck + 1) & 1) * C::W_BYTES;
-                char* nabuf = smem + (aslot == 0 ? 2 : aslot - 1) * C::ACT_BYTES;
-                const bool more = ck + 1 < nchunks, more2 = ck + 2 < nchunks;
-                if (more) {
-#pragma unroll
-                    for (int j = 0; j < NWI; ++j) glds_dma_1k(rw, nwbuf + j * 1024, (unsigned)(lane + 64 * j) * 16u, (unsigned)(ck + 1) * (9u * MT * 1024u));
-                }
-                if (more2) {
-#pragma unroll
-                    for (int j = 0; j < NA; ++j) glds_dma_1k(rin, nabuf + j * 1024, lgoff[j], (unsigned)(ck + 2) * in_chunk_bytes);
-                    __builtin_amdgcn_s_waitcnt(WAIT_A);   // the weights of chunk ck + 1 and (requested a chunk ago) its activations have landed
-                } else {
-                    __builtin_amdgcn_s_waitcnt(0x0F70);
-                }
-                __builtin_amdgcn_s_barrier();
-                aslot = aslot == 2 ? 0 : aslot + 1;
-            }
-            return;
-        }
-    }
     // ---- fragment read addresses: row rr (0..5) of this wave's 6 input rows, column shift kx; lane (nn, kh2)
     const int nn = lane & 31, kh2 = lane >> 5;
     int baddr[6][3];
@@ -1215,7 +919,7 @@ __global__ __launch_bounds__((NW + (RING >= 2 ? 1 : 0)) * 64, RING >= 2 ? 3 : (N
     // (profiles/r03_conv_ablation.txt).  The residual is fetched HERE instead, straight into the accumulator registers -- all 32 loads of a wave
     // (128 KB per workgroup) in flight behind the DMA of chunk 0 -- and the MFMAs accumulate on top of (beta1 / alpha) * x; the epilogue only
     // scales by alpha and stores.  fp32 throughout: alpha * ((beta1 / alpha) x + conv) differs from alpha * conv + beta1 * x by ~1e-7 relative.
-    constexpr bool R1_PRE = MT == 2 && EPI != 0 && (EPI & 8) && !(ABL & 63) && RING == 0;
+    constexpr bool R1_PRE = MT == 2 && EPI != 0 && (EPI & 8);
     if constexpr (R1_PRE) {
         const __amdgpu_buffer_rsrc_t rr1 = make_rsrc((const float*)p.res1.p + (size_t)n * p.res1.n_stride);
         const unsigned r1_cb = (unsigned)p.res1.cb_stride;
@@ -1244,14 +948,8 @@ __global__ __launch_bounds__((NW + (RING >= 2 ? 1 : 0)) * 64, RING >= 2 ? 3 : (N
                 for (int j = 0; j < 16; ++j) acc[mi][nt][j] = 0.f;
     }
 
-    if constexpr (RING != 0) {
-        if (nchunks > 1 && !FLAGS) __builtin_amdgcn_s_waitcnt(0x0F70 | C::AR);   // vmcnt(AR): chunk 0 has landed, the activation pieces of chunk 1 may fly
-        else __builtin_amdgcn_s_waitcnt(0x0F70);
-        __builtin_amdgcn_s_barrier();
-    } else {
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this wave's DMA pieces have landed
-        __syncthreads();
-    }
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this wave's DMA pieces have landed
+    __syncthreads();
     if constexpr (R1_PRE) {
         const float c1 = p.beta1 / p.alpha;
 #pragma unroll
@@ -1261,25 +959,14 @@ __global__ __launch_bounds__((NW + (RING >= 2 ? 1 : 0)) * 64, RING >= 2 ? 3 : (N
     }
     TRACE_STAMP(2);
 
-    constexpr bool PRE = EPI == 68 && MT == 1 && !(ABL & 63) && RING < 2;   // (the loader-wave form runs three waves per SIMD: no registers left for the prefetched mask)
+    constexpr bool PRE = EPI == 68 && MT == 1;
     MaskPre<NT * MT> mpre;
     bf16x8 fb[2][6], fa[2][MT];
-    int aslot = 0;   // RING: activation image of the current chunk (ck % 3)
-    const unsigned flag_base = (unsigned)(size_t)(DASR_LDS char*)smem + C::FLAG_OFF;
-    int landed_seen = 0;
     for (int ck = 0; ck < nchunks; ++ck) {
-        if constexpr (FLAGS) {   // chunk ck is complete in LDS once the loader has published landed >= ck (peeked during the previous chunk: rarely a wait)
-            while (landed_seen < ck) {
-                landed_seen = lds_peek(flag_base + 16);
-                if (landed_seen < ck) __builtin_amdgcn_s_sleep(1);
-            }
-        }
-        const char* buf = RING != 0 ? smem + aslot * C::ACT_BYTES : smem + (ck & 1) * C::BUF_BYTES;                   // activation image
-        const char* wbuf = RING != 0 ? smem + C::RING_W_OFF + (ck & 1) * C::W_BYTES : buf + C::ACT_BYTES;            // weight image
+        const char* buf = smem + (ck & 1) * C::BUF_BYTES;   // activation image
+        const char* wbuf = buf + C::ACT_BYTES;              // weight image
         char* nbuf = smem + ((ck + 1) & 1) * C::BUF_BYTES;
-        char* nwbuf = smem + C::RING_W_OFF + ((ck + 1) & 1) * C::W_BYTES;                                            // RING: weights of chunk ck + 1
-        char* nabuf = smem + (aslot == 0 ? 2 : aslot - 1) * C::ACT_BYTES;                                            // RING: activations of chunk ck + 2 -> the image chunk ck - 1 used
-        const bool more = ck + 1 < nchunks, more2 = ck + 2 < nchunks;
+        const bool more = ck + 1 < nchunks;
         if constexpr (PRE) {
             if (!more) mask_prefetch<MT, NT>(p, mpre, tid, mg, n, oy0, ox0);   // last chunk: the memory pipe is idle, the epilogue finds the mask in registers
         }
@@ -1287,17 +974,14 @@ __global__ __launch_bounds__((NW + (RING >= 2 ? 1 : 0)) * 64, RING >= 2 ? 3 : (N
         const int ckp = ckn >= in_wrap ? ckn - in_wrap : ckn;                            // ... and the input plane group it reads
         if (ck == 2) TRACE_STAMP(8);
         // step s = kx * 3 + ky; B rows of phase kx live in fb[kx & 1], A of step s in fa[s & 1]
-        const bool rd = !(ABL & 2) || ck == 0;   // ablation: fragments are read in the first chunk only
-        if (rd) {
 #pragma unroll
-            for (int rr = 0; rr < 6; ++rr) fb[0][rr] = *(const bf16x8*)(buf + baddr[rr][0]);
+        for (int rr = 0; rr < 6; ++rr) fb[0][rr] = *(const bf16x8*)(buf + baddr[rr][0]);
 #pragma unroll
-            for (int mi = 0; mi < MT; ++mi) fa[0][mi] = *(const bf16x8*)(wbuf + aoff + (0 * MT + mi) * 1024);
-        }
+        for (int mi = 0; mi < MT; ++mi) fa[0][mi] = *(const bf16x8*)(wbuf + aoff + (0 * MT + mi) * 1024);
 #pragma unroll
         for (int s = 0; s < 9; ++s) {
             const int kx = s / 3, ky = s - kx * 3;
-            if (s + 1 < 9 && rd) {
+            if (s + 1 < 9) {
                 const int kx1 = (s + 1) / 3, ky1 = (s + 1) - kx1 * 3;
 #pragma unroll
                 for (int mi = 0; mi < MT; ++mi) fa[(s + 1) & 1][mi] = *(const bf16x8*)(wbuf + aoff + ((ky1 * 3 + kx1) * MT + mi) * 1024);
@@ -1306,66 +990,27 @@ __global__ __launch_bounds__((NW + (RING >= 2 ? 1 : 0)) * 64, RING >= 2 ? 3 : (N
                     for (int rr = 0; rr < 6; ++rr) fb[(kx + 1) & 1][rr] = *(const bf16x8*)(buf + baddr[rr][kx + 1]);
                 }
             }
-            if constexpr (LW) {
-                // (the loader wave issues every DMA instruction)
-            } else if constexpr (RING != 0) {   // issue order: the weights of chunk ck + 1 first, then the activations of chunk ck + 2 (the counted wait below)
-                if (s < 4 && !(ABL & 1)) {
-#pragma unroll
-                    for (int j = s * NP / 4; j < (s + 1) * NP / 4; ++j) {
-                        if (j < C::WR) {
-                            if (more) glds_dma_w<MT, NW>(j, ck + 1, nwbuf, rw, wave, tid);
-                        } else if (more2) {
-                            glds_dma_act<MT, NW>(j - C::WR, ck + 2, nabuf, rin, goff, in_chunk_bytes, wave);
-                        }
-                    }
-                }
-            } else if (more && s < 4 && !(ABL & 1)) {  // all pieces of the next chunk are requested in the first steps: they have the rest of the chunk to land
+            if (more && s < 4) {  // all pieces of the next chunk are requested in the first steps: they have the rest of the chunk to land
 #pragma unroll
                 for (int i = s * NP / 4; i < (s + 1) * NP / 4; ++i) glds_dma_piece<MT, NW>(i, ckn, nbuf, rin, rw, goff, in_chunk_bytes, wave, tid, ckp);
             }
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (!(ABL & 8)) {
 #pragma unroll
-                for (int mi = 0; mi < MT; ++mi)
+            for (int mi = 0; mi < MT; ++mi)
 #pragma unroll
-                    for (int nt = 0; nt < NT; ++nt)
-                        acc[mi][nt] = mfma16<F16>(fa[s & 1][mi], fb[kx & 1][nt + ky], acc[mi][nt]);
-            } else {
-#pragma unroll
-                for (int mi = 0; mi < MT; ++mi) asm volatile("" ::"v"(fa[s & 1][mi]));
-#pragma unroll
-                for (int rr = 0; rr < 6; ++rr) asm volatile("" ::"v"(fb[kx & 1][rr]));
-            }
+                for (int nt = 0; nt < NT; ++nt)
+                    acc[mi][nt] = mfma16<F16>(fa[s & 1][mi], fb[kx & 1][nt + ky], acc[mi][nt]);
             __builtin_amdgcn_sched_barrier(0);
         }
         if (ck == 2) TRACE_STAMP(9);
-        if constexpr (FLAGS) {
-            lds_poke(flag_base + 4 * wave, ck + 1);            // done[wave]: this wave has read everything it needs of chunk ck
-            if (more) landed_seen = lds_peek(flag_base + 16);  // (the round trip overlaps the MFMAs still in the pipe)
-            aslot = aslot == 2 ? 0 : aslot + 1;
-        } else if constexpr (LW) {
-            if (ck == 0) __builtin_amdgcn_s_waitcnt(0x0F70);   // this wave's activation pieces of chunk 1 (the prologue's); later chunks: the loader waits
-            __builtin_amdgcn_s_barrier();
-            aslot = aslot == 2 ? 0 : aslot + 1;
-        } else if constexpr (RING != 0) {
-            // chunk ck + 1 (its activations were requested a whole chunk ago, its weights at the top of this one) has landed once only the AR
-            // activation pieces of chunk ck + 2 are still outstanding
-            if (more2) __builtin_amdgcn_s_waitcnt(0x0F70 | C::AR);
-            else __builtin_amdgcn_s_waitcnt(0x0F70);
-            __builtin_amdgcn_s_barrier();   // every wave's pieces of chunk ck + 1 are in LDS; every wave is done reading chunk ck
-            aslot = aslot == 2 ? 0 : aslot + 1;
-        } else if constexpr (!(ABL & 4)) {
-            if constexpr (!(ABL & 16)) __builtin_amdgcn_s_waitcnt(0x0F70);   // ABL bit 4: the barrier without the DMA wait
-            if (ck == 2) TRACE_STAMP(10);
-            if constexpr (ABL & 32) __builtin_amdgcn_s_barrier();              // ABL bit 5 (with bit 4): raw s_barrier instead of __syncthreads()
-            else __syncthreads();
-        }
+        __builtin_amdgcn_s_waitcnt(0x0F70);
+        if (ck == 2) TRACE_STAMP(10);
+        __syncthreads();
         if (ck == 2) TRACE_STAMP(11);
     }
     TRACE_STAMP(4);
-    if constexpr (FLAGS) __builtin_amdgcn_s_barrier();   // the waves drift: nobody may still read fragments when the epilogue reuses LDS for the bias
     if constexpr (EPI == 68 && MT == 2 && !PRE) {   // (the DSN generator's data-gradient convs also leave the PReLU-slope partials: dasr_conv_params::prelu_part)
-        if (p.prelu_part) conv_epilogue<false, MT, NT, 1, EPI, F16 ? 1 : 0, false, false, false, false, 0, 16, true>(p, acc, smem, bias_reg, tid, mg, n, oy0, ox0, &mpre);
+        if (p.prelu_part) conv_epilogue<false, MT, NT, 1, EPI, F16 ? 1 : 0, false, false, false, false, true>(p, acc, smem, bias_reg, tid, mg, n, oy0, ox0, &mpre);
         else conv_epilogue<false, MT, NT, 1, EPI, F16 ? 1 : 0, PRE>(p, acc, smem, bias_reg, tid, mg, n, oy0, ox0, &mpre);
     } else {
         conv_epilogue<false, MT, NT, 1, R1_PRE ? (EPI & ~8) : EPI, F16 ? 1 : 0, PRE>(p, acc, smem, bias_reg, tid, mg, n, oy0, ox0, &mpre);
@@ -1558,68 +1203,40 @@ __device__ __forceinline__ void chain_layer(const dasr_conv_params& p, char* sme
         if constexpr (PRE) {
             if (!more) mask_prefetch<MT, NT>(p, mpre, tid, 0, n, oy0, ox0);
         }
-        // CHV (compile-time, -DCHV=bits; 0 in the product): loop experiments of round 5, measured on the chain's launch duration (profiles/r05_chain_variants.txt).
-        // bit 0: the DMA pieces of the next chunk spread over the steps (one or two per step) instead of all in steps 0-3; bit 1: weight fragments read two
-        // steps ahead; bit 2: no sched_barrier around the MFMA groups.  Diagnostics with WRONG results: bit 3 no chunk barrier, bit 4 no DMA after chunk 0,
-        // bit 5 no MFMA, bit 6 no fragment reads after chunk 0.  (Also tried, in git history only: conv5 storing and publishing its 16-bit shadow in front of the
-        // fp32 stream -- 29.53-29.57 vs 29.46-29.49 ms per step; plain instead of write-through stores for that fp32 stream, which only the same tile reads again --
-        // 29.44-29.53 vs 29.33-29.46 ms.)
-        constexpr int V = CHV;
-        constexpr int FAD = (V & 2) ? 3 : 2;
-        bf16x8 fa3[3][MT];
-        const bool rd = !(V & 64) || ck == 0;
-        if (rd) {
+        // (Measured in round 5 and not kept, profiles/r05_chain_variants.txt: other spreads of the DMA pieces over the steps, weight fragments read two
+        // steps ahead, no sched_barrier; conv5 storing and publishing its 16-bit shadow in front of the fp32 stream; plain stores for that stream.)
+        // Only fa[0] / fa[1] are used.  The third set exists to steer the compiler: with fa[2][MT] hipcc schedules and allocates this loop differently,
+        // so the size is kept at 3 to preserve the code object that was measured (profiles/r05_chain_trace.txt).  Do not shrink it without re-measuring.
+        bf16x8 fa[3][MT];
 #pragma unroll
-            for (int rr = 0; rr < 6; ++rr) fb[0][rr] = *(const bf16x8*)(buf + baddr[rr][0]);
+        for (int rr = 0; rr < 6; ++rr) fb[0][rr] = *(const bf16x8*)(buf + baddr[rr][0]);
 #pragma unroll
-            for (int mi = 0; mi < MT; ++mi) fa3[0][mi] = *(const bf16x8*)(wbuf + aoff + (0 * MT + mi) * 1024);
-            if constexpr (V & 2) {
-#pragma unroll
-                for (int mi = 0; mi < MT; ++mi) fa3[1][mi] = *(const bf16x8*)(wbuf + aoff + ((1 * 3 + 0) * MT + mi) * 1024);   // step 1: kx 0, ky 1
-            }
-        }
+        for (int mi = 0; mi < MT; ++mi) fa[0][mi] = *(const bf16x8*)(wbuf + aoff + (0 * MT + mi) * 1024);
 #pragma unroll
         for (int s = 0; s < 9; ++s) {
             const int kx = s / 3, ky = s - kx * 3;
-            const int sa = s + FAD - 1;   // weight fragment requested in this step
-            if (sa < 9 && rd) {
-                const int kxa = sa / 3, kya = sa - kxa * 3;
+            if (s + 1 < 9) {
+                const int kx1 = (s + 1) / 3, ky1 = (s + 1) - kx1 * 3;
 #pragma unroll
-                for (int mi = 0; mi < MT; ++mi) fa3[sa % FAD][mi] = *(const bf16x8*)(wbuf + aoff + ((kya * 3 + kxa) * MT + mi) * 1024);
-            }
-            if (s + 1 < 9 && rd) {
+                for (int mi = 0; mi < MT; ++mi) fa[(s + 1) & 1][mi] = *(const bf16x8*)(wbuf + aoff + ((ky1 * 3 + kx1) * MT + mi) * 1024);
                 if (ky == 1 && kx < 2) {
 #pragma unroll
                     for (int rr = 0; rr < 6; ++rr) fb[(kx + 1) & 1][rr] = *(const bf16x8*)(buf + baddr[rr][kx + 1]);
                 }
             }
-            if (more && !((V & 16))) {
-                if constexpr (V & 1) {
-                    if (s < 8) {
+            if (more && s < 4) {
 #pragma unroll
-                        for (int i = s * NP / 8; i < (s + 1) * NP / 8; ++i) glds_dma_piece<MT, NW>(i, ck + 1, nbuf, rin, rw, goff, in_chunk_bytes, wave, tid, ck + 1);
-                    }
-                } else if (s < 4) {
-#pragma unroll
-                    for (int i = s * NP / 4; i < (s + 1) * NP / 4; ++i) glds_dma_piece<MT, NW>(i, ck + 1, nbuf, rin, rw, goff, in_chunk_bytes, wave, tid, ck + 1);
-                }
+                for (int i = s * NP / 4; i < (s + 1) * NP / 4; ++i) glds_dma_piece<MT, NW>(i, ck + 1, nbuf, rin, rw, goff, in_chunk_bytes, wave, tid, ck + 1);
             }
-            if constexpr (!(V & 4)) __builtin_amdgcn_sched_barrier(0);
-            if constexpr (!(V & 32)) {
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int mi = 0; mi < MT; ++mi)
+            for (int mi = 0; mi < MT; ++mi)
 #pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) acc[mi][nt] = mfma16<F16>(fa3[s % FAD][mi], fb[kx & 1][nt + ky], acc[mi][nt]);
-            } else {
-#pragma unroll
-                for (int mi = 0; mi < MT; ++mi) asm volatile("" ::"v"(fa3[s % FAD][mi]));
-#pragma unroll
-                for (int rr = 0; rr < 6; ++rr) asm volatile("" ::"v"(fb[kx & 1][rr]));
-            }
-            if constexpr (!(V & 4)) __builtin_amdgcn_sched_barrier(0);
+                for (int nt = 0; nt < NT; ++nt) acc[mi][nt] = mfma16<F16>(fa[s & 1][mi], fb[kx & 1][nt + ky], acc[mi][nt]);
+            __builtin_amdgcn_sched_barrier(0);
         }
         __builtin_amdgcn_s_waitcnt(0x0F70);
-        if constexpr (!(V & 8)) __syncthreads();
+        __syncthreads();
     }
     const unsigned long long t_d = CH_T();
     conv_epilogue<false, MT, NT, 1, R1_PRE ? (EPI & ~8) : EPI, F16 ? 1 : 0, PRE, true>(p, acc, smem, bias_reg, tid, 0, n, oy0, ox0, &mpre);
@@ -1697,487 +1314,19 @@ __global__ __launch_bounds__(256, 2) void conv_chain_kernel(const dasr_conv_para
     }
 }
 
-#ifdef DASR_BENCH
-// ---------------------------------------------------------------------------------------------------
-// conv_chain2_kernel (round 5; libdasr_hip_ablate.so only, -DDASR_BENCH): the chained launch, second form -- BUILT, PARITY-GREEN (bit-identical on 512, 1024
-// and 1536 tiles), AND MEASURED SLOWER than conv_chain_kernel: 10.3 vs 9.1 ms per chain at configs[1] (profiles/r05_chain_trace.txt: the early chunk-0 request
-// queues the epilogue's stores behind eight 1-KiB LDS-DMA instructions, epilogue 4 k -> 14.5 k cycles per item), and at configs[2] (two tiles per
-// workgroup) the GAN step went from 72 to 88 ms against one launch per conv.  Kept as the record of the experiment, like the ring / loader forms of round 3.
-//  Same arithmetic, same tile / XCD / flag protocol as conv_chain_kernel; what changes is
-// what a workgroup does BETWEEN two main loops (~7 us of a ~18 us Cout-32 layer had the matrix pipe idle) and how many tiles it owns:
-//  * work items.  A workgroup owns `tpw` tiles (tiles j, j + 64, ... of its XCD's tile list) and walks the items (layer 0, tile 0), (layer 0, tile 1), ...,
-//    (layer 1, tile 0), ...: batches of 512 * tpw tiles (configs[2]: 32 crops of 128 x 128 = 1024) run chained too, not only the exact fit of configs[1].
-//    A wait always refers to an item that is strictly earlier in (layer, slot) order, so the walk cannot deadlock.
-//  * chunk 0 of the NEXT item is requested in front of the epilogue of the current one whenever it holds only planes that are at least two layers old
-//    (every item but conv1 of a dense block, whose 64 input channels all come from the layer before): the DMA round trip (~2 us under load) and the
-//    epilogue's store drain overlap, and the barrier that ends `publish` is also the barrier that says "chunk 0 is in LDS" -- the next main loop starts
-//    at once.  LDS: chunk k lives in buffer k & 1 at a FIXED offset (the 64-channel layout) for both workgroup shapes, all chunk counts are even, so the
-//    last chunk of an item sits in buffer 1 and buffer 0 is free when its main loop ends.
-//  * the bias is handed round through a 256-byte LDS area outside the chunk buffers, written in front of the LAST chunk barrier of the main loop: no
-//    separate hand-over barrier in the epilogue.
-//  * the neighbour-flag poll in the middle of a layer happens in front of the chunk barrier that precedes the first dependent request instead of
-//    bringing its own barrier.
-// Barriers per item: chunks + 1 (V1: chunks + 4).  Bit-identical results (same MFMA order, same epilogue arithmetic).
-// ---------------------------------------------------------------------------------------------------
-struct Chain2 {
-    static constexpr int BUF1 = GCfg<2, 4>::BUF_BYTES;              // offset of buffer 1 for BOTH workgroup shapes
-    static constexpr int XOFF = 2 * BUF1;                            // extra area: bias[64] floats, then f0[8] words
-    static constexpr int LDS_BYTES = XOFF + 512;
-    static constexpr int MAX_TPW = 8;
-};
-
-
-// the eight neighbours of tile (ty, tx) have published `target`: polled by lanes 0..8 of wave 0 (no barrier of its own: the caller's next barrier hands the
-// result to the other waves)
-__device__ __forceinline__ void chain_poll(const ChainSync& cs, int layer, int tid) {
-    if (layer > 0 && tid < 9 && tid != 4) {
-        const int y = cs.ty + tid / 3 - 1, x = cs.tx + tid % 3 - 1;
-        if ((y >= 0) & (y < cs.tiles_y) & (x >= 0) & (x < cs.tiles_x)) {
-            const unsigned off = (unsigned)(cs.base + y * cs.tiles_x + x) * 4u, target = cs.f0 + (unsigned)layer;
-            int spins = 0;
-            while ((int)(__builtin_amdgcn_raw_buffer_load_b32(cs.rflags, off, 0, 17) - target) < 0) {
-                __builtin_amdgcn_s_sleep(2);
-                ++spins;
-                if (spins > (1 << 21) || ((spins & 1023) == 0 && __builtin_amdgcn_raw_buffer_load_b32(make_rsrc(cs.err), 0, 0, 17) != 0)) {
-                    atomicOr(cs.err, 2);
-                    break;
-                }
-            }
-        }
-    }
-}
-
-struct ChainNext {        // the item behind the current one, if its chunk 0 may be requested early.  Plain scalars, fetched from the layer table by the kernel
-    bool on;              // body (scalar loads through the __restrict__ kernel argument; through a pointer kept in a struct hipcc falls back to vector loads
-    const void* in;       // and a waterfall loop around the buffer descriptor)
-    long long n_stride;
-    const void* w;
-    int mt, n, oy0, ox0;
-};
-
-// chunk 0 (activations of tile (n, oy0, ox0) + weights) of the next item's layer into LDS buffer 0; mt = workgroup shape of that layer (run-time: the
-// requesting item may have the other one); Hin, Win: the chain's one geometry
-__device__ __forceinline__ void chain_request_chunk0(const ChainNext& nx, int Hin, int Win, char* smem, int tid, int wave) {
-    using C = GCfg<1, 4>;
-    typedef __attribute__((address_space(3))) void* lds_ptr;
-    const __amdgpu_buffer_rsrc_t rin = make_rsrc((const bf16_t*)nx.in + (size_t)nx.n * nx.n_stride);
-    const __amdgpu_buffer_rsrc_t rw = make_rsrc(nx.w);
-    const int mt = nx.mt, oy0 = nx.oy0, ox0 = nx.ox0;
-#pragma unroll
-    for (int r = 0; r < C::AR; ++r) {
-        const int q = tid + r * C::NTH;
-        const int pp = q >> 1, h = (q & 1) ^ ((pp >> 3) & 1);
-        const int iy = pp / C::IW, ix = pp - iy * C::IW;
-        const int gy = oy0 - 1 + iy, gx = ox0 - 1 + ix;
-        const bool ok = (pp < C::NPIX) & (gy >= 0) & (gy < Hin) & (gx >= 0) & (gx < Win);
-        const unsigned go = ok ? (unsigned)(((gy * Win + gx) * 16 + 8 * h) * 2) : OOB;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rin, (lds_ptr)(smem + (r * C::NTH + wave * 64) * 16), 16, go, 0, 0, 0);
-    }
-    const int wpiece = 9 * mt * 64;
-#pragma unroll
-    for (int r = 0; r < GCfg<2, 4>::WR; ++r) {
-        if (r * C::NTH + wave * 64 < wpiece)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr)(smem + C::ACT_BYTES + (r * C::NTH + wave * 64) * 16), 16, (unsigned)(tid + r * C::NTH) * 16u, 0, 0, 0);
-    }
-}
-
-template <int MT, int EPI, bool F16>
-__device__ __forceinline__ void chain_item(const dasr_conv_params& p, char* smem, const int tid, const int n, const int oy0, const int ox0, const int dep_chunk,
-                                           const ChainSync& cs, const int layer, const bool have0, const ChainNext& nx) {
-    using C = GCfg<MT, 4>;
-    constexpr int NT = C::NT, NW = 4;
-    constexpr int TYPE = MT == 2 ? 2 : -1;
-    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int nchunks = p.cin >> 4;
-    const int ttype = TYPE >= 0 ? TYPE : (dep_chunk <= 1 ? 0 : 1);
-    (void)ttype;
-    const unsigned long long t_a = CH_T();
-    float bias_reg;
-    {
-        const unsigned bo = ((p.bias != nullptr) & (tid < 32 * MT)) ? (unsigned)tid * 4u : OOB;
-        bias_reg = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(make_rsrc(p.bias), bo, 0, 0));
-    }
-    const __amdgpu_buffer_rsrc_t rin = make_rsrc((const bf16_t*)p.in.p + (size_t)n * p.in.n_stride);
-    const unsigned in_chunk_bytes = (unsigned)(p.in.cb_stride * 2);
-    const __amdgpu_buffer_rsrc_t rw = make_rsrc(p.w);
-    constexpr int NP = C::AR + C::WR;
-    unsigned goff[C::AR];
-#pragma unroll
-    for (int r = 0; r < C::AR; ++r) {
-        const int q = tid + r * C::NTH;
-        const int pp = q >> 1, h = (q & 1) ^ ((pp >> 3) & 1);
-        const int iy = pp / C::IW, ix = pp - iy * C::IW;
-        const int gy = oy0 - 1 + iy, gx = ox0 - 1 + ix;
-        const bool ok = (pp < C::NPIX) & (gy >= 0) & (gy < p.Hin) & (gx >= 0) & (gx < p.Win);
-        goff[r] = ok ? (unsigned)(((gy * p.Win + gx) * 16 + 8 * h) * 2) : OOB;
-    }
-    if (!have0) {
-        if (dep_chunk <= 1) {   // every input plane comes from the previous layer (conv1 of a dense block): the neighbours first
-            chain_poll(cs, layer, tid);
-            if (layer > 0) __syncthreads();
-        }
-#pragma unroll
-        for (int i = 0; i < NP; ++i) glds_dma_piece<MT, NW>(i, 0, smem, rin, rw, goff, in_chunk_bytes, wave, tid, 0);
-    }
-    const unsigned long long t_b = CH_T();
-    const int nn = lane & 31, kh2 = lane >> 5;
-    int baddr[6][3];
-#pragma unroll
-    for (int rr = 0; rr < 6; ++rr)
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-            const int pp = (wave * NT + rr) * C::IW + nn + kx;
-            baddr[rr][kx] = ((pp << 1) + (kh2 ^ ((pp >> 3) & 1))) << 4;
-        }
-    const int aoff = lane * 16;
-    f32x16 acc[MT][NT];
-    constexpr bool R1_PRE = MT == 2 && (EPI & 8);   // conv5: the fp32 residual lands in the accumulators (see conv_glds_kernel)
-    if constexpr (R1_PRE) {
-        const __amdgpu_buffer_rsrc_t rr1 = make_rsrc((const float*)p.res1.p + (size_t)n * p.res1.n_stride);
-        const unsigned r1_cb = (unsigned)p.res1.cb_stride;
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const int oy = oy0 + wave * NT + nt, ox = ox0 + nn;
-            const bool pv = (oy < p.Hout) & (ox < p.Wout);
-            const unsigned pixel = (unsigned)(oy * p.Wout + ox) * 16u;
-#pragma unroll
-            for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int oc = mi * 32 + 8 * g + 4 * kh2;
-                    const u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(rr1, pv ? ((unsigned)(oc >> 4) * r1_cb + pixel + (unsigned)(oc & 15)) * 4u : OOB, 0, 0);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[mi][nt][4 * g + j] = __uint_as_float(t[j]);
-                }
-        }
-    } else {
-#pragma unroll
-        for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int j = 0; j < 16; ++j) acc[mi][nt][j] = 0.f;
-    }
-    if (!have0) {   // (have0: the previous item's publish waited for this wave's pieces and its barrier covered all four waves)
-        __builtin_amdgcn_s_waitcnt(0x0F70);
-        __syncthreads();
-    }
-    if constexpr (R1_PRE) {
-        const float c1 = p.beta1 / p.alpha;
-#pragma unroll
-        for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) acc[mi][nt] *= c1;
-    }
-    const unsigned long long t_c = CH_T();
-    unsigned long long t_poll = 0;
-    (void)t_poll;
-    constexpr bool PRE = EPI == 68 && MT == 1;
-    MaskPre<NT * MT> mpre;
-    bf16x8 fb[2][6], fa[2][MT];
-    float* bl = (float*)(smem + Chain2::XOFF);
-    for (int ck = 0; ck < nchunks; ++ck) {
-        const char* buf = smem + (ck & 1) * Chain2::BUF1;
-        const char* wbuf = buf + C::ACT_BYTES;
-        char* nbuf = smem + ((ck + 1) & 1) * Chain2::BUF1;
-        const bool more = ck + 1 < nchunks;
-        if constexpr (PRE) {
-            if (!more) mask_prefetch<MT, NT>(p, mpre, tid, 0, n, oy0, ox0);
-        }
-#pragma unroll
-        for (int rr = 0; rr < 6; ++rr) fb[0][rr] = *(const bf16x8*)(buf + baddr[rr][0]);
-#pragma unroll
-        for (int mi = 0; mi < MT; ++mi) fa[0][mi] = *(const bf16x8*)(wbuf + aoff + (0 * MT + mi) * 1024);
-#pragma unroll
-        for (int s = 0; s < 9; ++s) {
-            const int kx = s / 3, ky = s - kx * 3;
-            if (s + 1 < 9) {
-                const int kx1 = (s + 1) / 3, ky1 = (s + 1) - kx1 * 3;
-#pragma unroll
-                for (int mi = 0; mi < MT; ++mi) fa[(s + 1) & 1][mi] = *(const bf16x8*)(wbuf + aoff + ((ky1 * 3 + kx1) * MT + mi) * 1024);
-                if (ky == 1 && kx < 2) {
-#pragma unroll
-                    for (int rr = 0; rr < 6; ++rr) fb[(kx + 1) & 1][rr] = *(const bf16x8*)(buf + baddr[rr][kx + 1]);
-                }
-            }
-            if (more && s < 4) {
-#pragma unroll
-                for (int i = s * NP / 4; i < (s + 1) * NP / 4; ++i) glds_dma_piece<MT, NW>(i, ck + 1, nbuf, rin, rw, goff, in_chunk_bytes, wave, tid, ck + 1);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) acc[mi][nt] = mfma16<F16>(fa[s & 1][mi], fb[kx & 1][nt + ky], acc[mi][nt]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (ck + 2 == dep_chunk) {   // the request after next is the first that holds the previous layer's output: the neighbours must have published it
-            const unsigned long long t0 = CH_T();
-            chain_poll(cs, layer, tid);
-            t_poll += CH_T() - t0;
-        }
-        if (!more && tid < 32 * MT) bl[tid] = bias_reg;   // bias hand-over rides on the last chunk barrier
-        __builtin_amdgcn_s_waitcnt(0x0F70);
-        __syncthreads();
-    }
-    const unsigned long long t_d = CH_T();
-    if (nx.on) chain_request_chunk0(nx, p.Hin, p.Win, smem, tid, wave);   // buffer 0 is free: the last chunk (odd index) sat in buffer 1
-    conv_epilogue<false, MT, NT, 1, R1_PRE ? (EPI & ~8) : EPI, F16 ? 1 : 0, PRE, true, true>(p, acc, (char*)bl, bias_reg, tid, 0, n, oy0, ox0, &mpre);
-    const unsigned long long t_e = CH_T();
-    cs.publish(layer, tid);
-    const unsigned long long t_f = CH_T();
-    CH_ACC(ttype, 0, t_b - t_a);
-    CH_ACC(ttype, 1, t_c - t_b);
-    CH_ACC(ttype, 2, t_d - t_c);
-    CH_ACC(ttype, 3, t_poll);
-    CH_ACC(ttype, 4, t_e - t_d);
-    CH_ACC(ttype, 5, t_f - t_e);
-    CH_ACC(ttype, 6, 1ull);
-    CH_ACC(ttype, 7, (unsigned long long)nchunks);
-    (void)t_a; (void)t_b; (void)t_c; (void)t_d; (void)t_e; (void)t_f;
-}
-
-template <bool F16, bool BWD>
-__global__ __launch_bounds__(256, 2) void conv_chain2_kernel(const dasr_conv_params* __restrict__ layers, const int* __restrict__ dep_chunk, int nlayers,
-                                                            int tiles_y, int tiles_x, unsigned* flags, unsigned* tickets, int* err, int tpw) {
-    using C = GCfg<1, 4>;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x;
-    const int T = tiles_y * tiles_x;
-    unsigned xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    const int xcd = (int)(xcc & 7u);
-    const int quota = (int)(gridDim.x >> 3);
-    int* xi = (int*)(smem + Chain2::XOFF + 256);   // [0..7] f0 of this workgroup's tiles, [8] ticket
-    const __amdgpu_buffer_rsrc_t rflags = make_rsrc(flags);
-    if (tid == 0) xi[8] = (int)(atomicAdd(tickets + xcd, 1u) % (unsigned)quota);
-    __syncthreads();
-    const int j = __builtin_amdgcn_readfirstlane(xi[8]);
-    if (tid < tpw) {   // stage base of every tile this workgroup owns (the flag words count on from launch to launch)
-        const int idx = j + quota * tid;
-        const int img = idx / T, tile = idx - img * T;
-        xi[tid] = (int)__builtin_amdgcn_raw_buffer_load_b32(rflags, (unsigned)((xcd + 8 * img) * T + tile) * 4u, 0, 17);
-    }
-    __syncthreads();
-    CH_WHERE(j, xcc);
-    bool have0 = false;
-    for (int L = 0; L < nlayers; ++L) {
-        const dasr_conv_params& p = layers[L];
-        const int dep = dep_chunk[L];
-        for (int slot = 0; slot < tpw; ++slot) {
-            const int idx = j + quota * slot;
-            const int img = idx / T, tile = idx - img * T;
-            const int n = xcd + 8 * img;                        // all tiles of image n on XCD n % 8
-            const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-            ChainSync cs;
-            cs.rflags = rflags;
-            cs.err = err;
-            cs.base = n * T;
-            cs.ty = ty, cs.tx = tx, cs.tiles_y = tiles_y, cs.tiles_x = tiles_x;
-            cs.f0 = (unsigned)__builtin_amdgcn_readfirstlane(xi[slot]);
-            const int oy0 = ty * C::TH, ox0 = tx * C::TW;
-            // the item behind this one: (L, slot + 1), or (L + 1, 0); its chunk 0 may be requested early iff it holds old planes only
-            ChainNext nx;
-            {
-                const bool same = slot + 1 < tpw;
-                const int Ln = same ? L : L + 1, sn = same ? slot + 1 : 0;
-                const int Lc = Ln < nlayers ? Ln : nlayers - 1;
-                const dasr_conv_params& pn = layers[Lc];
-                const int idn = j + quota * sn;
-                const int imn = idn / T, tin = idn - imn * T;
-                const int tyn = tin / tiles_x, txn = tin - tyn * tiles_x;
-                nx.on = Ln < nlayers && dep_chunk[Lc] > 1;
-                nx.in = pn.in.p, nx.n_stride = pn.in.n_stride, nx.w = pn.w, nx.mt = pn.mt;
-                nx.n = xcd + 8 * imn, nx.oy0 = tyn * C::TH, nx.ox0 = txn * C::TW;
-            }
-            if constexpr (BWD) {
-                if (p.mt == 1) chain_item<1, 68, F16>(p, smem, tid, n, oy0, ox0, dep, cs, L, have0, nx);
-                else if (p.res2.p != nullptr) chain_item<2, 248, F16>(p, smem, tid, n, oy0, ox0, dep, cs, L, have0, nx);
-                else chain_item<2, 232, F16>(p, smem, tid, n, oy0, ox0, dep, cs, L, have0, nx);
-            } else {
-                if (p.mt == 1) chain_item<1, 67, F16>(p, smem, tid, n, oy0, ox0, dep, cs, L, have0, nx);
-                else if (p.res2.p != nullptr) chain_item<2, 249, F16>(p, smem, tid, n, oy0, ox0, dep, cs, L, have0, nx);
-                else chain_item<2, 233, F16>(p, smem, tid, n, oy0, ox0, dep, cs, L, have0, nx);
-            }
-            have0 = nx.on;
-        }
-    }
-}
-
-#endif  // DASR_BENCH (conv_chain2_kernel)
-
-// ---------------------------------------------------------------------------------------------------
-// Dense-block convolution, third generation ("ring3"): Cout = 32 (MT = 1), 8 waves, 32 x 32 output pixels per workgroup, one workgroup
-// per CU.  Same LDS image, fragment reuse and epilogue as conv_glds_kernel; what changes is the staging pipeline:
-//  * THREE chunk buffers in a ring (3 x 48 KiB).  The DMA of chunk k+2 is issued while chunk k is multiplied, and the top of chunk k
-//    waits only for chunk k's own pieces with a COUNTED vmcnt (the six pieces of chunk k+1 stay in flight across the barrier), so the
-//    memory pipe is never drained inside the main loop and a chunk's transfer has two chunk times to land instead of a fraction of one.
-//  * a chunk is exactly 48 DMA instructions of 1 KiB: 37 activation (34 x 34 halo tile x 16 ch), 9 weight, 2 padding; wave w issues
-//    slots w, w+8, ..., w+40, i.e. every wave has the same six instructions per chunk in flight (uniform vmcnt arithmetic).
-//  * raw s_barrier (a __syncthreads() would drain vmcnt while LDS-DMA is pending).
-// 160 B of DMA per MFMA instead of 200 (halo and weights amortised over twice the pixels of the 4-wave tile).
-// ---------------------------------------------------------------------------------------------------
-struct G3 {
-    static constexpr int NW = 8, NTH = 512, NT = 4, TH = 32, TW = 32, IH = 34, IW = 34, NPIX = IH * IW;
-    static constexpr int ACT_SLOTS = 37, W_SLOTS = 9, SLOTS = 48, PPW = 6;   // 1 KiB DMA instructions per chunk / per wave
-    static constexpr int BUF_BYTES = SLOTS * 1024, W_OFF = ACT_SLOTS * 1024, LDS_BYTES = 3 * BUF_BYTES;
-};
-
-template <int EPI>
-__global__ __launch_bounds__(512, 1) void conv_ring3_kernel(const dasr_conv_params p) {
-    using C = G3;
-    constexpr int NT = C::NT, MT = 1;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    typedef __attribute__((address_space(3))) void* lds_ptr;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int tiles_x = (p.Wout + C::TW - 1) / C::TW, tiles_y = (p.Hout + C::TH - 1) / C::TH;
-    int bid = blockIdx.x;
-    {
-        const int total = gridDim.x;
-        if ((p.xcd_remap & 1) && (total & 7) == 0) bid = (bid & 7) * (total >> 3) + (bid >> 3);
-    }
-    const int tx = bid % tiles_x;
-    bid /= tiles_x;
-    const int ty = bid % tiles_y;
-    const int n = bid / tiles_y;
-    const int oy0 = ty * C::TH, ox0 = tx * C::TW;
-    const int iy0 = oy0 - 1, ix0 = ox0 - 1;
-    const int nchunks = p.cin >> 4;
-    float bias_reg = 0.f;
-    {
-        const unsigned bo = ((p.bias != nullptr) & (tid < 32) & (tid < p.cout)) ? (unsigned)tid * 4u : OOB;
-        bias_reg = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(make_rsrc(p.bias), bo, 0, 0));
-    }
-    // ---- the wave's six DMA slots: global byte offset of this lane's 16 bytes (chunk-independent part)
-    unsigned goff[C::PPW];
-#pragma unroll
-    for (int i = 0; i < C::PPW; ++i) {
-        const int s = wave + 8 * i;
-        if (s < C::ACT_SLOTS) {  // piece q -> pixel pp = q >> 1, stored half q & 1 holds channel half (q & 1) ^ bit3(pp)
-            const int q = s * 64 + lane;
-            const int pp = q >> 1, h = (q & 1) ^ ((pp >> 3) & 1);
-            const int iy = pp / C::IW, ix = pp - iy * C::IW;
-            const int gy = iy0 + iy, gx = ix0 + ix;
-            const bool ok = (pp < C::NPIX) & (gy >= 0) & (gy < p.Hin) & (gx >= 0) & (gx < p.Win);
-            goff[i] = ok ? (unsigned)(((gy * p.Win + gx) * 16 + 8 * h) * 2) : OOB;
-        } else if (s < C::ACT_SLOTS + C::W_SLOTS) {
-            goff[i] = (unsigned)(((s - C::ACT_SLOTS) * 64 + lane) * 16);
-        } else {
-            goff[i] = OOB;  // padding slot: zero fill of an unused KiB, keeps the per-wave instruction count uniform
-        }
-    }
-    const __amdgpu_buffer_rsrc_t rin = make_rsrc((const bf16_t*)p.in.p + (size_t)n * p.in.n_stride);
-    const unsigned in_chunk_bytes = (unsigned)(p.in.cb_stride * 2);
-    const __amdgpu_buffer_rsrc_t rw = make_rsrc((const bf16_t*)p.w);
-    // per-slot descriptor and chunk stride, chosen once (wave-uniform scalar selects, no branches in the main loop)
-    __amdgpu_buffer_rsrc_t rs[C::PPW];
-    unsigned cstride[C::PPW];
-#pragma unroll
-    for (int i = 0; i < C::PPW; ++i) {
-        const bool isw = wave + 8 * i >= C::ACT_SLOTS;
-        rs[i] = isw ? rw : rin;
-        cstride[i] = isw ? 9216u : in_chunk_bytes;
-    }
-    auto dma = [&](int i, int ck, char* buf) {
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs[i], (lds_ptr)(buf + (wave + 8 * i) * 1024), 16, goff[i], (unsigned)ck * cstride[i], 0, 0);
-    };
-#pragma unroll
-    for (int i = 0; i < C::PPW; ++i) dma(i, 0, smem);
-    if (nchunks > 1) {
-#pragma unroll
-        for (int i = 0; i < C::PPW; ++i) dma(i, 1, smem + C::BUF_BYTES);
-    }
-    // ---- fragment read addresses (same swizzled image as conv_glds_kernel)
-    const int nn = lane & 31, kh2 = lane >> 5;
-    int baddr[6][3];
-#pragma unroll
-    for (int rr = 0; rr < 6; ++rr)
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-            const int pp = (wave * NT + rr) * C::IW + nn + kx;
-            baddr[rr][kx] = ((pp << 1) + (kh2 ^ ((pp >> 3) & 1))) << 4;
-        }
-    const int aoff = C::W_OFF + lane * 16;
-    f32x16 acc[MT][NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int j = 0; j < 16; ++j) acc[0][nt][j] = 0.f;
-
-    int bsel = 0;  // ring position of chunk ck
-    for (int ck = 0; ck < nchunks; ++ck) {
-        // chunk ck's pieces (this wave's) have landed once at most the six pieces of chunk ck+1 are outstanding
-        if (ck + 1 < nchunks) __builtin_amdgcn_s_waitcnt(0x0F76);  // vmcnt(6)
-        else __builtin_amdgcn_s_waitcnt(0x0F70);                    // vmcnt(0)
-        __builtin_amdgcn_s_barrier();   // every wave's pieces of chunk ck are in LDS; every wave is done reading chunk ck-1
-        const char* buf = smem + bsel * C::BUF_BYTES;
-        const int nsel = bsel == 0 ? 2 : bsel - 1;   // (bsel + 2) % 3: the buffer chunk ck-1 was read from
-        char* nbuf = smem + nsel * C::BUF_BYTES;
-        auto body = [&](auto more_c) {   // two straight-line copies: with / without the DMA of chunk ck+2
-            constexpr bool MORE = decltype(more_c)::value;
-            bf16x8 fb[2][6], fa[2][MT];
-#pragma unroll
-            for (int rr = 0; rr < 6; ++rr) fb[0][rr] = *(const bf16x8*)(buf + baddr[rr][0]);
-            fa[0][0] = *(const bf16x8*)(buf + aoff);
-#pragma unroll
-            for (int s = 0; s < 9; ++s) {
-                const int kx = s / 3, ky = s - kx * 3;
-                if (s + 1 < 9) {
-                    const int kx1 = (s + 1) / 3, ky1 = (s + 1) - kx1 * 3;
-                    fa[(s + 1) & 1][0] = *(const bf16x8*)(buf + aoff + (ky1 * 3 + kx1) * 1024);
-                    if (ky == 1 && kx < 2) {
-#pragma unroll
-                        for (int rr = 0; rr < 6; ++rr) fb[(kx + 1) & 1][rr] = *(const bf16x8*)(buf + baddr[rr][kx + 1]);
-                    }
-                }
-                if (MORE && s >= 1 && s <= C::PPW) dma(s - 1, ck + 2, nbuf);   // one piece per step, behind the first step's fragment reads
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-                    acc[0][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s & 1][0], fb[kx & 1][nt + ky], acc[0][nt], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        };
-        if (ck + 2 < nchunks) body(std::true_type{});
-        else body(std::false_type{});
-        bsel = bsel == 2 ? 0 : bsel + 1;
-    }
-    __builtin_amdgcn_s_barrier();   // all fragment reads done before the epilogue reuses LDS for the bias
-    conv_epilogue<false, MT, NT, 1, EPI>(p, acc, smem, bias_reg, tid, 0, n, oy0, ox0);
-}
-
-template <int EPI = 0>
-int launch_ring3(const dasr_conv_params& p, hipStream_t s) {
-    using C = G3;
-    static bool attr_set = false;
-    auto kfn = conv_ring3_kernel<EPI>;
-    if ((p.cin & 15) || p.kh != 3 || p.stride != 1 || p.pad != 1 || p.ups || p.in_f32 || p.prec != 1 || (p.pad_x >= 0 && p.pad_x != 1) || p.in_stride > 1 ||
-        p.cout > 32 || p.mt != 1 || p.prelu_part)
-        return DASR_EINVAL;
-    if (!attr_set) {
-        HIP_TRY(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES));
-        attr_set = true;
-    }
-    const int tiles_x = (p.Wout + C::TW - 1) / C::TW, tiles_y = (p.Hout + C::TH - 1) / C::TH;
-    const long long grid = (long long)tiles_x * tiles_y * p.N;
-    if (grid <= 0 || grid > 0x7fffffffLL) return DASR_EINVAL;
-    DASR_LAUNCH_TAG(__PRETTY_FUNCTION__, kfn, dim3((unsigned)grid), dim3(C::NTH), C::LDS_BYTES, s, p);
-    return (int)hipGetLastError();
-}
-
 template <int MT, int EPI = 0, int NW = 4, int ABL = 0, bool F16 = false, int RING = 0>
 int launch_glds(const dasr_conv_params& p, hipStream_t s) {
+    // ABL / RING stay in the signature only because bench.py and profiles/pmc_*.json key on the printed name (conv_glds_kernel<2, 0, 4, 0, true, 0>)
+    static_assert(ABL == 0 && RING == 0, "one dense-block conv kernel");
     using C = GCfg<MT, NW>;
     static bool attr_set = false;
     auto kfn = conv_glds_kernel<MT, EPI, NW, ABL, F16, RING>;
-    constexpr int LDS = RING == 3 ? C::RING_LDS_BYTES + C::FLAG_BYTES : (RING != 0 ? C::RING_LDS_BYTES : C::LDS_BYTES);
-    constexpr int NTHREADS = C::NTH + (RING >= 2 ? 64 : 0);
     if ((p.cin & 15) || p.kh != 3 || p.stride != 1 || p.pad != 1 || p.in_f32 || p.prec != (F16 ? 2 : 1) || (p.pad_x >= 0 && p.pad_x != 1) || p.in_stride > 1)
         return DASR_EINVAL;
     if (p.out_bf16.p && (p.out16_f16 != 0) != F16) return DASR_EINVAL;   // the 16-bit output format of this kernel is its operand format (compile time)
-    if (p.prelu_part && !(EPI == 68 && MT == 2 && RING == 0 && ABL == 0)) return DASR_EINVAL;   // the slope-gradient partials exist in the 64-channel mask-only epilogue alone
+    if (p.prelu_part && !(EPI == 68 && MT == 2)) return DASR_EINVAL;   // the slope-gradient partials exist in the 64-channel mask-only epilogue alone
     if (!attr_set) {
-        HIP_TRY(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+        HIP_TRY(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES));
         attr_set = true;
     }
     const int cout_tiles = (p.cout + 31) >> 5;
@@ -2187,13 +1336,15 @@ int launch_glds(const dasr_conv_params& p, hipStream_t s) {
     if (grid <= 0 || grid >= (1LL << 20)) return DASR_EINVAL;
     dasr_conv_params q = p;
     q.xcd_remap = (p.xcd_remap & 0xfff) | (int)((unsigned)grid << 12);   // bits 12-31: the grid size (conv_glds_kernel reads it instead of gridDim.x)
-    DASR_LAUNCH_TAG(__PRETTY_FUNCTION__, kfn, dim3((unsigned)grid), dim3(NTHREADS), LDS, s, q);
+    DASR_LAUNCH_TAG(__PRETTY_FUNCTION__, kfn, dim3((unsigned)grid), dim3(C::NTH), C::LDS_BYTES, s, q);
     return (int)hipGetLastError();
 }
 
 template <int PREC, bool IN_F32, int MT, int KH, int STRIDE, int NT, int KS = 1, bool DBUF = false, int MODE = 0, int EPI = 0>
 int launch(const dasr_conv_params& p, hipStream_t s) {
-    using C = Cfg<PREC, IN_F32, MT, KH, STRIDE, NT, KS, DBUF>;
+    // KS / DBUF / MODE stay in the signature only because bench.py and profiles/pmc_*.json key on the printed name (conv_kernel<3, true, 1, 3, 1, 4, 1, false, 0, 0>)
+    static_assert(KS == 1 && !DBUF && MODE == 0, "one staging form of the register-staged kernel");
+    using C = Cfg<PREC, IN_F32, MT, KH, STRIDE, NT, KS>;
     static bool attr_set = false;
     auto kfn = conv_kernel<PREC, IN_F32, MT, KH, STRIDE, NT, KS, DBUF, MODE, EPI>;
     if (p.cin % (16 * KS)) return DASR_EINVAL;
@@ -2263,14 +1414,9 @@ int classify_epi(const dasr_conv_params& p) {
     return e;
 }
 
-// kernel-variant selection (A/B-able from the host: dasr_set_tuning)
-int g_tune_rot = 0;  // chunk-order rotation of the LDS-DMA dense-block conv (A/B)
-#ifdef DASR_BENCH
-int g_chain_form = 1;  // chained launches: 1 = conv_chain_kernel for the exact fit of 512 tiles, conv_chain2_kernel for multiples; 2 = conv_chain2_kernel always
-#endif
-int g_tune_is_th = 0;   // dasr_set_tuning key 10: force the tile height of the input-stationary chained launch (16 / 8 / 4 / 2; 0 = the rule of dasr_rdb_chain)
-int g_tune_is_stagger = 0;   // rdb_is_kernel: start offset between XCDs (units of ~4 us)
-int g_tune_rdb32 = 12, g_tune_rdb64 = 13, g_tune_stream = 0, g_tune_xcd = 1, g_tune_epi = 1;  // Cout=64: 13 = 8-wave form for launches of <= 256 four-wave workgroups (worth 1-2 % of the step under two sub-batch streams)
+// workgroup-shape rule of the Cout = 64 dense-block convs (dasr_set_tuning key 2): 13 = the 8-wave form for launches of <= 256 four-wave workgroups
+// (worth 1-2 % of the step under two sub-batch streams), 12 = always 4 waves
+int g_tune_rdb64 = 13;
 
 #include "rdb_is.h"
 
@@ -2283,26 +1429,11 @@ extern "C" int dasr_debug_set_trace(void* buf) {
 #endif
 
 extern "C" int dasr_set_tuning(int32_t key, int32_t value) {
-    if (key == 9 && value >= 0 && value <= 64) { g_tune_is_stagger = value; return 0; }   // rdb_is_kernel: XCD start stagger
-    if (key == 10 && (value == 0 || value == 4 || value == 8 || value == 16)) { g_tune_is_th = value; return 0; }   // rdb_is_kernel: forced tile height (experiments)
-#ifndef DASR_BENCH
-    // product library: one dense-block conv kernel; the only live choice is the workgroup shape rule of the Cout = 64 launches (key 2)
+    // one dense-block conv kernel: the only live choice is the workgroup-shape rule of the Cout = 64 launches (key 2); keys 1 / 3-6 accept the one
+    // value the library is built for
     if (key == 2 && (value == 12 || value == 13)) { g_tune_rdb64 = value; return 0; }
     if ((key == 1 && value == 12) || (key == 3 && value == 0) || (key == 4 && value == 1) || (key == 5 && value == 1) || (key == 6 && value == 0)) return 0;
-    return DASR_EINVAL;   // the A/B variants of rounds 1-3 live in libdasr_hip_ablate.so (python -m dasr_amd.build --ablate)
-#else
-    switch (key) {
-        case 1: g_tune_rdb32 = value; return 0;   // Cout=32 dense conv: 12 LDS-DMA kernel (default), 13 its 8-wave 32x32-tile form, 14-17 ring / loader / flag forms;
-                                                   // first-generation kernel: 0 single LDS buffer, 1 double, 4/5 8x32 tiles, 6 4x32 tiles, 8/9 row reuse, 10/11 register-staged pipeline
-        case 2: g_tune_rdb64 = value; return 0;   // Cout=64 dense conv: same codes as key 1
-        case 3: g_tune_stream = value; return 0;  // split-bf16 stream conv: 0 single, 1 double
-        case 4: g_tune_xcd = value; return 0;     // XCD-aware tile order on/off
-        case 5: g_tune_epi = value; return 0;     // compile-time specialised epilogues on/off
-        case 6: g_tune_rot = value; return 0;     // LDS-DMA dense conv: per-workgroup chunk-order rotation on/off
-        case 7: if (value != 1 && value != 2) return DASR_EINVAL; g_chain_form = value; return 0;   // form of the chained launches
-        default: return DASR_EINVAL;
-    }
-#endif
+    return DASR_EINVAL;
 }
 
 // host_layers: the same nlayers parameter blocks the device array holds (the launcher validates them; the kernel reads the device copy)
@@ -2329,18 +1460,8 @@ extern "C" int dasr_conv_chain(const dasr_conv_params* dev_layers, const dasr_co
     const int tiles_x = (p0.Wout + C::TW - 1) / C::TW, tiles_y = (p0.Hout + C::TH - 1) / C::TH;
     const long long ntiles = (long long)tiles_x * tiles_y * p0.N;
     const long long grid = 512;   // the launch fills the chip exactly (2 workgroups x 256 CUs, all resident): see the ticket comment in the kernels
-    if ((p0.N & 7) || ntiles < grid || ntiles % grid) return DASR_EINVAL;   // whole images per XCD; every workgroup owns ntiles / 512 tiles
-    const int tpw = (int)(ntiles / grid);
-#ifdef DASR_BENCH
-    const bool form2 = g_chain_form == 2 || tpw > 1;
-    if (form2) {
-        if (tpw > Chain2::MAX_TPW) return DASR_EINVAL;
-        for (int i = 0; i < nlayers; ++i)
-            if ((host_layers[i].cin >> 4) & 1) return DASR_EINVAL;   // even chunk counts: the last chunk of an item sits in LDS buffer 1 (conv_chain2_kernel)
-    }
-#else
-    if (tpw != 1) return DASR_EINVAL;   // the product library runs the exact fit only (the multi-tile form measured slower than one launch per conv)
-#endif
+    // whole images per XCD, one tile per workgroup (a multi-tile form measured slower than one launch per conv: profiles/r05_chain_trace.txt)
+    if ((p0.N & 7) || ntiles != grid) return DASR_EINVAL;
     {
         static int n_cu = -1;   // (a partitioned device -- CPX / DPX -- exposes fewer CUs per logical GPU: the launch would not be resident as a whole)
         if (n_cu < 0) {
@@ -2366,27 +1487,6 @@ extern "C" int dasr_conv_chain(const dasr_conv_params* dev_layers, const dasr_co
         DASR_LAUNCH_TAG(NAME, kfn, dim3((unsigned)grid), dim3(256), C::LDS_BYTES, s, dev_layers, (const int*)dev_dep_chunk, (int)nlayers, tiles_y, tiles_x, \
                         dev_flags, dev_flags + grid, dev_err);                                                                                           \
     }
-#ifdef DASR_BENCH
-    static bool attr2_set[4] = {false, false, false, false};
-#define DASR_CHAIN2_LAUNCH(F16_, BWD_, NAME)                                                                                                             \
-    {                                                                                                                                                    \
-        auto kfn = conv_chain2_kernel<F16_, BWD_>;                                                                                                       \
-        if (!attr2_set[v]) {                                                                                                                             \
-            HIP_TRY(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, Chain2::LDS_BYTES));                               \
-            attr2_set[v] = true;                                                                                                                         \
-        }                                                                                                                                                \
-        DASR_LAUNCH_TAG(NAME, kfn, dim3((unsigned)grid), dim3(256), Chain2::LDS_BYTES, s, dev_layers, (const int*)dev_dep_chunk, (int)nlayers, tiles_y, tiles_x, \
-                        dev_flags, dev_flags + ntiles, dev_err, tpw);                                                                                    \
-    }
-    if (form2) {
-        if (v == 0) DASR_CHAIN2_LAUNCH(false, false, "conv_chain2_kernel<false, false>")
-        else if (v == 1) DASR_CHAIN2_LAUNCH(true, false, "conv_chain2_kernel<true, false>")
-        else if (v == 2) DASR_CHAIN2_LAUNCH(false, true, "conv_chain2_kernel<false, true>")
-        else DASR_CHAIN2_LAUNCH(true, true, "conv_chain2_kernel<true, true>")
-        return (int)hipGetLastError();
-    }
-#undef DASR_CHAIN2_LAUNCH
-#endif
     if (v == 0) DASR_CHAIN_LAUNCH(false, false, "conv_chain_kernel<false, false>")
     else if (v == 1) DASR_CHAIN_LAUNCH(true, false, "conv_chain_kernel<true, false>")
     else if (v == 2) DASR_CHAIN_LAUNCH(false, true, "conv_chain_kernel<false, true>")
@@ -2425,7 +1525,7 @@ extern "C" int dasr_rdb_chain(const dasr_conv_params* dev_layers, const dasr_con
     // are spread over more CUs (the reference's shipped 16 crops of 32 x 32: 128 workgroups of 4-row tiles), but never at the price of more tiles per workgroup.
     // Measured (profiles/r06_is_chain.txt): 16 x 32 x 32: 8.8 / 6.6 / 6.0 ms per SR step with 16- / 8- / 4-row tiles -- and 6.4 ms with 2-row tiles (2 waves, 256
     // workgroups; built, bit-identical, dropped): below 4 rows the launch is bound by the latency chain store -> flag -> poll -> halo DMA between neighbouring tiles, which
-    // more workgroups do not shorten.  g_tune_is_th != 0 forces a height (experiments).
+    // more workgroups do not shorten.
     if (p0.N & 7) return DASR_EINVAL;
     const int tiles_x = (p0.Wout + ISC::TW - 1) / ISC::TW;
     auto geometry = [&](int th, int& q_out, int& tpw_out) -> bool {   // workgroups per XCD / tiles per workgroup for tiles of th rows
@@ -2443,7 +1543,6 @@ extern "C" int dasr_rdb_chain(const dasr_conv_params* dev_layers, const dasr_con
     int th = 0, q = 0, tpw = 0, best = 1 << 30;
     for (int cand = 16; cand >= 4; cand >>= 1) {
         int qc = 0, tc = 0;
-        if (g_tune_is_th && cand != g_tune_is_th) continue;
         if (!geometry(cand, qc, tc)) continue;
         const int cost = tc * (cand == 16 ? 43 : cand == 8 ? 30 : 24);
         if (cost < best) best = cost, th = cand, q = qc, tpw = tc;
@@ -2467,8 +1566,8 @@ extern "C" int dasr_rdb_chain(const dasr_conv_params* dev_layers, const dasr_con
     const int nrdb = nlayers / 5;
     hipStream_t st = as_stream(stream);
 #define IS_GO(NTv, NWv)                                                                                                                                              \
-    return bwd ? launch_rdb_is<false, true, NTv, NWv>(dev_layers, nrdb, tiles_y, tiles_x, tpw, dev_flags, tickets, dev_err, st, "rdb_is_kernel<false, true, " #NTv ", " #NWv ">", g_tune_is_stagger, grid) \
-               : launch_rdb_is<false, false, NTv, NWv>(dev_layers, nrdb, tiles_y, tiles_x, tpw, dev_flags, tickets, dev_err, st, "rdb_is_kernel<false, false, " #NTv ", " #NWv ">", g_tune_is_stagger, grid)
+    return bwd ? launch_rdb_is<false, true, NTv, NWv>(dev_layers, nrdb, tiles_y, tiles_x, tpw, dev_flags, tickets, dev_err, st, "rdb_is_kernel<false, true, " #NTv ", " #NWv ">", grid) \
+               : launch_rdb_is<false, false, NTv, NWv>(dev_layers, nrdb, tiles_y, tiles_x, tpw, dev_flags, tickets, dev_err, st, "rdb_is_kernel<false, false, " #NTv ", " #NWv ">", grid)
     if (th == 16) { IS_GO(2, 8); }
     if (th == 8) { IS_GO(1, 8); }
     IS_GO(1, 4);
@@ -2477,7 +1576,7 @@ extern "C" int dasr_rdb_chain(const dasr_conv_params* dev_layers, const dasr_con
 
 extern "C" int dasr_conv(const dasr_conv_params* pp, void* stream) {
     dasr_conv_params p = *pp;
-    p.xcd_remap = g_tune_xcd;  // bit 1 (trace builds): contiguous-store timing experiment
+    p.xcd_remap = 1;  // bit 0: XCD-aware tile order (bit 1, trace builds only: the contiguous-store timing experiment of conv_epilogue)
     if (p.pad_x == 0 && p.out_stride == 0 && p.kh != 2 && p.kh != 1) p.pad_x = -1;  // zero-initialised extension fields = "same as pad"
     hipStream_t s = as_stream(stream);
     if (p.cin <= 0 || (p.cin & 15) || p.cout <= 0 || !p.w || !p.in.p) return DASR_EINVAL;
@@ -2506,107 +1605,20 @@ extern "C" int dasr_conv(const dasr_conv_params* pp, void* stream) {
         if (p.in_wrap && (p.cin >> 4) * 2 != p.in_wrap * 3) return DASR_EINVAL;   // cin = 3 * 16K virtual channels, in_wrap = 2K
         if (p.out16_lo && !p.out_bf16.p) return DASR_EINVAL;
         if (p.res1_lo < 0 || (p.res1_lo && !p.res1.p)) return DASR_EINVAL;
-        if (p.prec == 1 && ((p.mt == 1 && g_tune_rdb32 != 12) || (p.mt == 2 && g_tune_rdb64 != 12 && g_tune_rdb64 != 13))) return DASR_EINVAL;   // (A/B variants of the first-generation kernel do not know the layout)
     }
     switch (key) {
         // prec 1, bf16 input (RDB dense-block convs, fwd and dgrad)
         case 10:
-#ifdef DASR_BENCH   // libdasr_hip_ablate.so only (python -m dasr_amd.build --ablate): A/B variants measured slower in rounds 1-3 and the wrong-result
-                    // ablation series; the product library has exactly one dense-block conv kernel (conv_glds_kernel)
-            switch (g_tune_rdb32) {
-                case 1: return launch<1, false, 1, 3, 1, 4, 1, true>(p, s);
-                case 4: return launch<1, false, 1, 3, 1, 2>(p, s);          // 8x32 tiles: 2x the workgroups
-                case 5: return launch<1, false, 1, 3, 1, 2, 1, true>(p, s);
-                case 6: return launch<1, false, 1, 3, 1, 1>(p, s);          // 4x32 tiles
-                case 8: return launch<1, false, 1, 3, 1, 4, 1, false, 1>(p, s);  // row reuse of B fragments across ky
-                case 9: return launch<1, false, 1, 3, 1, 4, 1, true, 1>(p, s);
-                case 10: return launch<1, false, 1, 3, 1, 4, 1, true, 2>(p, s);  // pipelined: prefetch distance 2, ds_write inside the MFMA stream
-                case 11: return launch<1, false, 1, 3, 1, 2, 1, true, 2>(p, s);
-                case 0:   // first-generation register-staged kernel
-                    switch (g_tune_epi ? classify_epi(p) : 0) {
-                        case 67: return launch<1, false, 1, 3, 1, 4, 1, false, 0, 67>(p, s);
-                        case 68: return launch<1, false, 1, 3, 1, 4, 1, false, 0, 68>(p, s);
-                        default: return launch<1, false, 1, 3, 1, 4>(p, s);
-                    }
-                case 100: return launch_glds<1, 67, 4, 0>(p, s);   // ablation series (scripts/micro_conv.py --mode fwd): wrong results, timing only
-                case 101: return launch_glds<1, 67, 4, 1>(p, s);
-                case 102: return launch_glds<1, 67, 4, 2>(p, s);
-                case 103: return launch_glds<1, 67, 4, 3>(p, s);
-                case 104: return launch_glds<1, 67, 4, 4>(p, s);
-                case 107: return launch_glds<1, 67, 4, 7>(p, s);
-                case 108: return launch_glds<1, 67, 4, 8>(p, s);
-                case 112: return launch_glds<1, 67, 4, 12>(p, s);
-                case 115: return launch_glds<1, 67, 4, 15>(p, s);
-                case 116: return launch_glds<1, 67, 4, 16>(p, s);   // barrier per chunk, no DMA wait
-                case 117: return launch_glds<1, 67, 4, 17>(p, s);   // no DMA in the loop, no wait, barrier kept
-                case 164:   // activations read from a cache-resident 256 KB window (round 4: is the fabric read traffic what bounds these launches?)
-                    switch (classify_epi(p)) {
-                        case 68: return launch_glds<1, 68, 4, 64>(p, s);
-                        default: return launch_glds<1, 67, 4, 64>(p, s);
-                    }
-                case 15:   // RING: three activation images + two weight images, counted vmcnt (round 3)
-                    switch (g_tune_epi ? classify_epi(p) : 0) {
-                        case 67: return launch_glds<1, 67, 4, 0, false, 1>(p, s);
-                        case 68: return launch_glds<1, 68, 4, 0, false, 1>(p, s);
-                        default: return launch_glds<1, 0, 4, 0, false, 1>(p, s);
-                    }
-                case 17:   // RING + loader wave, flag words instead of the chunk barrier
-                    switch (g_tune_epi ? classify_epi(p) : 0) {
-                        case 67: return launch_glds<1, 67, 4, 0, false, 3>(p, s);
-                        case 68: return launch_glds<1, 68, 4, 0, false, 3>(p, s);
-                        default: return launch_glds<1, 0, 4, 0, false, 3>(p, s);
-                    }
-                case 16:   // RING + one loader wave per workgroup
-                    switch (g_tune_epi ? classify_epi(p) : 0) {
-                        case 67: return launch_glds<1, 67, 4, 0, false, 2>(p, s);
-                        case 68: return launch_glds<1, 68, 4, 0, false, 2>(p, s);
-                        default: return launch_glds<1, 0, 4, 0, false, 2>(p, s);
-                    }
-                case 14:  // 8 waves, 32x32 tile, three-buffer ring with counted vmcnt (no drain inside the main loop)
-                    switch (g_tune_epi ? classify_epi(p) : 0) {
-                        case 67: return launch_ring3<67>(p, s);
-                        case 68: return launch_ring3<68>(p, s);
-                        default: return launch_ring3<0>(p, s);
-                    }
-                case 13:  // 8 waves, 32x32-pixel tile: -20 % DMA bytes per MFMA (weights and halo amortised over twice the pixels)
-                    switch (g_tune_epi ? classify_epi(p) : 0) {
-                        case 67: return launch_glds<1, 67, 8>(p, s);
-                        case 68: return launch_glds<1, 68, 8>(p, s);
-                        default: return launch_glds<1, 0, 8>(p, s);
-                    }
-                default: break;
-            }
-#endif
-            switch (g_tune_epi ? classify_epi(p) : 0) {
+            switch (classify_epi(p)) {
                 case 67: return launch_glds<1, 67>(p, s);   // bias + LeakyReLU -> bf16 slab planes (forward conv1-4)
                 case 68: return launch_glds<1, 68>(p, s);   // LeakyReLU' mask -> bf16 gslab planes (data gradient)
                 default: return launch_glds<1, 0>(p, s);
             }
         case 20:
-#ifdef DASR_BENCH
-            switch (g_tune_rdb64) {
-                case 1: return launch<1, false, 2, 3, 1, 4, 1, true>(p, s);
-                case 4: return launch<1, false, 2, 3, 1, 2>(p, s);
-                case 5: return launch<1, false, 2, 3, 1, 2, 1, true>(p, s);
-                case 8: return launch<1, false, 2, 3, 1, 4, 1, false, 1>(p, s);
-                case 9: return launch<1, false, 2, 3, 1, 4, 1, true, 1>(p, s);
-                case 10: return launch<1, false, 2, 3, 1, 4, 1, true, 2>(p, s);
-                case 11: return launch<1, false, 2, 3, 1, 2, 1, true, 2>(p, s);
-                case 0:
-                    switch (g_tune_epi ? classify_epi(p) : 0) {
-                        case 233: return launch<1, false, 2, 3, 1, 4, 1, false, 0, 233>(p, s);
-                        case 249: return launch<1, false, 2, 3, 1, 4, 1, false, 0, 249>(p, s);
-                        case 232: return launch<1, false, 2, 3, 1, 4, 1, false, 0, 232>(p, s);
-                        case 248: return launch<1, false, 2, 3, 1, 4, 1, false, 0, 248>(p, s);
-                        default: return launch<1, false, 2, 3, 1, 4>(p, s);
-                    }
-                default: break;
-            }
-#endif
             // one kernel, two workgroup shapes: 13 (default) = the 8-wave form when the 4-wave grid would not exceed one workgroup per CU
             // (sub-batch launches), else 4 waves; 12 = always 4 waves
             if (g_tune_rdb64 == 12 || (long long)p.N * ((p.Hout + 15) / 16) * ((p.Wout + 31) / 32) * ((p.cout + 63) / 64) > 256) {
-                switch (g_tune_epi ? classify_epi(p) : 0) {
+                switch (classify_epi(p)) {
                     case 233: return launch_glds<2, 233>(p, s);   // conv5: bias, alpha, one residual -> fp32 stream + bf16 shadow
                     case 249: return launch_glds<2, 249>(p, s);   // conv5 of RDB3: two residuals (RRDB skip fused)
                     case 232: return launch_glds<2, 232>(p, s);   // data gradient w.r.t. the RDB input
@@ -2614,7 +1626,7 @@ extern "C" int dasr_conv(const dasr_conv_params* pp, void* stream) {
                     default: return launch_glds<2, 0>(p, s);
                 }
             }
-            switch (g_tune_epi ? classify_epi(p) : 0) {
+            switch (classify_epi(p)) {
                 case 233: return launch_glds<2, 233, 8>(p, s);
                 case 249: return launch_glds<2, 249, 8>(p, s);
                 case 232: return launch_glds<2, 232, 8>(p, s);
@@ -2625,12 +1637,7 @@ extern "C" int dasr_conv(const dasr_conv_params* pp, void* stream) {
         case 110: return launch<1, true, 1, 3, 1, 4>(p, s);
         case 120: return launch<1, true, 2, 3, 1, 4>(p, s);
         // prec 3, f32 input (residual-stream convs of the generator, discriminator)
-        case 1110:
-#ifdef DASR_BENCH
-            if (g_tune_stream == 1) return launch<3, true, 1, 3, 1, 4, 1, true>(p, s);
-            if (g_tune_stream == 4) return launch<3, true, 1, 3, 1, 2>(p, s);
-#endif
-            return launch<3, true, 1, 3, 1, 4>(p, s);
+        case 1110: return launch<3, true, 1, 3, 1, 4>(p, s);
         case 1111: return launch<3, true, 1, 4, 1, 2>(p, s);
         case 1112: return launch<3, true, 1, 4, 2, 1>(p, s);
         case 1113: return launch<3, true, 1, 2, 1, 4>(p, s);  // 2x2 parity sub-convs of the stride-2 data-gradient
@@ -2639,7 +1646,7 @@ extern "C" int dasr_conv(const dasr_conv_params* pp, void* stream) {
         case 1116: return launch<3, true, 1, 3, 2, 1>(p, s);  // De_resnet down-sampling convs
         // prec 2 on f16 TENSORS (HR tail in f16 storage): the LDS-DMA dense-conv kernel with the f16 MFMA
         case 2010:
-            switch (g_tune_epi ? classify_epi(p) : 0) {
+            switch (classify_epi(p)) {
                 case 67: return launch_glds<1, 67, 4, 0, true>(p, s);
                 case 68: return launch_glds<1, 68, 4, 0, true>(p, s);
                 case 64: return launch_glds<1, 64, 4, 0, true>(p, s);
@@ -2650,7 +1657,7 @@ extern "C" int dasr_conv(const dasr_conv_params* pp, void* stream) {
             // same workgroup-shape rule as the bf16 launches
             if (p.res1.p) {
                 const bool four = g_tune_rdb64 == 12 || (long long)p.N * ((p.Hout + 15) / 16) * ((p.Wout + 31) / 32) * ((p.cout + 63) / 64) > 256;
-                switch (g_tune_epi ? classify_epi(p) : 0) {
+                switch (classify_epi(p)) {
                     case 233: return four ? launch_glds<2, 233, 4, 0, true>(p, s) : launch_glds<2, 233, 8, 0, true>(p, s);
                     case 249: return four ? launch_glds<2, 249, 4, 0, true>(p, s) : launch_glds<2, 249, 8, 0, true>(p, s);
                     case 232: return four ? launch_glds<2, 232, 4, 0, true>(p, s) : launch_glds<2, 232, 8, 0, true>(p, s);
@@ -2658,7 +1665,7 @@ extern "C" int dasr_conv(const dasr_conv_params* pp, void* stream) {
                     default: return launch_glds<2, 0, 4, 0, true>(p, s);
                 }
             }
-            switch (g_tune_epi ? classify_epi(p) : 0) {
+            switch (classify_epi(p)) {
                 case 67: return launch_glds<2, 67, 4, 0, true>(p, s);
                 case 68: return launch_glds<2, 68, 4, 0, true>(p, s);
                 case 64: return launch_glds<2, 64, 4, 0, true>(p, s);

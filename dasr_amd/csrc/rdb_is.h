@@ -25,19 +25,7 @@
 // PIPELINE, not a spin: wave 0 requests the nine flag words by LDS-DMA at the start of a step, every wave reads them from LDS after the step's barrier;
 // only when a group is still missing where it is needed does the workgroup spin (and counts it: err stays 0, the time shows in the trace).
 // ---------------------------------------------------------------------------------------------------
-#ifndef IS_ABL
-#define IS_ABL 0   // timing experiments with WRONG results (scripts/r06/is_ablate.sh): 1 no epilogues, 2 no weight DMA, 4 no MFMA, 8 no activation DMA, 16 no residual preload
-#endif
-#ifndef IS_BORDER
-#define IS_BORDER 0   // 1: epilogues store the border pixels of their 16-bit planes first and the flag waits for those only (conv_epilogue BMODE).  Built, bit-identical, and
-                      // SLOWER (9.9 / 10.6 ms per chain against 8.7 / 9.0): the second pass doubles the epilogue's store instructions and arithmetic -- profiles/r06_is_chain.txt
-#endif
-#ifndef IS_WDIST
-#define IS_WDIST 3   // 16-row tiles: the weights of step g + IS_WDIST are requested in step g (ring of four granules: at most 3; 2 measured the same)
-#endif
-#ifndef IS_PUB_DELAY
-#define IS_PUB_DELAY 1
-#endif
+// (Storing the border pixels of the 16-bit planes first, with the flag waiting for those only, measured slower: profiles/r06_is_chain.txt.)
 struct ISC {   // what does not depend on the tile height
     static constexpr int TW = 32, IW = 34;
     static constexpr int WGRAN = 18432, NSLOT = 4;
@@ -50,7 +38,7 @@ struct ISC {   // what does not depend on the tile height
     static constexpr int DEC_OFF = F0_OFF + 64;              // decision words [2 step parities][2]: {target reached ? target : target - 1, tile slot}, written by wave 0
     static constexpr int TRC_OFF = DEC_OFF + 64;             // trace builds: 16 64-bit accumulators
     static constexpr int NSTEP = 34;
-    static constexpr int PUB_DELAY = IS_PUB_DELAY;           // a conv's flag goes out at the end of the PUB_DELAY-th step behind its epilogue (its stores have that long to be acknowledged)
+    static constexpr int PUB_DELAY = 1;                      // a conv's flag goes out at the end of the PUB_DELAY-th step behind its epilogue (its stores have that long to be acknowledged)
 };
 // NT = output rows per wave: 2 = tiles of 16 x 32 pixels (the full-chip shapes), 1 = tiles of 8 x 32 (launches that would otherwise fill less of the chip: the reference's
 // shipped 32 x 32 crops run as 64 instead of 32 workgroups; half the MFMA work per step and workgroup)
@@ -68,7 +56,8 @@ struct ISCfg : ISC {
     static constexpr int W_OFF = NSLOT * ACT_SLOT;
     // ring of weight granules and how many steps ahead they are requested.  (8-row tiles have room for six granules, five steps ahead -- the same lead TIME as three steps
     // of the 16-row tiles; measured: 2.53 / 2.59 ms per chain of the 32 x 32-crop launches against 2.43 / 2.52 ms with four / three.  Neither form waits for its weights.)
-    static constexpr int NWG = 4, WDIST = IS_WDIST;
+    static constexpr int NWG = 4;
+    static constexpr int WDIST = 3;   // 16-row tiles: the weights of step g + 3 are requested in step g (ring of four granules: at most 3; 2 measured the same)
     static_assert(W_OFF + NWG * WGRAN <= X_OFF && WDIST < NWG && WDIST >= 2 && WDIST <= 5, "LDS budget / ring depth");
 };
 
@@ -227,13 +216,8 @@ __device__ __forceinline__ void is_body(f32x16 (&a0)[NT], f32x16 (&a1)[NT], cons
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
-            if constexpr (IS_ABL & 4) {
-                asm volatile("" ::"v"(fa[s % R][0]), "v"(fb[kx & 1][nt + ky]));
-                if constexpr (NU == 2) asm volatile("" ::"v"(fa[s % R][1]));
-            } else {
-                a0[nt] = mfma16<F16>(fa[s % R][0], fb[kx & 1][nt + ky], a0[nt]);
-                if constexpr (NU == 2) a1[nt] = mfma16<F16>(fa[s % R][1], fb[kx & 1][nt + ky], a1[nt]);
-            }
+            a0[nt] = mfma16<F16>(fa[s % R][0], fb[kx & 1][nt + ky], a0[nt]);
+            if constexpr (NU == 2) a1[nt] = mfma16<F16>(fa[s % R][1], fb[kx & 1][nt + ky], a1[nt]);
         }
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -242,7 +226,7 @@ __device__ __forceinline__ void is_body(f32x16 (&a0)[NT], f32x16 (&a1)[NT], cons
 
 template <bool F16, bool BWD, int NT, int NW>
 __global__ __launch_bounds__(64 * NW, NW >= 8 ? 2 : 1) void rdb_is_kernel(const dasr_conv_params* __restrict__ layers, const int nrdb, const int tiles_y, const int tiles_x, const int tpw,
-                                                        unsigned* flags, unsigned* tickets, int* err, const int stagger) {
+                                                        unsigned* flags, unsigned* tickets, int* err) {
     using C = ISCfg<NT, NW>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -316,9 +300,8 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 2 : 1) void rdb_is_kernel(const 
     int mk[8] = {0, 0, 0, 0, 0, 0, 0, 0};           // mk[k]: `issued` at the end of step g - 1 - k (g: the current step)
     int g = 0;                                     // global step counter: the granule of step g lives in ring slot g % NWG
     bool pub_on = false;                           // a flag store is pending: value pub_val to word pub_off once every op up to pub_mark is acknowledged, at the end of step pub_due
-    int pub_mark = 0, pub_due = 0, pub_late = 0;
+    int pub_mark = 0, pub_due = 0;
     unsigned pub_off = 0, pub_val = 0;
-    int own_mark = 0;                              // `issued` behind ALL stores of the newest epilogue
     int mark_x = 0;                                // `issued` behind the DMA of the current item's x chunks
     bool poll_pend = false;                        // wave 0: a poll of flag words is in flight (requested behind poll_mark)
     int poll_mark = 0;
@@ -361,9 +344,6 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 2 : 1) void rdb_is_kernel(const 
         IS_ACC(11, 1ull);
     };
 
-    // XCD stagger (tuning key 9): XCD k starts k * stagger * ~4 us late, so that the eight XCDs (which never wait for each other: whole images per XCD) reach
-    // their store / DMA bursts at different times
-    for (int i = 0; i < xcd * stagger; ++i) __builtin_amdgcn_s_sleep(127);
     ISGeo<C> cur = geo_of(0);
     // ---- prologue: x of the first item, the weights of steps 0-2, the biases of the first item
     {
@@ -440,7 +420,7 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 2 : 1) void rdb_is_kernel(const 
             // Requested here, scaled in front of conv1's epilogue (step 3): four steps for the round trip.
             // (A conv5 WITHOUT a 16-bit shadow -- the last block of the trunk -- is one dasr_conv runs with its generic epilogue, alpha * acc + beta1 * x: same here.)
             const dasr_conv_params& p5 = layers[L0 + 4];
-            const bool r1pre = p5.out_bf16.p != nullptr && !(IS_ABL & 16);
+            const bool r1pre = p5.out_bf16.p != nullptr;
             if (r1pre) {
                 const __amdgpu_buffer_rsrc_t rr1 = make_rsrc((const float*)p5.res1.p + (size_t)cur.n * p5.res1.n_stride);
                 const unsigned r1_cb = (unsigned)p5.res1.cb_stride;
@@ -478,9 +458,8 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 2 : 1) void rdb_is_kernel(const 
             const unsigned f0n = (unsigned)__builtin_amdgcn_readfirstlane(xi[sn]);
 
             auto request_group = [&](int c0) {   // chunks c0, c0 + 1 of this item's slab
-                if constexpr (IS_BORDER) is_wait_vm(__builtin_amdgcn_readfirstlane(issued - own_mark));   // (the flag covered the border only: this tile's own interior pixels must be in memory)
-                if constexpr (!(IS_ABL & 8)) issued += is_dma_act<C>(rin, smem + (c0 & 3) * C::ACT_SLOT, cur.goff, (unsigned)c0 * icb, wave, tid);
-                if constexpr (!(IS_ABL & 8)) issued += is_dma_act<C>(rin, smem + ((c0 + 1) & 3) * C::ACT_SLOT, cur.goff, (unsigned)(c0 + 1) * icb, wave, tid);
+                issued += is_dma_act<C>(rin, smem + (c0 & 3) * C::ACT_SLOT, cur.goff, (unsigned)c0 * icb, wave, tid);
+                issued += is_dma_act<C>(rin, smem + ((c0 + 1) & 3) * C::ACT_SLOT, cur.goff, (unsigned)(c0 + 1) * icb, wave, tid);
                 arr_issued = true;
                 mark_act = issued;
             };
@@ -489,8 +468,7 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 2 : 1) void rdb_is_kernel(const 
                 const __amdgpu_buffer_rsrc_t rinn = make_rsrc((const bf16_t*)pn.in.p + (size_t)nxt.n * pn.in.n_stride);
                 const unsigned icbn = (unsigned)(pn.in.cb_stride * 2);
 #pragma unroll
-                for (int c = 0; c < 4; ++c)
-                    if constexpr (!(IS_ABL & 8)) issued += is_dma_act<C>(rinn, smem + c * C::ACT_SLOT, nxt.goff, (unsigned)c * icbn, wave, tid);
+                for (int c = 0; c < 4; ++c) issued += is_dma_act<C>(rinn, smem + c * C::ACT_SLOT, nxt.goff, (unsigned)c * icbn, wave, tid);
                 mark_x = issued;
                 next_x_issued = true;
             };
@@ -530,7 +508,7 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 2 : 1) void rdb_is_kernel(const 
                 }
                 constexpr int EU_AFTER = is_epi_after(TT);
                 auto prefetch_w = [&]() {   // weights of step g + 3 (g: this step)
-                    if (g + C::WDIST < total_steps && !(IS_ABL & 2)) {
+                    if (g + C::WDIST < total_steps) {
                         constexpr int T3 = (TT + C::WDIST) % C::NSTEP;
                         constexpr ISStep e = IS_PROG[T3];
                         constexpr bool NX = TT + C::WDIST >= C::NSTEP;
@@ -581,12 +559,12 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 2 : 1) void rdb_is_kernel(const 
                 // (the fragment registers are dead, the weight requests of such a step are held back until after the epilogue: the loads have the queue to themselves and
                 // fly during the barrier; fetched inside the epilogue they waited in order behind the LDS-DMA in flight -- 29 k against 17 k cycles per item, r06_is_chain.txt)
                 MaskPre<NT> mpre;
-                if constexpr (BWD && EU_AFTER >= 0 && EU_AFTER < 4 && !IS_BORDER && !(IS_ABL & 1)) mask_prefetch<1, NT>(layers[L0 + EU_AFTER], mpre, tid, 0, cur.n, cur.oy0, cur.ox0);
+                if constexpr (BWD && EU_AFTER >= 0 && EU_AFTER < 4) mask_prefetch<1, NT>(layers[L0 + EU_AFTER], mpre, tid, 0, cur.n, cur.oy0, cur.ox0);
                 const unsigned long long t1 = IS_T();
                 // ---- end of the step: everything requested up to the end of step g - 2 has landed (the granule of step g + 1 among it); flag words / publish / group as due
                 int nwait = issued - mk[C::WDIST - 2];   // everything requested up to the end of step g + 1 - WDIST: the granule of step g + 1 among it
                 bool do_pub = false;
-                if (pub_on && g >= pub_due) do_pub = true, nwait = min(nwait, issued - pub_mark + pub_late);
+                if (pub_on && g >= pub_due) do_pub = true, nwait = min(nwait, issued - pub_mark);
                 if constexpr (MUST) {
                     if (arr_issued) nwait = min(nwait, issued - mark_act);
                 }
@@ -646,7 +624,6 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 2 : 1) void rdb_is_kernel(const 
                     const unsigned long long t4 = IS_T();
                     const dasr_conv_params& p = layers[L0 + EU];
                     char* bl = smem + C::BIAS_OFF + par * 1280 + EU * 256;
-                    int pmark = issued, nlate = 0;
                     if constexpr (EU == 4) {
                         if (has_next) {   // x of the next item (+ its biases) goes out in front of the conv5 epilogue when its neighbours are there already (the usual case: another tile's
                                           // block, finished an item ago); else behind it (a workgroup with one tile waits for its own conv5 there)
@@ -655,40 +632,16 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 2 : 1) void rdb_is_kernel(const 
                                 next_rdy = __builtin_amdgcn_readfirstlane(dw[0]) == f0n + (unsigned)L0n && __builtin_amdgcn_readfirstlane(dw[1]) == (unsigned)sn;
                             }
                         }
-                        const bool two = p.res2.p != nullptr && !(IS_ABL & 1), sh = p.out_bf16.p != nullptr;
+                        const bool two = p.res2.p != nullptr, sh = p.out_bf16.p != nullptr;
                         constexpr int E0 = BWD ? 160 : 161;   // alpha, fp32 out (+ bias forward); + 16 second residual, + 64 the 16-bit shadow
-                        // BORDER FIRST (IS_BORDER): the neighbours read only the border pixels of the 16-bit planes, and the flag waits for the acknowledgement of what it covers:
-                        // pass 1 stores those pixels alone (a few KB per tile), the flag's bookkeeping is taken behind it, pass 2 stores the rest (and the fp32 stream)
-                        if constexpr (IS_ABL & 1) {
-                            asm volatile("" ::"v"(A5[0][0]), "v"(A5[0][NT - 1]), "v"(A5[1][0]), "v"(A5[1][NT - 1]));
-                        } else if (two && sh) {
-                            if constexpr (IS_BORDER) conv_epilogue<false, 2, NT, 1, E0 + 80 - 32, F16 ? 1 : 0, false, true, true, true, 1, C::TH>(p, A5, bl, 0.f, tid, 0, cur.n, cur.oy0, cur.ox0);
-                            pmark = issued;
-                            conv_epilogue<false, 2, NT, 1, E0 + 80, F16 ? 1 : 0, false, true, true, true, IS_BORDER ? 2 : 0, C::TH>(p, A5, bl, 0.f, tid, 0, cur.n, cur.oy0, cur.ox0);
-                            nlate = 12 * NT;
-                        } else if (sh) {
-                            if constexpr (IS_BORDER) conv_epilogue<false, 2, NT, 1, E0 + 64 - 32, F16 ? 1 : 0, false, true, true, true, 1, C::TH>(p, A5, bl, 0.f, tid, 0, cur.n, cur.oy0, cur.ox0);
-                            pmark = issued;
-                            conv_epilogue<false, 2, NT, 1, E0 + 64, F16 ? 1 : 0, false, true, true, true, IS_BORDER ? 2 : 0, C::TH>(p, A5, bl, 0.f, tid, 0, cur.n, cur.oy0, cur.ox0);
-                            nlate = 12 * NT;
-                        } else if (two) {   // (no 16-bit output: nothing a neighbour waits for)
-                            conv_epilogue<false, 2, NT, 1, E0 + 8 + 16, F16 ? 1 : 0, false, true, true, true>(p, A5, bl, 0.f, tid, 0, cur.n, cur.oy0, cur.ox0);
-                            pmark = issued, nlate = 0;
-                        } else {
-                            conv_epilogue<false, 2, NT, 1, E0 + 8, F16 ? 1 : 0, false, true, true, true>(p, A5, bl, 0.f, tid, 0, cur.n, cur.oy0, cur.ox0);
-                            pmark = issued, nlate = 0;
-                        }
+                        if (two && sh) conv_epilogue<false, 2, NT, 1, E0 + 80, F16 ? 1 : 0, false, true, true, true>(p, A5, bl, 0.f, tid, 0, cur.n, cur.oy0, cur.ox0);
+                        else if (sh) conv_epilogue<false, 2, NT, 1, E0 + 64, F16 ? 1 : 0, false, true, true, true>(p, A5, bl, 0.f, tid, 0, cur.n, cur.oy0, cur.ox0);
+                        else if (two) conv_epilogue<false, 2, NT, 1, E0 + 8 + 16, F16 ? 1 : 0, false, true, true, true>(p, A5, bl, 0.f, tid, 0, cur.n, cur.oy0, cur.ox0);
+                        else conv_epilogue<false, 2, NT, 1, E0 + 8, F16 ? 1 : 0, false, true, true, true>(p, A5, bl, 0.f, tid, 0, cur.n, cur.oy0, cur.ox0);
                     } else {
                         auto epi14 = [&](f32x16 (&A)[1][NT]) {
-                            if constexpr (IS_ABL & 1) {
-                                asm volatile("" ::"v"(A[0][0]), "v"(A[0][NT - 1]));
-                            } else {
-                                if constexpr (IS_BORDER) conv_epilogue<false, 1, NT, 1, BWD ? 68 : 67, F16 ? 1 : 0, false, true, true, true, 1, C::TH>(p, A, bl, 0.f, tid, 0, cur.n, cur.oy0, cur.ox0);
-                                pmark = issued;
-                                if constexpr (BWD && !IS_BORDER) conv_epilogue<false, 1, NT, 1, 68, F16 ? 1 : 0, true, true, true, true>(p, A, bl, 0.f, tid, 0, cur.n, cur.oy0, cur.ox0, &mpre);
-                                else conv_epilogue<false, 1, NT, 1, BWD ? 68 : 67, F16 ? 1 : 0, false, true, true, true, IS_BORDER ? 2 : 0, C::TH>(p, A, bl, 0.f, tid, 0, cur.n, cur.oy0, cur.ox0);
-                                nlate = 2 * NT;
-                            }
+                            if constexpr (BWD) conv_epilogue<false, 1, NT, 1, 68, F16 ? 1 : 0, true, true, true, true>(p, A, bl, 0.f, tid, 0, cur.n, cur.oy0, cur.ox0, &mpre);
+                            else conv_epilogue<false, 1, NT, 1, 67, F16 ? 1 : 0, false, true, true, true>(p, A, bl, 0.f, tid, 0, cur.n, cur.oy0, cur.ox0);
                         };
                         if constexpr (EU == 0) epi14(A0);
                         else if constexpr (EU == 1) epi14(A1);
@@ -697,10 +650,8 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 2 : 1) void rdb_is_kernel(const 
                     }
                     // the flag of this conv: PUB_DELAY steps from now (an older one that is still pending goes out first)
                     flush_pub();
-                    pub_on = true, pub_mark = pmark, pub_due = g + C::PUB_DELAY;
-                    pub_late = IS_BORDER ? nlate : 0;   // store instructions of pass 2: issued behind the mark, not covered by the flag
+                    pub_on = true, pub_mark = issued, pub_due = g + C::PUB_DELAY;   // (`issued` counts LDS-DMA only: the epilogue's stores are in front of the mark)
                     pub_off = cur.selfo, pub_val = cur.f0 + (unsigned)(L0 + EU + 1);
-                    own_mark = issued;                  // this tile's own planes are complete in memory once everything up to here is acknowledged (request_group waits for it)
                     // ... and only now the LDS-DMA requests this step held back: the weights of step g + 3, the next item's x
                     prefetch_w();
                     if constexpr (EU == 4) {
@@ -751,13 +702,13 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 2 : 1) void rdb_is_kernel(const 
 }
 
 template <bool F16, bool BWD, int NT, int NW>
-int launch_rdb_is(const dasr_conv_params* dev_layers, int nrdb, int tiles_y, int tiles_x, int tpw, unsigned* flags, unsigned* tickets, int* err, hipStream_t s, const char* name, int stagger, int grid) {
+int launch_rdb_is(const dasr_conv_params* dev_layers, int nrdb, int tiles_y, int tiles_x, int tpw, unsigned* flags, unsigned* tickets, int* err, hipStream_t s, const char* name, int grid) {
     static bool attr_set = false;
     auto kfn = rdb_is_kernel<F16, BWD, NT, NW>;
     if (!attr_set) {
         HIP_TRY(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, ISC::LDS_BYTES));
         attr_set = true;
     }
-    DASR_LAUNCH_TAG(name, kfn, dim3((unsigned)grid), dim3(64 * NW), ISC::LDS_BYTES, s, dev_layers, nrdb, tiles_y, tiles_x, tpw, flags, tickets, err, stagger);
+    DASR_LAUNCH_TAG(name, kfn, dim3((unsigned)grid), dim3(64 * NW), ISC::LDS_BYTES, s, dev_layers, nrdb, tiles_y, tiles_x, tpw, flags, tickets, err);
     return (int)hipGetLastError();
 }

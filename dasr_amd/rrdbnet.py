@@ -204,7 +204,7 @@ class RRDBNetHIP:
         form 'layer', k >= 1: round 4's layer-by-layer chained launches (dasr_conv_chain).  A launch needs whole images per XCD and exactly 512 tiles: N images of T
             tiles qualify when N T = 512 k and N / k is a multiple of 8 -- the plan then runs k launches BACK TO BACK over image ranges of N / k (k = 1 at configs[1];
             k = 2 for configs[2]'s 32 crops of 128 x 128: at batch 32 the per-layer launches run a dense block in 274 + 287 us, two chained half-batches in 2 x (131 + 129) us).
-            (Round 5 also built a form whose workgroups own several tiles -- bit-identical, but 88 ms per GAN step against 72 ms; -DDASR_BENCH library only.)
+            (Round 5 also built a form whose workgroups own several tiles -- bit-identical, but 88 ms per GAN step against 72 ms; not kept.)
         form 'is', k = 1: round 6's input-stationary chained launch (dasr_rdb_chain, csrc/rdb_is.h): every slab chunk staged once per dense block, 8 q <= 256 workgroups of
             8 waves (one per CU) owning up to 8 tiles each; whole images per XCD (N % 8 == 0) and every tile of an image in flight at once (is_geometry).
             Measured (profiles/r06_is_chain.txt): level with the layer form where both apply (31.3 vs 30.6 ms at 16 x 128^2), 6-23 % faster than one launch per conv where

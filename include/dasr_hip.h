@@ -144,15 +144,9 @@ typedef struct {
 } dasr_resblock_params;
 int dasr_resblock(const dasr_resblock_params* p, void* stream);
 
-/* kernel-variant knobs for A/B runs (bench.py --sweep / --tune); defaults are the tuned choice.
- * key 1 / 2: dense-block conv with Cout = 32 / 64: 12 = LDS-DMA kernel (default for Cout 32), 13 = its 8-wave 32x32-tile form (Cout 64 default: chosen per launch when the 4-wave grid has <= 256 workgroups), 0 = first-generation register-staged kernel,
- *            1 double-buffered LDS, 4/5 8x32 tiles, 6 4x32 tiles, 8/9 row reuse, 10/11 register-staged pipeline;
- * key 3: split-bf16 stream conv (0 single / 1 double LDS buffer, 4 8x32 tiles); key 4: XCD-aware tile order on/off;
- * key 5: compile-time specialised epilogues on/off;
- *            key 1 also: 15 / 16 / 17 = ring of three LDS images with counted vmcnt / + one loader wave / + LDS flags instead of the chunk barrier
- *            (round 3: built, parity-tested, measured flat -- profiles/r03_conv_ablation.txt);
- * key 7 (-DDASR_BENCH library only): form of the chained launches: 1 = conv_chain_kernel for 512 tiles and conv_chain2_kernel (round 5: workgroups that own
- *        several tiles; measured slower, profiles/r05_chain_trace.txt) for multiples, 2 = conv_chain2_kernel always;
+/* kernel-variant knob (bench.py --sweep / --tune).  key 2: workgroup shape of the Cout = 64 dense-block convs: 13 (default) = the 8-wave 32x32-tile
+ * form when the 4-wave grid has <= 256 workgroups, else 4 waves; 12 = always 4 waves.  Keys 1 / 3 / 4 / 5 / 6 accept only their fixed values 12 / 0 / 1 / 1 / 0
+ * (one dense-block conv kernel, one stream conv, XCD-aware tile order, compile-time specialised epilogues, no chunk-order rotation); anything else: DASR_EINVAL.
  * (round 3: the Cout-32 dense-block convs store their output `sc1`, written through -- measured with a run-time switch, now compile time.) */
 int dasr_set_tuning(int32_t key, int32_t value);
 
@@ -184,10 +178,7 @@ typedef struct {
  * (g_planes = 2/4/6), workspace [split][tap][3][32][64], bias [split][96]. */
 int dasr_wgrad(const dasr_wgrad_part* parts_dev, int32_t nparts, int32_t nsplit, int32_t kh, int32_t stride, int32_t f32,
                float* ws, void* stream);
-/* bit 0: 1 = ds_read_b64_tr_b16 gathers, 0 = scalar LDS gathers (dasr_probe_tr16 sets it from the device);
- * bit 1: dense-block wgrad3 staged by LDS-DMA instead of registers (A/B; default off); bit 7: kh = 33 launches on 16-bit tensors run
- * wgrad4_kernel (4 waves, LDS-DMA ring of three tiles, register window of X fragments; measured slower, kept as a tested alternative)
- * instead of wgrad3_kernel (12 waves, register-staged). */
+/* bit 0: 1 = ds_read_b64_tr_b16 gathers, 0 = scalar LDS gathers (dasr_probe_tr16 sets it from the device); any other bit: DASR_EINVAL. */
 int dasr_wgrad_set_mode(int32_t use_tr);
 
 typedef struct {

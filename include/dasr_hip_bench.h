@@ -2,8 +2,6 @@
  *
  * NOT part of the product library: libdasr_hip.so exports nothing declared here.  bench.py uses the MFMA-only probes to report the
  * dense-MFMA rate the box sustains at the clock its power state allows next to the spec peak; scripts/micro_*.py use the rest.
- * The wrong-result ablation instantiations of the dense conv kernel live in a third library (libdasr_hip_ablate.so =
- * the product sources compiled with -DDASR_BENCH, `python -m dasr_amd.build --ablate`), reachable through dasr_set_tuning(1, 100 + bits).
  */
 #ifndef DASR_HIP_BENCH_H
 #define DASR_HIP_BENCH_H

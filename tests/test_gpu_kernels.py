@@ -165,12 +165,12 @@ def test_prelu_slope_partials_from_the_mask_epilogue():
 
 
 def test_product_library_has_one_dense_conv_family():
-    """round 4: the A/B variants of rounds 1-3 (first-generation tilings, ring / loader / flag forms, dasr_set_tuning keys 1-6) live in
-    libdasr_hip_ablate.so only; the product library accepts the defaults and the workgroup-shape rule of the Cout = 64 launches (key 2)"""
+    """the A/B variants of rounds 1-3 (first-generation tilings, ring / loader / flag forms) and the experiment keys 7 / 9 / 10 are gone (git history);
+    dasr_set_tuning accepts the defaults of keys 1 / 3-6 and the workgroup-shape rule of the Cout = 64 launches (key 2)"""
     _gpu()
     from dasr_amd import _lib
     L = _lib.lib()
-    for key, value in ((1, 0), (1, 13), (1, 14), (1, 15), (2, 0), (2, 8), (3, 1), (4, 0), (5, 0), (6, 1)):
+    for key, value in ((1, 0), (1, 13), (1, 14), (1, 15), (2, 0), (2, 8), (3, 1), (4, 0), (5, 0), (6, 1), (7, 1), (9, 1), (10, 8)):
         assert L.dasr_set_tuning(key, value) == -22, (key, value)
     for key, value in ((1, 12), (2, 12), (2, 13), (3, 0), (4, 1), (5, 1), (6, 0)):
         assert L.dasr_set_tuning(key, value) == 0, (key, value)

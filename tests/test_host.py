@@ -180,7 +180,7 @@ def test_ranks_must_agree_on_numerics_switches(tmp_path):
 
 def test_product_library_carries_one_kernel_family_per_op():
     """the measured-slower alternatives (wgrad3_kernel, wgrad3_glds_kernel, wgrad4_kernel, conv_ring3_kernel, the
-    ring / loader-wave forms of the dense conv) are compiled into libdasr_hip_ablate.so (-DDASR_BENCH) only"""
+    ring / loader-wave forms of the dense conv) are not in the product library (their sources were removed; git history keeps them)"""
     from dasr_amd import _lib
     data = open(_lib.LIB_PATH, "rb").read()
     fams = set(m.decode() for m in re.findall(rb'(conv_ring3_kernel|wgrad4_kernel|wgrad3_glds_kernel|wgrad3_kernel|wgrad3_ld_kernel|conv_glds_kernel|conv_kernel|wgrad_kernel)', data))
@@ -318,8 +318,8 @@ def test_fold_batchnorm_fsd_equals_eval_mode_network(golden_dir):
 
 
 def test_product_library_has_no_probes_and_no_wrong_result_kernels():
-    """micro-benchmark probes live in libdasr_bench.so (include/dasr_hip_bench.h), the ablation instantiations of the dense conv
-    kernel (results wrong on purpose) only exist under -DDASR_BENCH (libdasr_hip_ablate.so); neither is in the product library or its header"""
+    """micro-benchmark probes live in libdasr_bench.so (include/dasr_hip_bench.h), and the ablation instantiations of the dense conv
+    kernel (results wrong on purpose) were removed from the sources; neither is in the product library or its header"""
     from dasr_amd import build, _lib
     blob = open(build.build(), 'rb').read()
     assert blob.count(b'conv_glds_kernelILi1ELi67ELi4ELi0E') > 0          # the production instantiation is there ...
