@@ -2,6 +2,7 @@
 there is no CPU / PyTorch fallback on the product path."""
 import ctypes as C
 import os
+import struct
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libdasr_hip.so')
@@ -61,8 +62,36 @@ class CropDesc(C.Structure):
 
 
 class Op(C.Structure):
+    """dasr_op: one recorded launch.  OP_CONV carries a ConvParams; every other kind passes its arguments in the untyped slots i / f / l / p / t,
+    laid out by OP_ARGS (build with make_op, read and patch with get / set)."""
     _fields_ = [('op', c_i32), ('i', c_i32 * 8), ('f', c_f32 * 4), ('l', c_i64 * 4), ('p', c_vp * 4), ('t', Tensor * 5),
                 ('conv', ConvParams), ('flops', C.c_double), ('bytes', C.c_double)]
+
+    def get(self, name):
+        """the argument `name` of this op (OP_ARGS)"""
+        arr, k, enc = _slot(self.op, name)
+        a = getattr(self, arr)
+        if enc == '*':
+            return list(a) if arr == 'f' else list((c_f32 * 4).from_buffer(a))
+        if enc == 'f':
+            return struct.unpack('<f', struct.pack('<I', a[k] & 0xffffffff))[0]
+        return a[k]
+
+    def set(self, name, value):
+        """write the argument `name` of this op (OP_ARGS); None / NULL_T are the zero bytes an argument left out has"""
+        arr, k, enc = _slot(self.op, name)
+        a = getattr(self, arr)
+        if enc == '*':
+            if arr == 'f':
+                a[:] = [float(v) for v in value]
+            else:
+                (c_f32 * 4).from_buffer(a)[:] = [float(v) for v in value]
+        elif enc == 'f':
+            a[k] = struct.unpack('<I', struct.pack('<f', value))[0]
+        elif value is None:
+            a[k] = Tensor(None, 0, 0) if arr == 't' else 0
+        else:
+            a[k] = value
 
 
 OP_CONV, OP_WGRAD, OP_WGRAD_REDUCE, OP_PACK, OP_DOWNSUM, OP_AXPBY, OP_FILL, OP_L1LOSS, OP_NCHW2B, OP_B2NCHW = range(1, 11)
@@ -79,6 +108,98 @@ OP_RDB_CHAIN = 49
 OP_BNORM_JVP, OP_BNORM_SECOND = 50, 51   # --wgan with BatchNorm discriminators (round 6)
 OP_PRELU_FINAL = 52
 OP_RESBLOCK = 53   # fused residual block of SRResNet (ABI 21)
+
+# Argument slots of every op kind the plan builders record (all but OP_CONV), by the parameter name of the entry point that dasr_run_ops
+# (csrc/misc.hip) passes the slot to.  Slot codes: i0..i6 int32, f0..f3 float, l0..l3 int64, p0..p3 pointer, t0..t4 dasr_tensor;
+# 'f*': four floats in f[0..3]; 'l*': four floats in the first 16 bytes of l; 'l1f' / 'l2f': a float's bits in the low half of l[1] / l[2].
+# i[7] of every kind is 'tag', the time bucket of OpList.tag (no kernel reads it).  tests/test_host.py checks the table against the switch.
+OP_ARGS = {
+    OP_WGRAD: dict(parts_dev='p0', nparts='i0', nsplit='i1', kh='i2', stride='i3', f32='i4', ws='p1'),
+    # scale x inv_prescale (when non-zero) is the reduce scale: inv_prescale undoes the f16 operand pre-scale
+    OP_WGRAD_REDUCE: dict(parts_dev='p0', nparts='i0', ws='p1', grad_flat='p2', scale='f0', inv_prescale='f1', few_splits='i1'),
+    OP_PACK: dict(descs_dev='p0', ndesc='i0', total_pieces='l0', piece_prefix_dev='p1', params_flat='p2', packed='p3'),
+    OP_DOWNSUM: dict(src='t0', N='i0', C='i1', H='i2', W='i3', mask='t1', mask_f32='i4', slope='f0', dst_f32='t2', dst_bf16='t3'),
+    OP_AXPBY: dict(x='t0', a='f0', z='t1', b='f1', N='i0', C='i1', H='i2', W='i3', out_f32='t2', out_bf16='t3', gamma='f2', mask='t4', slope='f3',
+                   slope_ptr='p0'),
+    OP_FILL: dict(p='p0', n='l0', value='f0'),
+    OP_L1LOSS: dict(sr='t0', hr_nchw='p0', weight_map='p1', N='i0', C='i1', H='i2', W='i3', coef='f0', loss_acc='p2', grad='t1', accumulate='i4',
+                    grad_scale='f1'),
+    OP_NCHW2B: dict(src='p0', N='i0', C='i1', H='i2', W='i3', dst_f32='t0', dst_bf16='t1'),
+    OP_B2NCHW: dict(src='t0', N='i0', C='i1', H='i2', W='i3', dst='p0'),
+    OP_INORM_FWD: dict(x='t0', N='i0', C='i1', H='i2', W='i3', eps='f0', slope='f1', y='t1', stats='p0'),
+    OP_INORM_BWD: dict(a='t0', ga='t1', N='i0', C='i1', H='i2', W='i3', slope='f0', stats='p0', gx='t2'),
+    OP_BCE: dict(x='t0', N='i0', C='i1', H='i2', W='i3', gan_type='i4', target='f0', coef='f1', gcoef='f2', loss_acc='p0', score_acc='p1',
+                 score_coef='f3', grad='t1'),
+    OP_DWT_FWD: dict(x='t0', N='i0', C='i1', H2='i2', W2='i3', norm='i4', ll='t1', hc='t2'),
+    OP_DWT_BWD: dict(gll='t0', ghc='t1', N='i0', C='i1', H2='i2', W2='i3', norm='i4', gx='t2', accumulate='i5'),
+    OP_LOWPASS: dict(x='t0', x2='t1', w='p0', k='i4', N='i0', C='i1', H='i2', W='i3', mode='i5', a_h='f0', b_h='f1', out_low='t2', out_high='t3',
+                     accumulate='i6'),
+    OP_MAXPOOL: dict(x='t0', is_f32='i4', N='i0', C='i1', Ho='i2', Wo='i3', y='t1', Win='i6'),
+    OP_MAXPOOL_BWD: dict(x='t0', gy='t1', is_f32='i4', N='i0', C='i1', Ho='i2', Wo='i3', gx='t2', relu_mask='i5', Win='i6'),
+    OP_L1DIFF: dict(a='t0', b='t1', is_f32='i4', N='i0', C='i1', H='i2', W='i3', coef='f0', gcoef='f1', loss_acc='p0', ga='t2'),
+    OP_AFFINE4: dict(x='t0', N='i0', C='i1', H='i2', W='i3', scale4='f*', shift4='l*', y='t1', y_f32='i4', accumulate='i5'),
+    OP_BILINEAR: dict(src='p0', N='i0', h='i1', w='i2', factor='i3', dst='p1'),
+    OP_LOGLOSS: dict(x='t0', N='i0', H='i1', W='i2', mode='i3', eps='f0', coef='f1', gcoef='f2', loss_acc='p0', score_acc='p1', score_coef='f3',
+                     grad='t1', accumulate='i4'),
+    OP_SIGMOID_BWD: dict(y='t0', g='t1', N='i0', C='i1', H='i2', W='i3', gz='t2'),
+    # f16 != 0: dasr_prelu_grad_f16 (y and gx f16, gx pre-scaled by 1 / inv_prescale; scale x inv_prescale when that is non-zero)
+    OP_PRELU_GRAD: dict(y='t0', gx='t1', N='i0', C='i1', H='i2', W='i3', slope='p0', scratch256='p1', dst='p2', scale='f0', f16='i4', inv_prescale='f1'),
+    OP_LOWPASS_VALID: dict(x='t0', w='p0', k='i4', N='i0', C='i1', H='i2', W='i3', mode='i5', out='t1', accumulate='i6'),
+    OP_ADD_FLAT: dict(y='p0', x='p1', n='l0'),
+    OP_SIGMOID_FWD: dict(x='t0', N='i0', C='i1', H='i2', W='i3', y='t1'),
+    OP_EVENT_RECORD: dict(event='p0'),
+    OP_STREAM_WAIT: dict(event='p0'),
+    OP_SET_STREAM: dict(stream='p0'),   # null: back to the stream dasr_run_ops was called with
+    OP_PIXSHUF: dict(src='t0', N='i0', C4='i1', H='i2', W='i3', dst='t1'),
+    OP_PIXUNSHUF: dict(gsrc='t0', mask='t1', slope='f0', N='i0', C4='i1', H='i2', W='i3', gdst='t2'),
+    # form selects the entry point: 0 dasr_cvt_f16, 1 / 2 dasr_cvt_split16 (f16 / bf16), 3 dasr_f16_residual
+    OP_CVT_F16: dict(x='t0', N='i0', C='i1', H='i2', W='i3', scale='f0', y='t1', form='i4'),
+    OP_DOWNSUM_F16: dict(src='t0', N='i0', C='i1', H='i2', W='i3', mask='t1', slope='f0', out_scale='f1', dst_f32='t2', dst_f16='t3'),
+    OP_BNORM_FWD: dict(x='t0', N='i0', C='i1', H='i2', W='i3', group='i4', eps='f0', slope='f1', gamma='p0', beta='p1', y='t1', stats='p2'),
+    OP_BNORM_BWD: dict(x='t0', ga='t1', N='i0', C='i1', H='i2', W='i3', group='i4', slope='f0', gamma='p0', beta='p1', stats='p2', gx='t2', dgamma='p3',
+                       dbeta='l0', pscale='f1'),   # dbeta: a device address
+    OP_BNORM_RUNNING: dict(stats='p0', g='i0', C='i1', count='i2', momentum='f0', running_mean='p1', running_var='p2', num_batches_tracked='p3'),
+    OP_INORM_JVP: dict(a='t0', t='t1', N='i0', C='i1', H='i2', W='i3', slope='f0', stats='p0', out='t2'),
+    OP_INORM_SECOND: dict(a='t0', t='t1', ga='t2', N='i0', C='i1', H='i2', W='i3', slope='f0', stats='p0', out='t3', accumulate='i4'),
+    OP_RESBLOCK: dict(p='p0'),
+    OP_PRELU_FINAL: dict(partial='p0', nblocks='i0', stride='l0', count='i1', slopes='p1', dsts='p2', scale='f0'),
+    OP_BNORM_JVP: dict(x='t0', t='t1', N='i0', C='i1', H='i2', W='i3', group='i4', slope='f0', gamma='p0', beta='p1', stats='p2', out='t2'),
+    OP_BNORM_SECOND: dict(x='t0', t='t1', ga='t2', N='i0', C='i1', H='i2', W='i3', group='i4', slope='f0', gamma='p0', beta='p1', stats='p2', out='t3',
+                          accumulate='i5', dgamma='p3', pscale='f1'),
+    OP_GRAD_PENALTY: dict(g='t0', N='i0', C='i1', H='i2', W='i3', weight='f0', part256='p0', out3='p1', loss_acc='p2', stage='i4',
+                          world='i5'),   # world 0 is read as 1
+    OP_FILL_SCALED: dict(x='t0', N='i0', C='i1', H='i2', W='i3', scalar='p0', factor='f0'),
+    OP_CONV_CHAIN: dict(dev_layers='p0', host_layers='p1', dev_dep_chunk='p2', nlayers='i0', dev_flags='p3', dev_err='l0'),   # dev_err: a device address
+    OP_RDB_CHAIN: dict(dev_layers='p0', host_layers='p1', nlayers='i0', dev_flags='p3', dev_err='l0'),
+    OP_DDM_SPREAD: dict(d='t0', N='i0', n_h='i1', n_w='i2', H='i3', W='i4', jump='i5', rf='i6', start='f0', out='t1'),
+    OP_RAGAN: dict(a='t0', b='t1', N='i0', H='i1', W='i2', stage='i3', n_glob='i4', form='i5', ta='f0', tb='f1', coef='f2', gcoef='f3', eps='l2f',
+                   sums='p0', part='p1', loss_acc='p2', score_a='p3', score_b='l0', score_coef='l1f', ga='t2', gb='t3'),   # score_b: a device address
+    OP_LPIPS_S2D: dict(x='t0', N='i0', H='i1', W='i2', scale4='f*', shift4='l*', y='t1', mode='i3'),
+    OP_MAXPOOL3: dict(x='t0', N='i0', C='i1', H='i2', W='i3', y='t1'),
+    OP_MAXPOOL3_BWD: dict(x='t0', gy='t1', N='i0', C='i1', H='i2', W='i3', gx='t2', relu_mask='i4', accumulate='i5'),
+    OP_LPIPS_HEAD: dict(f='t0', pair_off='l0', N='i0', C='i1', H='i2', W='i3', lin='p0', eps='f0', coef='f1', gcoef='f2', loss_acc='p1', g0='t1',
+                        relu_mask='i4'),
+}
+
+
+def _slot(kind, name):
+    """(slot array, index, encoding) of argument `name` of op kind `kind`: 'i3' -> ('i', 3, ''), 'f*' -> ('f', 0, '*'), 'l2f' -> ('l', 2, 'f')"""
+    code = 'i7' if name == 'tag' else OP_ARGS.get(kind, {}).get(name)
+    if code is None:
+        raise TypeError('op kind %d has no argument %r' % (kind, name))
+    if code[1] == '*':
+        return code[0], 0, '*'
+    return code[0], int(code[1]), code[2:]
+
+
+def make_op(kind, flops=0.0, bytes=0.0, **args):
+    """an Op of `kind` with the named arguments of OP_ARGS (and 'tag'); arguments left out are zero"""
+    o = Op()
+    o.op = kind
+    o.flops, o.bytes = flops, bytes
+    for name, v in args.items():
+        o.set(name, v)
+    return o
 
 _SIGS = {
     'dasr_conv': [C.POINTER(ConvParams), c_vp],

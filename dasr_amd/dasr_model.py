@@ -10,7 +10,6 @@ stepped before the optimizer, FilterHigh normalised twice under `norm`.  D(Hf_t(
 the G and the D loss (same weights, same input in the reference too); the reference's discarded D weight-gradients of
 the G step are not computed.
 """
-import ctypes as C
 import logging
 import math
 import os
@@ -19,7 +18,8 @@ from collections import OrderedDict
 import torch
 
 from . import _lib
-from .engine import BTensor, Op, OpList, NULL_T, Tensor, _stream
+from ._lib import make_op
+from .engine import BTensor, OpList, NULL_T, Tensor, _stream
 from .gan_nets import (NLayerDiscriminatorHIP, DiscriminatorVGG128HIP, VGGFeatureHIP, VGG_MEAN, VGG_STD, nlayer_d_spec, vgg128_spec,
                        vgg128_init_state_dict)
 from .init import kaiming_state_dict
@@ -31,12 +31,6 @@ logger = logging.getLogger('base')
 A_PIX, A_LL, A_FEA, A_GAN, A_DREAL, A_DFAKE, A_SREAL, A_SFAKE = range(8)
 A_GAN_SRC, A_DREAL_SRC, A_DFAKE_SRC, A_SREAL_SRC, A_SFAKE_SRC = range(8, 13)   # source-domain discriminator (gan_H_source > 0)
 N_ACC = 16
-
-
-def _op(kind):
-    o = Op()
-    o.op = kind
-    return o
 
 
 def _nview(bt, n0):
@@ -384,17 +378,9 @@ class DASR_Model(BaseModel):
 
 def _ragan_ops(lists, a, b, n, H, W, n_glob, ta, tb, coef, gcoef, sums, part, p_loss, p_sa, p_sb, score_coef, ga, gb, form=0, eps=0.0, stages=(0, 1, 2)):
     """the three dasr_ragan stages of one relativistic loss, appended to lists[0..2] (include/dasr_hip.h); form 1 / eps: the DSN's form"""
-    import struct
     for stage in stages:
-        o = _op(_lib.OP_RAGAN)
-        o.t[0], o.t[1], o.i[0], o.i[1], o.i[2], o.i[3], o.i[4], o.i[5] = a, b, n, H, W, stage, n_glob, form
-        o.l[2] = struct.unpack('<I', struct.pack('<f', eps))[0]
-        o.f[0], o.f[1], o.f[2], o.f[3] = ta, tb, coef, gcoef
-        o.p[0], o.p[1], o.p[2], o.p[3] = sums.data_ptr(), part.data_ptr(), p_loss, p_sa
-        o.l[0] = p_sb or 0
-        o.l[1] = struct.unpack('<I', struct.pack('<f', score_coef))[0]
-        o.t[2], o.t[3] = ga, gb
-        lists[stage].add(o)
+        lists[stage].add(make_op(_lib.OP_RAGAN, a=a, b=b, N=n, H=H, W=W, stage=stage, n_glob=n_glob, form=form, eps=eps, ta=ta, tb=tb, coef=coef, gcoef=gcoef,
+                                 sums=sums.data_ptr(), part=part.data_ptr(), loss_acc=p_loss, score_a=p_sa, score_b=p_sb, score_coef=score_coef, ga=ga, gb=gb))
     lists[0].keep += [sums, part]
 
 
@@ -416,36 +402,23 @@ class _StepPlan:
         Hd, Wd = (H // 2, W // 2) if wavelet else (H, W)
         fwd, gl = OpList(), OpList()
 
-        def add(ol, o):
-            ol.add(o)
-            return o
-
         # ---- forward -------------------------------------------------------------------------------------------
         fwd.extend(g.fwd)
-        o = add(fwd, _op(_lib.OP_FILL))
-        o.p[0], o.l[0], o.f[0] = acc, N_ACC, 0.0
-        o = add(fwd, _op(_lib.OP_NCHW2B))
-        o.p[0], o.i[0], o.i[1], o.i[2], o.i[3], o.t[0], o.t[1] = self.hr_nchw.data_ptr(), N2, 3, H, W, self.hr_b.view(), NULL_T
-        o = add(fwd, _op(_lib.OP_BILINEAR))  # ddm -> HR size (DASR_model.py:173-174)
-        o.p[0], o.i[0], o.i[1], o.i[2], o.i[3], o.p[1] = self.fake_w.data_ptr(), n, h, w, 4, self.wmap.data_ptr()
-        o = add(fwd, _op(_lib.OP_FILL))      # dL/dSR accumulates contributions of every loss term
-        o.p[0], o.l[0], o.f[0] = g.g_sr.t.data_ptr(), g.g_sr.t.numel(), 0.0
+        fwd.add(make_op(_lib.OP_FILL, p=acc, n=N_ACC, value=0.0))
+        fwd.add(make_op(_lib.OP_NCHW2B, src=self.hr_nchw.data_ptr(), N=N2, C=3, H=H, W=W, dst_f32=self.hr_b.view()))
+        # ddm -> HR size (DASR_model.py:173-174)
+        fwd.add(make_op(_lib.OP_BILINEAR, src=self.fake_w.data_ptr(), N=n, h=h, w=w, factor=4, dst=self.wmap.data_ptr()))
+        # dL/dSR accumulates contributions of every loss term
+        fwd.add(make_op(_lib.OP_FILL, p=g.g_sr.t.data_ptr(), n=g.g_sr.t.numel(), value=0.0))
         # pixel loss on the source half
         if m.l_pix_w > 0:
-            o = add(fwd, _op(_lib.OP_L1LOSS))
             cnt = float(n * 3 * H * W)
-            o.t[0], o.p[0] = g.sr.view(), self.hr_nchw.data_ptr()
-            o.p[1] = self.wmap.data_ptr() if m.multiweights else None
-            o.i[0], o.i[1], o.i[2], o.i[3], o.i[4] = n, 3, H, W, 1 | (2 if (m.pix_l2 and not m.multiweights) else 0)
             # multiweights: l_g_pix = w * mean(W|d|) and total += w * l_g_pix  (DASR_model.py:213-218)
-            self.pix_log_div = 1.0
-            if m.multiweights:
-                o.f[0] = float(m.l_pix_w) * float(m.l_pix_w) / cnt
-                self.pix_log_div = float(m.l_pix_w)
-            else:
-                o.f[0] = float(m.l_pix_w) / cnt
-                self.pix_log_div = float(m.l_pix_w)
-            o.p[2], o.t[1] = acc + 4 * A_PIX, g.g_sr.view()
+            coef = float(m.l_pix_w) * float(m.l_pix_w) / cnt if m.multiweights else float(m.l_pix_w) / cnt
+            self.pix_log_div = float(m.l_pix_w)
+            fwd.add(make_op(_lib.OP_L1LOSS, sr=g.sr.view(), hr_nchw=self.hr_nchw.data_ptr(), weight_map=self.wmap.data_ptr() if m.multiweights else None,
+                            N=n, C=3, H=H, W=W, accumulate=1 | (2 if (m.pix_l2 and not m.multiweights) else 0), coef=coef, loss_acc=acc + 4 * A_PIX,
+                            grad=g.g_sr.view()))
         # frequency separation
         D = m.netD_target
         self.d = D.plan(N2, Hd, Wd) if D is not None else None
@@ -478,8 +451,7 @@ class _StepPlan:
                                     (self.hr_b, 0, self.real_low.view(), sx_real), (self.hr_b, n, NULL_T, dx_real)):
                 if ll.p is None and hc.p is None:
                     continue
-                o = add(fwd, _op(_lib.OP_DWT_FWD))
-                o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.i[4], o.t[1], o.t[2] = _nview(src, n0), n, 3, Hd, Wd, int(m.norm), ll, hc
+                fwd.add(make_op(_lib.OP_DWT_FWD, x=_nview(src, n0), N=n, C=3, H2=Hd, W2=Wd, norm=int(m.norm), ll=ll, hc=hc))
         else:
             a_h, b_h = (0.25, 0.75) if m.norm else (0.5, 0.5)  # FilterHigh normalises, filter_func normalises again (App. C-11)
             self.ab = (a_h, b_h)
@@ -487,17 +459,13 @@ class _StepPlan:
                                     (self.hr_b, 0, self.real_low.view(), sx_real), (self.hr_b, n, NULL_T, dx_real)):
                 if lo.p is None and hi.p is None:
                     continue
-                o = add(fwd, _op(_lib.OP_LOWPASS))
-                o.t[0], o.t[1], o.p[0], o.i[4] = _nview(src, n0), NULL_T, m.fs_w.data_ptr(), m.fs_k
-                o.i[0], o.i[1], o.i[2], o.i[3], o.i[5], o.i[6] = n, 3, H, W, 0, 0
-                o.f[0], o.f[1], o.t[2], o.t[3] = a_h, b_h, lo, hi
+                fwd.add(make_op(_lib.OP_LOWPASS, x=_nview(src, n0), w=m.fs_w.data_ptr(), k=m.fs_k, N=n, C=3, H=H, W=W, a_h=a_h, b_h=b_h, out_low=lo,
+                                out_high=hi))
         # LL loss (source half)
         if m.sup_LL:
-            o = add(fwd, _op(_lib.OP_L1DIFF))
             cnt = float(n * 3 * Hd * Wd)
-            o.t[0], o.t[1], o.i[4] = self.fake_low.view(), self.real_low.view(), 1 | (2 if m.pix_l2 else 0)
-            o.i[0], o.i[1], o.i[2], o.i[3] = n, 3, Hd, Wd
-            o.f[0], o.f[1], o.p[0], o.t[2] = 1.0 / cnt, float(m.l_pix_LL_w) / cnt, acc + 4 * A_LL, self.g_low.view()
+            fwd.add(make_op(_lib.OP_L1DIFF, a=self.fake_low.view(), b=self.real_low.view(), is_f32=1 | (2 if m.pix_l2 else 0), N=n, C=3, H=Hd, W=Wd,
+                            coef=1.0 / cnt, gcoef=float(m.l_pix_LL_w) / cnt, loss_acc=acc + 4 * A_LL, ga=self.g_low.view()))
         # VGG feature loss (source half): batch [fake_s; real_s]
         self.v = None
         lpips = m.netF is not None and m.l_fea_type == 'LPIPS'
@@ -514,36 +482,27 @@ class _StepPlan:
             sc = [1.0 / s for s in VGG_STD] + [0.0]
             sh = [-mu / s for mu, s in zip(VGG_MEAN, VGG_STD)] + [0.0]
             for src, dst in ((g.sr.view(), v.x.view()), (self.hr_b.view(), _nview(v.x, n))):
-                o = add(fwd, _op(_lib.OP_AFFINE4))
-                o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.t[1], o.i[4], o.i[5] = src, n, 3, H, W, dst, v.x_flag, 0
-                for j in range(4):
-                    o.f[j] = sc[j]
-                C.memmove(C.addressof(o.l), (C.c_float * 4)(*sh), 16)
+                fwd.add(make_op(_lib.OP_AFFINE4, x=src, N=n, C=3, H=H, W=W, y=dst, y_f32=v.x_flag, scale4=sc, shift4=sh))
             fwd.extend(v.fwd)
-            o = add(fwd, _op(_lib.OP_L1DIFF))
             f = v.feat
             cnt = float(n * f.C * f.H * f.W)
-            o.t[0], o.t[1], o.i[4] = f.view(), _nview(f, n), 1 | (2 if m.l_fea_type == 'l2' else 0)
-            o.i[0], o.i[1], o.i[2], o.i[3] = n, f.C, f.H, f.W
-            o.f[0], o.f[1], o.p[0], o.t[2] = 1.0 / cnt, float(m.l_fea_w) / cnt, acc + 4 * A_FEA, v.g_feat.view()
+            fwd.add(make_op(_lib.OP_L1DIFF, a=f.view(), b=_nview(f, n), is_f32=1 | (2 if m.l_fea_type == 'l2' else 0), N=n, C=f.C, H=f.H, W=f.W,
+                            coef=1.0 / cnt, gcoef=float(m.l_fea_w) / cnt, loss_acc=acc + 4 * A_FEA, ga=v.g_feat.view()))
         # discriminator forward on [fake_t; real_t] and the generator's GAN loss
         if d is not None:
             fwd.extend(d.fwd)
             lg = d.logits
             cnt = float(n * 1 * lg.H * lg.W)
             if not m.ragan:
-                o = add(fwd, _op(_lib.OP_BCE))
-                o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.i[4] = lg.view(), n, 1, lg.H, lg.W, m.gan_mode
-                o.f[0], o.f[1], o.f[2], o.p[0], o.p[1], o.f[3], o.t[1] = 1.0, 1.0 / cnt, float(m.l_gan_H_target_w) / cnt, acc + 4 * A_GAN, None, 0.0, d.g_logits.view()
+                fwd.add(make_op(_lib.OP_BCE, x=lg.view(), N=n, C=1, H=lg.H, W=lg.W, gan_type=m.gan_mode, target=1.0, coef=1.0 / cnt,
+                                gcoef=float(m.l_gan_H_target_w) / cnt, loss_acc=acc + 4 * A_GAN, grad=d.g_logits.view()))
         if ds is not None:   # l_g_gan_source_Hf = w_src * BCE(D_s(fake_s), 1): value logged WITH the weight (DASR_model.py:258,316)
             fwd.extend(ds.fwd)
             lg = ds.logits
             cnt = float(n * 1 * lg.H * lg.W)
             if not m.ragan:
-                o = add(fwd, _op(_lib.OP_BCE))
-                o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.i[4] = lg.view(), n, 1, lg.H, lg.W, m.gan_mode
-                o.f[0], o.f[1], o.f[2], o.p[0], o.p[1], o.f[3], o.t[1] = 1.0, float(m.l_gan_H_source_w) / cnt, float(m.l_gan_H_source_w) / cnt, \
-                    acc + 4 * A_GAN_SRC, None, 0.0, ds.g_logits.view()
+                fwd.add(make_op(_lib.OP_BCE, x=lg.view(), N=n, C=1, H=lg.H, W=lg.W, gan_type=m.gan_mode, target=1.0, coef=float(m.l_gan_H_source_w) / cnt,
+                                gcoef=float(m.l_gan_H_source_w) / cnt, loss_acc=acc + 4 * A_GAN_SRC, grad=ds.g_logits.view()))
         # relativistic average form (`ragan`, DASR_model.py:240-244,252-256): three stages per loss, the per-pixel batch sums are all-reduced between
         # them under data parallelism (DASR_Model._run_ragan).  Weights: target w * (..)/2 enters the total times w AGAIN (w^2 on the gradient, w on
         # the logged value); source w * (..)/2 is added as is.
@@ -567,7 +526,7 @@ class _StepPlan:
                 g_fake, g_real = D_.g_logits.view(), _nview(D_.g_logits, n)
                 # generator: a = fake (target 1, gradient), b = real (target 0, detached)
                 _ragan_ops(self.rg, fake, real, n, lg.H, lg.W, n * world, 1.0, 0.0, 0.5 * float(w_log) / cnt, 0.5 * float(w_grad) / cnt, sums, part,
-                           acc + 4 * slot_g, None, None, 0.0, g_fake, NULL_T, form=(0, 2, 3)[m.gan_mode])
+                           acc + 4 * slot_g, None, None, 0.0, g_fake, None, form=(0, 2, 3)[m.gan_mode])
                 # discriminator: a = real (target 1), b = fake (target 0), both carry gradient; the whole loss goes to the "real" slot
                 _ragan_ops(lists_d, real, fake, n, lg.H, lg.W, n * world, 1.0, 0.0, 0.5 / cnt, 0.5 / cnt, sums, part,
                            acc + 4 * slots_d[0], acc + 4 * slots_d[1], acc + 4 * slots_d[2], 1.0 / cnt, g_real, g_fake, form=(0, 2, 3)[m.gan_mode])
@@ -580,11 +539,9 @@ class _StepPlan:
         elif self.v is not None:
             v = self.v
             gl.extend(v.bwd)
-            o = add(gl, _op(_lib.OP_AFFINE4))  # adjoint of the input normalisation, accumulated into dL/dSR (source half)
-            o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.t[1], o.i[4], o.i[5] = v.gx.view(), n, 3, H, W, g.g_sr.view(), 1, 1
-            for j in range(4):
-                o.f[j] = ([1.0 / s for s in VGG_STD] + [0.0])[j]
-            C.memmove(C.addressof(o.l), (C.c_float * 4)(0.0, 0.0, 0.0, 0.0), 16)
+            # adjoint of the input normalisation, accumulated into dL/dSR (source half)
+            gl.add(make_op(_lib.OP_AFFINE4, x=v.gx.view(), N=n, C=3, H=H, W=W, y=g.g_sr.view(), y_f32=1, accumulate=1,
+                           scale4=[1.0 / s for s in VGG_STD] + [0.0]))
         if d is not None:
             gl.extend(d.bwd_data_ops(n))
         if ds is not None:
@@ -596,16 +553,13 @@ class _StepPlan:
             for n0, gll, ghc in ((0, g_lo_s, g_hi_s), (n, NULL_T, g_hi_t)):
                 if gll.p is None and ghc.p is None:
                     continue
-                o = add(gl, _op(_lib.OP_DWT_BWD))
-                o.t[0], o.t[1], o.i[0], o.i[1], o.i[2], o.i[3], o.i[4], o.t[2], o.i[5] = gll, ghc, n, 3, Hd, Wd, int(m.norm), _nview(g.g_sr, n0), 1
+                gl.add(make_op(_lib.OP_DWT_BWD, gll=gll, ghc=ghc, N=n, C=3, H2=Hd, W2=Wd, norm=int(m.norm), gx=_nview(g.g_sr, n0), accumulate=1))
         else:
             for n0, glo, ghi in ((0, g_lo_s, g_hi_s), (n, NULL_T, g_hi_t)):
                 if glo.p is None and ghi.p is None:
                     continue
-                o = add(gl, _op(_lib.OP_LOWPASS))
-                o.t[0], o.t[1], o.p[0], o.i[4] = glo, ghi, m.fs_w.data_ptr(), m.fs_k
-                o.i[0], o.i[1], o.i[2], o.i[3], o.i[5], o.i[6] = n, 3, H, W, 1, 1
-                o.f[0], o.f[1], o.t[2], o.t[3] = self.ab[0], 0.0, _nview(g.g_sr, n0), NULL_T
+                gl.add(make_op(_lib.OP_LOWPASS, x=glo, x2=ghi, w=m.fs_w.data_ptr(), k=m.fs_k, N=n, C=3, H=H, W=W, mode=1, a_h=self.ab[0],
+                               out_low=_nview(g.g_sr, n0), accumulate=1))
         self.g_loss_bwd = gl
 
         # ---- discriminator step: BCE(real, 1), BCE(fake, 0), backward with weight gradients -----------------------------------
@@ -614,10 +568,8 @@ class _StepPlan:
             lg = d.logits
             cnt = float(n * lg.H * lg.W)
             for n0, target, a_loss, a_score in (() if m.ragan else ((n, 1.0, A_DREAL, A_SREAL), (0, 0.0, A_DFAKE, A_SFAKE))):
-                o = add(dstep, _op(_lib.OP_BCE))
-                o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.i[4] = _nview(lg, n0), n, 1, lg.H, lg.W, m.gan_mode
-                o.f[0], o.f[1], o.f[2] = target, 0.5 / cnt, 0.5 / cnt
-                o.p[0], o.p[1], o.f[3], o.t[1] = acc + 4 * a_loss, acc + 4 * a_score, 1.0 / cnt, _nview(d.g_logits, n0)
+                dstep.add(make_op(_lib.OP_BCE, x=_nview(lg, n0), N=n, C=1, H=lg.H, W=lg.W, gan_type=m.gan_mode, target=target, coef=0.5 / cnt,
+                                  gcoef=0.5 / cnt, loss_acc=acc + 4 * a_loss, score_acc=acc + 4 * a_score, score_coef=1.0 / cnt, grad=_nview(d.g_logits, n0)))
             dstep.extend(d.bwd_full)
         self.d_step = dstep
         # ---- source-domain discriminator step (DASR_model.py:287-303): the same on [fake_s ; real_s] ------------------------------------
@@ -626,19 +578,18 @@ class _StepPlan:
             lg = self.ds.logits
             cnt = float(n * lg.H * lg.W)
             for n0, target, a_loss, a_score in (() if m.ragan else ((n, 1.0, A_DREAL_SRC, A_SREAL_SRC), (0, 0.0, A_DFAKE_SRC, A_SFAKE_SRC))):
-                o = add(sstep, _op(_lib.OP_BCE))
-                o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.i[4] = _nview(lg, n0), n, 1, lg.H, lg.W, m.gan_mode
-                o.f[0], o.f[1], o.f[2] = target, 0.5 / cnt, 0.5 / cnt
-                o.p[0], o.p[1], o.f[3], o.t[1] = acc + 4 * a_loss, acc + 4 * a_score, 1.0 / cnt, _nview(self.ds.g_logits, n0)
+                sstep.add(make_op(_lib.OP_BCE, x=_nview(lg, n0), N=n, C=1, H=lg.H, W=lg.W, gan_type=m.gan_mode, target=target, coef=0.5 / cnt,
+                                  gcoef=0.5 / cnt, loss_acc=acc + 4 * a_loss, score_acc=acc + 4 * a_score, score_coef=1.0 / cnt,
+                                  grad=_nview(self.ds.g_logits, n0)))
             sstep.extend(self.ds.bwd_full)
         self.ds_step = sstep
 
     def set_d_grad_scale(self, scale):
         for ol in (self.d_step, self.ds_step):
             for o in ol.ops:
-                if o.op == _lib.OP_WGRAD_REDUCE and o.f[0] != scale:
-                    o.f[0] = scale
+                if o.op == _lib.OP_WGRAD_REDUCE and o.get('scale') != scale:
+                    o.set('scale', scale)
                     ol._arr = None
-                if o.op == _lib.OP_BNORM_BWD and o.f[1] != scale:   # dgamma / dbeta of the BatchNorm layers
-                    o.f[1] = scale
+                if o.op == _lib.OP_BNORM_BWD and o.get('pscale') != scale:   # dgamma / dbeta of the BatchNorm layers
+                    o.set('pscale', scale)
                     ol._arr = None

@@ -26,7 +26,8 @@ from collections import OrderedDict
 import torch
 
 from . import _lib
-from .engine import (BTensor, ParamStore, PackRegistry, OpList, WgradGroup, WgradGroup3, Workspace, conv_op, ceil_div, NULL_T, Op, Tensor,
+from ._lib import make_op
+from .engine import (BTensor, ParamStore, PackRegistry, OpList, WgradGroup, WgradGroup3, Workspace, conv_op, ceil_div, Tensor,
                      ensure_runtime_ready, _stream)
 from .gan_nets import NLayerDiscriminatorHIP, BatchNormDiscriminatorHIP, VGGFeatureHIP, VGG16_CFG, fsd_spec, dsn_nld_spec, fold_batchnorm_fsd
 from .models import AdamHIP
@@ -34,12 +35,6 @@ from .dasr_model import gaussian_kernel2d, vgg_random_state_dict, _nview, _ragan
 
 logger = logging.getLogger('base')
 EPS = 1e-8
-
-
-def _op(kind):
-    o = Op()
-    o.op = kind
-    return o
 
 
 def deresnet_spec(n_res_blocks=8, scale=4):
@@ -231,13 +226,9 @@ class _GPlan:
         sp = lambda key: P.ptr(key)
         # ---- forward ----
         f = OpList()
-        o = _op(_lib.OP_NCHW2B)
-        o.p[0], o.i[0], o.i[1], o.i[2], o.i[3], o.t[0], o.t[1] = self.x_nchw.data_ptr(), N, 3, H, W, self.x_in.view(), NULL_T
-        f.add(o)
+        f.add(make_op(_lib.OP_NCHW2B, src=self.x_nchw.data_ptr(), N=N, C=3, H=H, W=W, dst_f32=self.x_in.view()))
         if f16w and nb:
-            o = _op(_lib.OP_CVT_F16)
-            o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.f[0], o.t[1], o.i[4] = self.x_in.view(), N, 16, H, W, 1.0, self.x_s.view(), 1
-            f.add(o)
+            f.add(make_op(_lib.OP_CVT_F16, x=self.x_in.view(), N=N, C=16, H=H, W=W, scale=1.0, y=self.x_s.view(), form=1))
             f.add(conv_op(pack, pk['in_s'], self.x_s.view(), False, 48, H, W, H, W, N, bias=sp('block_input.0.bias'), act=1,
                           slope_ptr=sp('block_input.1.weight'), out_f32=self.s[0].view(), out_bf16=self.s16[0].view(), out16_f16=1, in_wrap=2, out16_lo=4))
         else:
@@ -273,9 +264,7 @@ class _GPlan:
         last = self.d2 if down else self.s[nb]
         f.add(conv_op(pack, pk['out'], last.view(), True, 64, H4, W4, H4, W4, N, bias=sp('block_output.bias'), act=2,
                       out_f32=self.fake.view()))
-        o = _op(_lib.OP_B2NCHW)
-        o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.p[0] = self.fake.view(), N, 3, H4, W4, self.fake_nchw.data_ptr()
-        f.add(o)
+        f.add(make_op(_lib.OP_B2NCHW, src=self.fake.view(), N=N, C=3, H=H4, W=W4, dst=self.fake_nchw.data_ptr()))
         self.fwd = f.tag(1)
         # ---- backward (input: g_fake = dL/d fake) ----
         b = OpList()
@@ -290,11 +279,11 @@ class _GPlan:
             b.keep.append(grp)
 
         def prelu_grad(key, y, gx, h, w, f16=False):
-            o = _op(_lib.OP_PRELU_GRAD)
-            o.t[0], o.t[1], o.i[0], o.i[1], o.i[2], o.i[3] = y.view(), gx.view(), N, 64, h, w
-            o.p[0], o.p[1], o.p[2], o.f[0] = sp(key), self.scratch.data_ptr(), P.ptr(key, P.grad), 1.0
+            o = make_op(_lib.OP_PRELU_GRAD, y=y.view(), gx=gx.view(), N=N, C=64, H=h, W=w, slope=sp(key), scratch256=self.scratch.data_ptr(),
+                        dst=P.ptr(key, P.grad), scale=1.0)
             if f16:   # f16 shadows: the gradient carries gscale
-                o.i[4], o.f[1] = 1, 1.0 / self.gscale
+                o.set('f16', 1)
+                o.set('inv_prescale', 1.0 / self.gscale)
             b.add(o)
             self._prelu_ops.append(o)
 
@@ -309,9 +298,7 @@ class _GPlan:
 
         self._prelu_ops = []
         self._prelu_final = None
-        o = _op(_lib.OP_SIGMOID_BWD)
-        o.t[0], o.t[1], o.i[0], o.i[1], o.i[2], o.i[3], o.t[2] = self.fake.view(), self.g_fake.view(), N, 3, H4, W4, self.gz_out.view()
-        b.add(o)
+        b.add(make_op(_lib.OP_SIGMOID_BWD, y=self.fake.view(), g=self.g_fake.view(), N=N, C=3, H=H4, W=W4, gz=self.gz_out.view()))
         wg('block_output.', self.gz_out, last, 3, 64, H4, W4, H4, W4)
         gs = self.g_s[0]
         if down:
@@ -326,9 +313,7 @@ class _GPlan:
         else:   # Generator (DSGAN): the output conv reads the residual stream directly (no activation in between)
             b.add(conv_op(pack, pk['out_b'], self.gz_out.view(), True, 16, H, W, H, W, N, out_f32=gs.view()))
         if b16 and nb:   # gscale * dL/ds[nb] in f16
-            o = _op(_lib.OP_CVT_F16)
-            o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.f[0], o.t[1] = gs.view(), N, 64, H, W, self.gscale, self.g_s16[nb].view()
-            b.add(o)
+            b.add(make_op(_lib.OP_CVT_F16, x=gs.view(), N=N, C=64, H=H, W=W, scale=self.gscale, y=self.g_s16[nb].view()))
         wgrp = None
         if b16 and nb:
             wgrp = WgradGroup3()
@@ -379,11 +364,9 @@ class _GPlan:
             keys = ['res_blocks.%d.prelu.weight' % k for k in range(nb)]
             self.prelu_slopes = torch.tensor([sp(k_) for k_ in keys], dtype=torch.int64, device=dev)
             self.prelu_dsts = torch.tensor([P.ptr(k_, P.grad) for k_ in keys], dtype=torch.int64, device=dev)
-            o = _op(_lib.OP_PRELU_FINAL)
-            o.p[0], o.i[0], o.l[0], o.i[1] = self.prelu_part.data_ptr(), self.prelu_nblk, self.prelu_nblk, nb
-            o.p[1], o.p[2], o.f[0] = self.prelu_slopes.data_ptr(), self.prelu_dsts.data_ptr(), 1.0 / self.gscale
-            b.add(o)
-            self._prelu_final = o
+            self._prelu_final = make_op(_lib.OP_PRELU_FINAL, partial=self.prelu_part.data_ptr(), nblocks=self.prelu_nblk, stride=self.prelu_nblk, count=nb,
+                                        slopes=self.prelu_slopes.data_ptr(), dsts=self.prelu_dsts.data_ptr(), scale=1.0 / self.gscale)
+            b.add(self._prelu_final)
             b.keep += [self.prelu_part, self.prelu_slopes, self.prelu_dsts]
         if wgrp is not None:   # all 2 nb residual-block weight gradients: one launch of 2 nb parts, one reduce
             wgrp.finalize(self.ws, dev)
@@ -391,11 +374,8 @@ class _GPlan:
                 b.add(op)
             b.keep.append(wgrp)
         # s[0] = PReLU(conv_in(x)): apply PReLU' to dL/ds0, then the input conv's weight gradient
-        o = _op(_lib.OP_AXPBY)
-        o.t[0], o.f[0], o.t[1], o.f[1] = gs.view(), 1.0, NULL_T, 0.0
-        o.i[0], o.i[1], o.i[2], o.i[3] = N, 64, H, W
-        o.t[2], o.t[3], o.f[2], o.t[4], o.f[3], o.p[0] = self.g_h.view(), NULL_T, 1.0, self.s[0].view(), 0.25, sp('block_input.1.weight')
-        b.add(o)
+        b.add(make_op(_lib.OP_AXPBY, x=gs.view(), a=1.0, N=N, C=64, H=H, W=W, out_f32=self.g_h.view(), gamma=1.0, mask=self.s[0].view(), slope=0.25,
+                      slope_ptr=sp('block_input.1.weight')))
         prelu_grad('block_input.1.weight', self.s[0], self.g_h, H, W)
         wg('block_input.0.', self.g_h, self.x_in, 64, 3, H, W, H, W)
         self.bwd = b.tag(4)
@@ -404,11 +384,11 @@ class _GPlan:
     def set_grad_scale(self, scale):
         for o in self.bwd.ops:
             if o.op == _lib.OP_WGRAD_REDUCE:
-                o.f[0] = scale
+                o.set('scale', scale)
         for o in self._prelu_ops:
-            o.f[0] = scale
+            o.set('scale', scale)
         if getattr(self, '_prelu_final', None) is not None:   # (the fused form: data-parallel factor x 1 / pre-scale of the 16-bit backward)
-            self._prelu_final.f[0] = scale / self.gscale
+            self._prelu_final.set('scale', scale / self.gscale)
         self.bwd._arr = None
 
 
@@ -738,9 +718,7 @@ class DSNModel:
             nchw = torch.zeros((2 * n, 3, h, w), dtype=torch.float32, device=self.device)
             img = BTensor(2 * n, 16, h, w, True, self.device)
             ops = OpList()
-            o = _op(_lib.OP_NCHW2B)
-            o.p[0], o.i[0], o.i[1], o.i[2], o.i[3], o.t[0], o.t[1] = nchw.data_ptr(), 2 * n, 3, h, w, img.view(), NULL_T
-            ops.add(o)
+            ops.add(make_op(_lib.OP_NCHW2B, src=nchw.data_ptr(), N=2 * n, C=3, H=h, W=w, dst_f32=img.view()))
             ops.add(v.input_copy_op(img.view(), 0, 2 * n, h, w))
             ops.extend(v.fwd)
             ops.keep += [v, nchw, img]
@@ -851,54 +829,36 @@ class _GradPenaltyPlan:
         self.ws = Workspace(dev)
         ops = OpList()
         # ---- sample (already behind the linear front end: F(r real + (1 - r) fake) = r F(real) + (1 - r) F(fake), the + 0.5 of the normalisation included)
-        o = _op(_lib.OP_AXPBY)
-        o.t[0], o.f[0], o.t[1], o.f[1] = _nview(d.x, N), 0.5, d.x.view(), 0.5       # f[0] = r (real half), f[1] = 1 - r (fake half): set_mix()
-        o.i[0], o.i[1], o.i[2], o.i[3] = N, nc, hd, wd
-        o.t[2], o.t[3], o.f[2], o.t[4] = dg.x.view(), NULL_T, 1.0, NULL_T
-        self.mix_op = len(ops.ops)
-        ops.add(o)
+        self.mix_op = len(ops.ops)   # a = r (real half), b = 1 - r (fake half): set_mix()
+        ops.add(make_op(_lib.OP_AXPBY, x=_nview(d.x, N), a=0.5, z=d.x.view(), b=0.5, N=N, C=nc, H=hd, W=wd, out_f32=dg.x.view(), gamma=1.0))
         ops.extend(dg.fwd)
         if m.bn:
             ops.extend(dg.running_ops(0))
         lg = dg.logits
         cnt = float(N * lg.H * lg.W)
-        o = _op(_lib.OP_FILL_SCALED)                  # d mean D / d D = 1 / cnt
-        o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.p[0], o.f[0] = dg.g_logits.view(), N, 1, lg.H, lg.W, self.one.data_ptr(), 1.0 / cnt
-        ops.add(o)
+        # d mean D / d D = 1 / cnt
+        ops.add(make_op(_lib.OP_FILL_SCALED, x=dg.g_logits.view(), N=N, C=1, H=lg.H, W=lg.W, scalar=self.one.data_ptr(), factor=1.0 / cnt))
         ops.extend(dg.bwd_data_ops(N))                # -> dg.gx = d mean D / d (front-end output)
-        o = _op(_lib.OP_FILL)
-        o.p[0], o.l[0], o.f[0] = self.g_img.t.data_ptr(), self.g_img.t.numel(), 0.0
-        ops.add(o)
+        ops.add(make_op(_lib.OP_FILL, p=self.g_img.t.data_ptr(), n=self.g_img.t.numel(), value=0.0))
         if wav:                                       # adjoint of the front end -> g = d mean D / d sample (image space)
-            o = _op(_lib.OP_DWT_BWD)
-            o.t[0], o.t[1], o.i[0], o.i[1], o.i[2], o.i[3], o.i[4], o.t[2], o.i[5] = NULL_T, dg.gx.view(), N, 3, hd, wd, m.dwt_norm, self.g_img.view(), 1
+            ops.add(make_op(_lib.OP_DWT_BWD, ghc=dg.gx.view(), N=N, C=3, H2=hd, W2=wd, norm=m.dwt_norm, gx=self.g_img.view(), accumulate=1))
         else:
-            o = _op(_lib.OP_LOWPASS)
-            o.t[0], o.t[1], o.p[0], o.i[4] = NULL_T, dg.gx.view(), m.fw.data_ptr(), k
-            o.i[0], o.i[1], o.i[2], o.i[3], o.i[5], o.i[6] = N, 3, h, w, 1 | norm_valid, 1
-            o.f[0], o.f[1], o.t[2], o.t[3] = 0.5, 0.0, self.g_img.view(), NULL_T
-        ops.add(o)
+            ops.add(make_op(_lib.OP_LOWPASS, x2=dg.gx.view(), w=m.fw.data_ptr(), k=k, N=N, C=3, H=h, W=w, mode=1 | norm_valid, accumulate=1, a_h=0.5,
+                            out_low=self.g_img.view()))
         # out3 = {||g||, 10 (||g|| - 1)^2, 20 (||g|| - 1) / ||g||}; acc[slot] += the penalty.  Data parallel: two stages around the all-reduce of the ranks'
         # sums of squares (dasr_grad_penalty; DSNModel.iteration runs ops[:cut], all-reduces out3[3], runs ops[cut:])
         self.world = m.dp.world if (getattr(m, 'dp', None) is not None and m.dp.active) else 1
         for stage in ((0,) if self.world == 1 else (1, 2)):
-            o = _op(_lib.OP_GRAD_PENALTY)
-            o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.f[0] = self.g_img.view(), N, 3, h, w, 10.0
-            o.p[0], o.p[1], o.p[2] = self.part.data_ptr(), self.out3.data_ptr(), m.acc.data_ptr() + 4 * acc_slot
-            o.i[4], o.i[5] = stage, self.world
-            ops.add(o)
+            ops.add(make_op(_lib.OP_GRAD_PENALTY, g=self.g_img.view(), N=N, C=3, H=h, W=w, weight=10.0, part256=self.part.data_ptr(), out3=self.out3.data_ptr(),
+                            loss_acc=m.acc.data_ptr() + 4 * acc_slot, stage=stage, world=self.world))
             if stage == 1:
                 self.cut = len(ops.ops)
         # ---- tangent pass along u = g: t0 = (linear part of the front end)(g)
         if wav:
-            o = _op(_lib.OP_DWT_FWD)
-            o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.i[4], o.t[1], o.t[2] = self.g_img.view(), N, 3, hd, wd, m.dwt_norm | 4, NULL_T, self.t0.view()
+            ops.add(make_op(_lib.OP_DWT_FWD, x=self.g_img.view(), N=N, C=3, H2=hd, W2=wd, norm=m.dwt_norm | 4, hc=self.t0.view()))
         else:
-            o = _op(_lib.OP_LOWPASS)
-            o.t[0], o.t[1], o.p[0], o.i[4] = self.g_img.view(), NULL_T, m.fw.data_ptr(), k
-            o.i[0], o.i[1], o.i[2], o.i[3], o.i[5], o.i[6] = N, 3, h, w, 0 | norm_valid, 0
-            o.f[0], o.f[1], o.t[2], o.t[3] = 0.5, 0.0, NULL_T, self.t0.view()
-        ops.add(o)
+            ops.add(make_op(_lib.OP_LOWPASS, x=self.g_img.view(), w=m.fw.data_ptr(), k=k, N=N, C=3, H=h, W=w, mode=0 | norm_valid, a_h=0.5,
+                            out_high=self.t0.view()))
         keep = []
         adot, zdot = [None] * nl, [None] * nl        # tangents of the layer outputs (after norm + lrelu) / of the conv outputs in front of a norm
         src = self.t0
@@ -909,14 +869,11 @@ class _GradPenaltyPlan:
                 adot[i] = B(dg.acts[i])
                 ops.add(conv_op(pack, L['fwd'], src.view(), True, L['cin_pad'], hi, wi, ho, wo, N, kh=L['kh'], stride=L['stride'], pad=L['pad'], out_f32=zdot[i].view()))
                 if L['norm'] == 'batch':
-                    o = _op(_lib.OP_BNORM_JVP)
-                    o.t[0], o.t[1], o.i[0], o.i[1], o.i[2], o.i[3], o.i[4] = dg.zs[i].view(), zdot[i].view(), N, L['cout'], ho, wo, dg.group
-                    o.f[0], o.p[0], o.p[1], o.p[2], o.t[2] = D_SLOPE, P.ptr(L['bn'] + 'weight'), P.ptr(L['bn'] + 'bias'), dg.stats[i].data_ptr(), adot[i].view()
+                    ops.add(make_op(_lib.OP_BNORM_JVP, x=dg.zs[i].view(), t=zdot[i].view(), N=N, C=L['cout'], H=ho, W=wo, group=dg.group, slope=D_SLOPE,
+                                    gamma=P.ptr(L['bn'] + 'weight'), beta=P.ptr(L['bn'] + 'bias'), stats=dg.stats[i].data_ptr(), out=adot[i].view()))
                 else:
-                    o = _op(_lib.OP_INORM_JVP)
-                    o.t[0], o.t[1], o.i[0], o.i[1], o.i[2], o.i[3] = dg.acts[i].view(), zdot[i].view(), N, L['cout'], ho, wo
-                    o.f[0], o.p[0], o.t[2] = D_SLOPE, dg.stats[i].data_ptr(), adot[i].view()
-                ops.add(o)
+                    ops.add(make_op(_lib.OP_INORM_JVP, a=dg.acts[i].view(), t=zdot[i].view(), N=N, C=L['cout'], H=ho, W=wo, slope=D_SLOPE,
+                                    stats=dg.stats[i].data_ptr(), out=adot[i].view()))
             else:   # conv + lrelu: adot = lrelu'(a) * conv(tangent) (the mask multiplies the conv output in the epilogue; no bias on a tangent)
                 adot[i] = B(dg.acts[i])
                 ops.add(conv_op(pack, L['fwd'], src.view(), True, L['cin_pad'], hi, wi, ho, wo, N, kh=L['kh'], stride=L['stride'], pad=L['pad'],
@@ -925,9 +882,7 @@ class _GradPenaltyPlan:
         # ---- reverse pass over (primal, tangent): s = mean(conv_last(adot)), upstream c / cnt
         Ll = net.layers[-1]
         gz = B(dg.g_logits)                           # adjoint of the last conv's TANGENT output
-        o = _op(_lib.OP_FILL_SCALED)
-        o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.p[0], o.f[0] = gz.view(), N, 1, lg.H, lg.W, self.out3.data_ptr() + 8, 1.0 / cnt
-        ops.add(o)
+        ops.add(make_op(_lib.OP_FILL_SCALED, x=gz.view(), N=N, C=1, H=lg.H, W=lg.W, scalar=self.out3.data_ptr() + 8, factor=1.0 / cnt))
         GS = 256.0   # power-of-two pre-scale of the f16-staged weight-gradient operands (the adjoints here are c / cnt ~ 1e-2 .. 1e1)
 
         def wgrad(i, pairs, bias):
@@ -958,28 +913,21 @@ class _GradPenaltyPlan:
                 (ho, wo) = dg.dims[i + 1]
                 gdst = (self.grad.data_ptr() + 4 * P.off(L['bn'] + 'weight'), self.grad.data_ptr() + 4 * P.off(L['bn'] + 'bias'))
                 for ga_, out_, prim in ((g_adot, g_zdot, False),) + (((g_a, g_z, True),) if g_a is not None else ()):
-                    o = _op(_lib.OP_BNORM_BWD)
-                    o.t[0], o.t[1], o.i[0], o.i[1], o.i[2], o.i[3], o.i[4] = dg.zs[i].view(), ga_.view(), N, L['cout'], ho, wo, dg.group
-                    o.f[0], o.p[0], o.p[1], o.p[2], o.t[2] = D_SLOPE, P.ptr(L['bn'] + 'weight'), P.ptr(L['bn'] + 'bias'), dg.stats[i].data_ptr(), out_.view()
-                    o.p[3], o.l[0], o.f[1] = (gdst[0] if prim else None), (gdst[1] if prim else 0), 1.0
-                    ops.add(o)
-                o = _op(_lib.OP_BNORM_SECOND)
-                o.t[0], o.t[1], o.t[2], o.i[0], o.i[1], o.i[2], o.i[3], o.i[4] = dg.zs[i].view(), zdot[i].view(), g_adot.view(), N, L['cout'], ho, wo, dg.group
-                o.f[0], o.p[0], o.p[1], o.p[2], o.t[3] = D_SLOPE, P.ptr(L['bn'] + 'weight'), P.ptr(L['bn'] + 'bias'), dg.stats[i].data_ptr(), g_z.view()
-                o.i[5], o.p[3], o.f[1] = (1 if g_a is not None else 0), gdst[0], 1.0
-                ops.add(o)
+                    ops.add(make_op(_lib.OP_BNORM_BWD, x=dg.zs[i].view(), ga=ga_.view(), N=N, C=L['cout'], H=ho, W=wo, group=dg.group, slope=D_SLOPE,
+                                    gamma=P.ptr(L['bn'] + 'weight'), beta=P.ptr(L['bn'] + 'bias'), stats=dg.stats[i].data_ptr(), gx=out_.view(),
+                                    dgamma=gdst[0] if prim else None, dbeta=gdst[1] if prim else None, pscale=1.0))
+                ops.add(make_op(_lib.OP_BNORM_SECOND, x=dg.zs[i].view(), t=zdot[i].view(), ga=g_adot.view(), N=N, C=L['cout'], H=ho, W=wo, group=dg.group,
+                                slope=D_SLOPE, gamma=P.ptr(L['bn'] + 'weight'), beta=P.ptr(L['bn'] + 'bias'), stats=dg.stats[i].data_ptr(), out=g_z.view(),
+                                accumulate=1 if g_a is not None else 0, dgamma=gdst[0], pscale=1.0))
                 mask = None
             elif L['norm']:
                 g_zdot, g_z = B(dg.zs[i]), B(dg.zs[i])
                 for ga_, out_ in ((g_adot, g_zdot),) + (((g_a, g_z),) if g_a is not None else ()):   # J (lrelu'(a) ga): the first-order InstanceNorm backward on both adjoints
-                    o = _op(_lib.OP_INORM_BWD)
-                    o.t[0], o.t[1], o.i[0], o.i[1], o.i[2], o.i[3] = dg.acts[i].view(), ga_.view(), N, L['cout'], dg.dims[i + 1][0], dg.dims[i + 1][1]
-                    o.f[0], o.p[0], o.t[2] = D_SLOPE, dg.stats[i].data_ptr(), out_.view()
-                    ops.add(o)
-                o = _op(_lib.OP_INORM_SECOND)        # + the dependence of J on z: tangent zdot, upstream lrelu'(a) * g_adot
-                o.t[0], o.t[1], o.t[2], o.i[0], o.i[1], o.i[2], o.i[3] = dg.acts[i].view(), zdot[i].view(), g_adot.view(), N, L['cout'], dg.dims[i + 1][0], dg.dims[i + 1][1]
-                o.f[0], o.p[0], o.t[3], o.i[4] = D_SLOPE, dg.stats[i].data_ptr(), g_z.view(), 1 if g_a is not None else 0
-                ops.add(o)
+                    ops.add(make_op(_lib.OP_INORM_BWD, a=dg.acts[i].view(), ga=ga_.view(), N=N, C=L['cout'], H=dg.dims[i + 1][0], W=dg.dims[i + 1][1],
+                                    slope=D_SLOPE, stats=dg.stats[i].data_ptr(), gx=out_.view()))
+                # + the dependence of J on z: tangent zdot, upstream lrelu'(a) * g_adot
+                ops.add(make_op(_lib.OP_INORM_SECOND, a=dg.acts[i].view(), t=zdot[i].view(), ga=g_adot.view(), N=N, C=L['cout'], H=dg.dims[i + 1][0],
+                                W=dg.dims[i + 1][1], slope=D_SLOPE, stats=dg.stats[i].data_ptr(), out=g_z.view(), accumulate=1 if g_a is not None else 0))
                 mask = None
             else:   # conv + lrelu: the adjoints pass through lrelu'(a) (applied as the mask of the data-gradient convs of the layer ABOVE, see below)
                 g_zdot, g_z = g_adot, g_a
@@ -999,8 +947,8 @@ class _GradPenaltyPlan:
         self.ops = ops.tag(10)
 
     def set_mix(self, r):
-        self.ops.set_f(self.mix_op, 0, float(r))
-        self.ops.set_f(self.mix_op, 1, 1.0 - float(r))
+        self.ops.set(self.mix_op, 'a', float(r))
+        self.ops.set(self.mix_op, 'b', 1.0 - float(r))
 
 
 class _DSNPlan:
@@ -1025,25 +973,17 @@ class _DSNPlan:
         o_ = m.opt
         f = OpList()
         f.extend(g.fwd)
-        o = _op(_lib.OP_FILL)
-        o.p[0], o.l[0], o.f[0] = acc, 8, 0.0
-        f.add(o)
+        f.add(make_op(_lib.OP_FILL, p=acc, n=8, value=0.0))
         for src, dst in ((self.bic_nchw, self.bic_b), (self.real_nchw, self.real_b)):
-            o = _op(_lib.OP_NCHW2B)
-            o.p[0], o.i[0], o.i[1], o.i[2], o.i[3], o.t[0], o.t[1] = src.data_ptr(), N, 3, h, w, dst.view(), NULL_T
-            f.add(o)
+            f.add(make_op(_lib.OP_NCHW2B, src=src.data_ptr(), N=N, C=3, H=h, W=w, dst_f32=dst.view()))
         # discriminator front end on fake -> d.x[:N], real -> d.x[N:]
         norm_valid = 2 if m.filter == 'avg_pool' else 0
         for src, n0 in ((g.fake, 0), (self.real_b, N)):
             if wav:
-                o = _op(_lib.OP_DWT_FWD)
-                o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.i[4], o.t[1], o.t[2] = src.view(), N, 3, hd, wd, m.dwt_norm, NULL_T, _nview(d.x, n0)
+                f.add(make_op(_lib.OP_DWT_FWD, x=src.view(), N=N, C=3, H2=hd, W2=wd, norm=m.dwt_norm, hc=_nview(d.x, n0)))
             else:
-                o = _op(_lib.OP_LOWPASS)
-                o.t[0], o.t[1], o.p[0], o.i[4] = src.view(), NULL_T, m.fw.data_ptr(), k
-                o.i[0], o.i[1], o.i[2], o.i[3], o.i[5], o.i[6] = N, 3, h, w, 0 | norm_valid, 0
-                o.f[0], o.f[1], o.t[2], o.t[3] = 0.5, 0.5, NULL_T, _nview(d.x, n0)
-            f.add(o)
+                f.add(make_op(_lib.OP_LOWPASS, x=src.view(), w=m.fw.data_ptr(), k=k, N=N, C=3, H=h, W=w, mode=0 | norm_valid, a_h=0.5, b_h=0.5,
+                              out_high=_nview(d.x, n0)))
         f.extend(d.fwd)
         # BatchNorm discriminator: the reference calls D(real) then D(fake) (with --ragan: net(real), net(fake), net(fake), net(real)); every call
         # in training mode moves the running statistics once, with that call's batch statistics (group 0 = fake half, 1 = real half)
@@ -1072,31 +1012,22 @@ class _DSNPlan:
                 self.ragan_cuts_fwd.append(len(f.ops))
         # discriminator loss: -log(real) - log(1 - fake)   (acc[0], acc[1]); scores acc[4] (real), acc[5] (fake)
         for n0, target, a_loss, a_score in (((N, 1.0, 0, 4), (0, 0.0, 1, 5)) if m.wgan else ()):   # --wgan: -mean(real) + mean(fake) on the raw map (loss.py:33-36)
-            o = _op(_lib.OP_BCE)
-            o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.i[4] = _nview(lg, n0), N, 1, lg.H, lg.W, 2
-            o.f[0], o.f[1], o.f[2] = target, 1.0 / cnt, (2.0 if m.ragan else 1.0) / cnt   # (--ragan: both relativistic terms carry every logit once)
-            o.p[0], o.p[1], o.f[3], o.t[1] = acc + 4 * a_loss, acc + 4 * a_score, 1.0 / cnt, _nview(d.g_logits, n0)
-            f.add(o)
+            # (--ragan: both relativistic terms carry every logit once)
+            f.add(make_op(_lib.OP_BCE, x=_nview(lg, n0), N=N, C=1, H=lg.H, W=lg.W, gan_type=2, target=target, coef=1.0 / cnt,
+                          gcoef=(2.0 if m.ragan else 1.0) / cnt, loss_acc=acc + 4 * a_loss, score_acc=acc + 4 * a_score, score_coef=1.0 / cnt,
+                          grad=_nview(d.g_logits, n0)))
         for n0, mode, a_loss, a_score in (() if (m.rel or m.wgan) else ((N, 0, 0, 4), (0, 1, 1, 5))):
-            o = _op(_lib.OP_LOGLOSS)
-            o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.i[4] = _nview(lg, n0), N, lg.H, lg.W, mode, 0
-            o.f[0], o.f[1], o.f[2], o.f[3] = EPS, 1.0 / cnt, 1.0 / cnt, 1.0 / cnt
-            o.p[0], o.p[1], o.t[1] = acc + 4 * a_loss, acc + 4 * a_score, _nview(d.g_logits, n0)
-            f.add(o)
+            f.add(make_op(_lib.OP_LOGLOSS, x=_nview(lg, n0), N=N, H=lg.H, W=lg.W, mode=mode, eps=EPS, coef=1.0 / cnt, gcoef=1.0 / cnt, score_coef=1.0 / cnt,
+                          loss_acc=acc + 4 * a_loss, score_acc=acc + 4 * a_score, grad=_nview(d.g_logits, n0)))
         # colour loss: L1 between the low-pass of fake and of the bicubic LR (acc[3])
         for src, dst in ((g.fake, self.col_f), (self.bic_b, self.col_b)):
             if wav:
-                o = _op(_lib.OP_DWT_FWD)
-                o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.i[4], o.t[1], o.t[2] = src.view(), N, 3, hd, wd, 1, dst.view(), NULL_T
+                f.add(make_op(_lib.OP_DWT_FWD, x=src.view(), N=N, C=3, H2=hd, W2=wd, norm=1, ll=dst.view()))
             else:
-                o = _op(_lib.OP_LOWPASS_VALID)
-                o.t[0], o.p[0], o.i[4], o.i[0], o.i[1], o.i[2], o.i[3], o.i[5], o.t[1], o.i[6] = src.view(), m.fw.data_ptr(), k, N, 3, h, w, 0, dst.view(), 0
-            f.add(o)
-        o = _op(_lib.OP_L1DIFF)
+                f.add(make_op(_lib.OP_LOWPASS_VALID, x=src.view(), w=m.fw.data_ptr(), k=k, N=N, C=3, H=h, W=w, out=dst.view()))
         ccnt = float(N * 3 * hc * wc)
-        o.t[0], o.t[1], o.i[4], o.i[0], o.i[1], o.i[2], o.i[3] = self.col_f.view(), self.col_b.view(), 1, N, 3, hc, wc
-        o.f[0], o.f[1], o.p[0], o.t[2] = 1.0 / ccnt, float(o_['w_col']) / ccnt, acc + 4 * 3, self.g_col.view()
-        f.add(o)
+        f.add(make_op(_lib.OP_L1DIFF, a=self.col_f.view(), b=self.col_b.view(), is_f32=1, N=N, C=3, H=hc, W=wc, coef=1.0 / ccnt,
+                      gcoef=float(o_['w_col']) / ccnt, loss_acc=acc + 4 * 3, ga=self.g_col.view()))
         self.v = None
         lpips = m.netF is not None and o_['per_type'] == 'LPIPS'
         if lpips:                # perceptual: LPIPS(fake, bicubic).mean() -> acc[6]; head gradients (weight w_per) in the forward list
@@ -1114,11 +1045,9 @@ class _DSNPlan:
                 f.add(v.input_copy_op(src.view(), n0, N, h, w))
             f.extend(v.fwd)
             ft = v.feat
-            o = _op(_lib.OP_L1DIFF)
             fcnt = float(N * ft.C * ft.H * ft.W)
-            o.t[0], o.t[1], o.i[4], o.i[0], o.i[1], o.i[2], o.i[3] = ft.view(), _nview(ft, N), 1 | 2, N, ft.C, ft.H, ft.W
-            o.f[0], o.f[1], o.p[0], o.t[2] = 1.0 / fcnt, float(o_['w_per']) / fcnt, acc + 4 * 6, v.g_feat.view()
-            f.add(o)
+            f.add(make_op(_lib.OP_L1DIFF, a=ft.view(), b=_nview(ft, N), is_f32=1 | 2, N=N, C=ft.C, H=ft.H, W=ft.W, coef=1.0 / fcnt,
+                          gcoef=float(o_['w_per']) / fcnt, loss_acc=acc + 4 * 6, ga=v.g_feat.view()))
         self.fwd = f
         # D weight gradients from the pre-update graph
         self.d_bwd = d.bwd_full
@@ -1128,50 +1057,33 @@ class _DSNPlan:
         if m.rel:   # -log(sigmoid(fake - mean_n(real)) + eps): stage 0's sums are still valid, the real term is absent (t < 0), real carries no gradient
             rl = [OpList(), OpList(), OpList()]
             _ragan_ops(rl, _nview(lg, N), lg.view(), N, lg.H, lg.W, N * self.ragan_world, -1.0, 1.0, 1.0 / cnt, float(o_['w_tex']) / cnt, self.r_sums, self.r_part,
-                       acc + 4 * 2, None, None, 0.0, NULL_T, d.g_logits.view(), form=1, eps=EPS, stages=(1, 2))
+                       acc + 4 * 2, None, None, 0.0, None, d.g_logits.view(), form=1, eps=EPS, stages=(1, 2))
             gb.extend(rl[1])
             self.ragan_cut_gbwd = len(gb.ops)
             gb.extend(rl[2])
         elif m.wgan:   # generator_loss(wasserstein): mean(-fake_tex) (loss.py:18-19): value -> acc[2], gradient w_tex * (-1 / cnt) -> g_logits[:N]
-            o = _op(_lib.OP_BCE)
-            o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.i[4] = lg.view(), N, 1, lg.H, lg.W, 2
-            o.f[0], o.f[1], o.f[2] = 1.0, 1.0 / cnt, float(o_['w_tex']) / cnt
-            o.p[0], o.p[1], o.f[3], o.t[1] = acc + 4 * 2, None, 0.0, d.g_logits.view()
-            gb.add(o)
-        else:
-            o = _op(_lib.OP_LOGLOSS)   # -log(fake_tex) on the fake half: value -> acc[2], gradient -> g_logits[:N]
-            o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.i[4] = lg.view(), N, lg.H, lg.W, 0, 0
-            o.f[0], o.f[1], o.f[2], o.f[3] = EPS, 1.0 / cnt, float(o_['w_tex']) / cnt, 0.0
-            o.p[0], o.p[1], o.t[1] = acc + 4 * 2, None, d.g_logits.view()
-            gb.add(o)
+            gb.add(make_op(_lib.OP_BCE, x=lg.view(), N=N, C=1, H=lg.H, W=lg.W, gan_type=2, target=1.0, coef=1.0 / cnt, gcoef=float(o_['w_tex']) / cnt,
+                           loss_acc=acc + 4 * 2, grad=d.g_logits.view()))
+        else:   # -log(fake_tex) on the fake half: value -> acc[2], gradient -> g_logits[:N]
+            gb.add(make_op(_lib.OP_LOGLOSS, x=lg.view(), N=N, H=lg.H, W=lg.W, eps=EPS, coef=1.0 / cnt, gcoef=float(o_['w_tex']) / cnt, loss_acc=acc + 4 * 2,
+                           grad=d.g_logits.view()))
         gb.extend(d.bwd_data_ops(N))
-        o = _op(_lib.OP_FILL)
-        o.p[0], o.l[0], o.f[0] = g.g_fake.t.data_ptr(), g.g_fake.t.numel(), 0.0
-        gb.add(o)
+        gb.add(make_op(_lib.OP_FILL, p=g.g_fake.t.data_ptr(), n=g.g_fake.t.numel(), value=0.0))
         if wav:
-            o = _op(_lib.OP_DWT_BWD)
-            o.t[0], o.t[1], o.i[0], o.i[1], o.i[2], o.i[3], o.i[4], o.t[2], o.i[5] = self.g_col.view(), d.gx.view(), N, 3, hd, wd, m.dwt_norm, g.g_fake.view(), 1
-            gb.add(o)
-        else:
-            o = _op(_lib.OP_LOWPASS)   # adjoint of the high-pass front end
-            o.t[0], o.t[1], o.p[0], o.i[4] = NULL_T, d.gx.view(), m.fw.data_ptr(), k
-            o.i[0], o.i[1], o.i[2], o.i[3], o.i[5], o.i[6] = N, 3, h, w, 1 | norm_valid, 1
-            o.f[0], o.f[1], o.t[2], o.t[3] = 0.5, 0.0, g.g_fake.view(), NULL_T
-            gb.add(o)
-            o = _op(_lib.OP_LOWPASS_VALID)
-            o.t[0], o.p[0], o.i[4], o.i[0], o.i[1], o.i[2], o.i[3], o.i[5], o.t[1], o.i[6] = self.g_col.view(), m.fw.data_ptr(), k, N, 3, h, w, 1, g.g_fake.view(), 1
-            gb.add(o)
+            gb.add(make_op(_lib.OP_DWT_BWD, gll=self.g_col.view(), ghc=d.gx.view(), N=N, C=3, H2=hd, W2=wd, norm=m.dwt_norm, gx=g.g_fake.view(),
+                           accumulate=1))
+        else:   # adjoint of the high-pass front end
+            gb.add(make_op(_lib.OP_LOWPASS, x2=d.gx.view(), w=m.fw.data_ptr(), k=k, N=N, C=3, H=h, W=w, mode=1 | norm_valid, accumulate=1, a_h=0.5,
+                           out_low=g.g_fake.view()))
+            gb.add(make_op(_lib.OP_LOWPASS_VALID, x=self.g_col.view(), w=m.fw.data_ptr(), k=k, N=N, C=3, H=h, W=w, mode=1, out=g.g_fake.view(),
+                           accumulate=1))
         if lpips:
             gb.extend(self.v.bwd)
             self.sym_ops.append((gb, len(gb.ops), 1))
             gb.add(self.v.adjoint_op(g.g_fake.view()))
         elif self.v is not None:
             gb.extend(self.v.bwd)
-            o = _op(_lib.OP_AXPBY)
-            o.t[0], o.f[0], o.t[1], o.f[1] = g.g_fake.view(), 1.0, self.v.gx.view(), 1.0
-            o.i[0], o.i[1], o.i[2], o.i[3] = N, 16, h, w
-            o.t[2], o.t[3], o.f[2], o.t[4] = g.g_fake.view(), NULL_T, 1.0, NULL_T
-            gb.add(o)
+            gb.add(make_op(_lib.OP_AXPBY, x=g.g_fake.view(), a=1.0, z=self.v.gx.view(), b=1.0, N=N, C=16, H=h, W=w, out_f32=g.g_fake.view(), gamma=1.0))
         gb.extend(g.bwd)
         self.g_bwd = gb
 
@@ -1180,7 +1092,7 @@ class _DSNPlan:
         if xf and (xf & 1) and self.v.H != self.v.W:
             raise ValueError('--lpips_rot_flip with a rotation needs square crops (torch.rot90 would change the shape)')
         for lst, idx, base in getattr(self, 'sym_ops', ()):
-            lst.set_i(idx, 3, base | (xf << 4))
+            lst.set(idx, 'mode', base | (xf << 4))
 
     def set_grad_scale(self, scale):
         self.scale = scale
@@ -1188,9 +1100,9 @@ class _DSNPlan:
         for ol in (self.d_bwd, self.g_bwd) + ((self.gp.ops,) if self.gp is not None else ()):
             for o in ol.ops:
                 if o.op == _lib.OP_WGRAD_REDUCE:
-                    o.f[0] = scale
-                elif (o.op == _lib.OP_BNORM_BWD and o.p[3]) or o.op == _lib.OP_BNORM_SECOND:   # dgamma / dbeta of a BatchNorm discriminator
-                    o.f[1] = scale
+                    o.set('scale', scale)
+                elif (o.op == _lib.OP_BNORM_BWD and o.get('dgamma')) or o.op == _lib.OP_BNORM_SECOND:   # dgamma / dbeta of a BatchNorm discriminator
+                    o.set('pscale', scale)
             ol._arr = None
 
 
@@ -1233,40 +1145,23 @@ class _InferPlan:
         else:
             self.lr_nchw = torch.zeros((N, 3, h, w), dtype=torch.float32, device=dev)
             src = BTensor(N, 16, h, w, True, dev)
-            o = _op(_lib.OP_NCHW2B)
-            o.p[0], o.i[0], o.i[1], o.i[2], o.i[3], o.t[0], o.t[1] = self.lr_nchw.data_ptr(), N, 3, h, w, src.view(), NULL_T
-            ops.add(o)
+            ops.add(make_op(_lib.OP_NCHW2B, src=self.lr_nchw.data_ptr(), N=N, C=3, H=h, W=w, dst_f32=src.view()))
             self.src = src
         if wav:
-            o = _op(_lib.OP_DWT_FWD)
-            o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.i[4], o.t[1], o.t[2] = src.view(), N, 3, hd, wd, m.dwt_norm, NULL_T, d.x.view()
+            ops.add(make_op(_lib.OP_DWT_FWD, x=src.view(), N=N, C=3, H2=hd, W2=wd, norm=m.dwt_norm, hc=d.x.view()))
         else:
-            o = _op(_lib.OP_LOWPASS)
-            o.t[0], o.t[1], o.p[0], o.i[4] = src.view(), NULL_T, m.fw.data_ptr(), m.k
-            o.i[0], o.i[1], o.i[2], o.i[3], o.i[5], o.i[6] = N, 3, h, w, 0 | (2 if m.filter == 'avg_pool' else 0), 0
-            o.f[0], o.f[1], o.t[2], o.t[3] = 0.5, 0.5, NULL_T, d.x.view()
-        ops.add(o)
+            ops.add(make_op(_lib.OP_LOWPASS, x=src.view(), w=m.fw.data_ptr(), k=m.k, N=N, C=3, H=h, W=w, mode=0 | (2 if m.filter == 'avg_pool' else 0),
+                            a_h=0.5, b_h=0.5, out_high=d.x.view()))
         ops.extend(d.fwd)
         if m.wgan:   # --wgan (model.py:104-105): the discriminator map is the raw logit map
-            o = _op(_lib.OP_AXPBY)
-            o.t[0], o.f[0], o.t[1], o.f[1] = d.logits.view(), 1.0, NULL_T, 0.0
-            o.i[0], o.i[1], o.i[2], o.i[3] = N, 1, nh, nw
-            o.t[2], o.t[3], o.f[2], o.t[4] = self.dout.view(), NULL_T, 1.0, NULL_T
+            ops.add(make_op(_lib.OP_AXPBY, x=d.logits.view(), a=1.0, N=N, C=1, H=nh, W=nw, out_f32=self.dout.view(), gamma=1.0))
         else:
-            o = _op(_lib.OP_SIGMOID_FWD)
-            o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.t[1] = d.logits.view(), N, 1, nh, nw, self.dout.view()
-        ops.add(o)
-        if m.d_arch == 'fsd':
-            o = _op(_lib.OP_LOWPASS)   # count-normalised box average = spread over the receptive field / coverage count
-            o.t[0], o.t[1], o.p[0], o.i[4] = self.dout.view(), NULL_T, self.box.data_ptr(), DDM_RF
-            o.i[0], o.i[1], o.i[2], o.i[3], o.i[5], o.i[6] = N, 1, hd, wd, 0 | 2, 0
-            o.f[0], o.f[1], o.t[2], o.t[3] = 0.0, 0.0, self.ddm.view(), NULL_T
+            ops.add(make_op(_lib.OP_SIGMOID_FWD, x=d.logits.view(), N=N, C=1, H=nh, W=nw, y=self.dout.view()))
+        if m.d_arch == 'fsd':   # count-normalised box average = spread over the receptive field / coverage count
+            ops.add(make_op(_lib.OP_LOWPASS, x=self.dout.view(), w=self.box.data_ptr(), k=DDM_RF, N=N, C=1, H=hd, W=wd, mode=0 | 2, out_low=self.ddm.view()))
         else:                          # general receptive-field spread (jump / rf / start of the WIDTH walk for both axes, as the reference does)
             n_h = receptive_walk(hd, DDM_CONVNETS[m.d_arch])[0]
             n_w, jump, rf, start = receptive_walk(wd, DDM_CONVNETS[m.d_arch])
             assert (n_h, n_w) == (nh, nw), ((n_h, n_w), (nh, nw))
-            o = _op(_lib.OP_DDM_SPREAD)
-            o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.i[4], o.i[5], o.i[6] = self.dout.view(), N, nh, nw, hd, wd, jump, rf
-            o.f[0], o.t[1] = float(start), self.ddm.view()
-        ops.add(o)
+            ops.add(make_op(_lib.OP_DDM_SPREAD, d=self.dout.view(), N=N, n_h=nh, n_w=nw, H=hd, W=wd, jump=jump, rf=rf, start=float(start), out=self.ddm.view()))
         self.ops = ops

@@ -9,7 +9,7 @@ from collections import OrderedDict
 import torch
 
 from . import _lib
-from ._lib import Tensor, ConvParams, WgradPart, WgradReducePart, PackDesc, Op
+from ._lib import Tensor, ConvParams, WgradPart, WgradReducePart, PackDesc, Op, make_op
 
 SLOPE = 0.2
 
@@ -172,11 +172,8 @@ class PackRegistry:
         return self.buf.data_ptr() + 2 * ref.off
 
     def op(self):
-        o = Op()
-        o.op = _lib.OP_PACK
-        o.p[0], o.i[0], o.l[0] = self.desc_dev.data_ptr(), len(self.descs), self.prefix[-1]
-        o.p[1], o.p[2], o.p[3] = self.prefix_dev.data_ptr(), self.params.flat.data_ptr(), self.buf.data_ptr()
-        return o
+        return make_op(_lib.OP_PACK, descs_dev=self.desc_dev.data_ptr(), ndesc=len(self.descs), total_pieces=self.prefix[-1],
+                       piece_prefix_dev=self.prefix_dev.data_ptr(), params_flat=self.params.flat.data_ptr(), packed=self.buf.data_ptr())
 
     def run(self):
         ops = (Op * 1)(self.op())
@@ -200,25 +197,19 @@ class OpList:
         self._arr = None
 
     def tag(self, bucket, start=0, end=None):
-        """time-bucket tag (Op.i[7], read by no kernel; bench.py's per-bucket table) on the not yet tagged ops [start, end)"""
+        """time-bucket tag (argument 'tag' of every op, read by no kernel; bench.py's per-bucket table) on the not yet tagged ops [start, end)"""
         for o in self.ops[start:end]:
-            if o.i[7] == 0:
-                o.i[7] = bucket
+            if o.get('tag') == 0:
+                o.set('tag', bucket)
         self._arr = None
         return self
 
-    def set_f(self, idx, slot, value):
-        """patch float argument `slot` of op `idx` in place (see set_i)"""
-        self.ops[idx].f[slot] = value
-        if self._arr is not None:
-            self._arr[idx].f[slot] = value
-
-    def set_i(self, idx, slot, value):
-        """patch integer argument `slot` of op `idx` in place (recorded list AND its ctypes image): for the few arguments that change from call to
+    def set(self, idx, name, value):
+        """patch argument `name` of op `idx` in place (recorded list AND its ctypes image): for the few arguments that change from call to
         call while the plan stays recorded (e.g. the random symmetry of DSN --lpips_rot_flip)"""
-        self.ops[idx].i[slot] = value
+        self.ops[idx].set(name, value)
         if self._arr is not None:
-            self._arr[idx].i[slot] = value
+            self._arr[idx].set(name, value)
 
     def safe_cuts(self, chunk):
         """[0, c1, c2, ..., len]: chunk boundaries of about `chunk` ops at which no stream redirect (OP_SET_STREAM) is open"""
@@ -227,7 +218,7 @@ class OpList:
             cuts, redirected, last = [0], False, 0
             for i, o in enumerate(self.ops):
                 if o.op == _lib.OP_SET_STREAM:
-                    redirected = bool(o.p[0])
+                    redirected = bool(o.get('stream'))
                 if i + 1 - last >= chunk and not redirected:
                     cuts.append(i + 1)
                     last = i + 1
@@ -344,12 +335,11 @@ class ConvChain:
         self.flops = sum(o.flops for o in ops)
 
     def op(self):
-        o = Op()
-        o.op = _lib.OP_RDB_CHAIN if self.form == 'is' else _lib.OP_CONV_CHAIN
-        o.p[0], o.p[1], o.p[2], o.p[3] = self.dev.data_ptr(), C.cast(self.host, C.c_void_p).value, self.dep.data_ptr(), self.flags.data_ptr()
-        o.l[0], o.i[0] = self.err.data_ptr(), self.n
-        o.flops = self.flops
-        return o
+        chain = dict(dev_layers=self.dev.data_ptr(), host_layers=C.cast(self.host, C.c_void_p).value, dev_flags=self.flags.data_ptr(),
+                     dev_err=self.err.data_ptr(), nlayers=self.n)
+        if self.form == 'is':
+            return make_op(_lib.OP_RDB_CHAIN, flops=self.flops, **chain)
+        return make_op(_lib.OP_CONV_CHAIN, flops=self.flops, dev_dep_chunk=self.dep.data_ptr(), **chain)
 
     def check(self):
         """host sync: raises if a launch of this chain flagged a broken neighbour wait / XCD placement"""
@@ -446,18 +436,15 @@ class WgradGroup:
 
     def ops(self, grad_ptr, scale=1.0):
         """[wgrad, reduce] ops; the workspace pointer is patched in by Workspace.finalize()."""
-        a, b = Op(), Op()
-        a.op = _lib.OP_WGRAD
-        a.p[0], a.i[0], a.i[1], a.i[2], a.i[3] = self.w_dev.data_ptr(), len(self.parts), self.nsplit, self.kh, self.stride
         f32s = set((p[0].g_f32, p[0].in_f32) for p in self.parts)
         assert f32s in ({(0, 0)}, {(1, 1)}), 'a wgrad group must be all-bf16 or all-f32'
-        a.i[4] = self.parts[0][0].g_f32 | (2 if getattr(self, 'f16', False) else 0)
-        a.flops = float(getattr(self, 'flops', 0.0))
-        b.op = _lib.OP_WGRAD_REDUCE
-        b.p[0], b.i[0], b.p[2], b.f[0] = self.r_dev.data_ptr(), self.n_red, grad_ptr, scale
-        b.i[1] = 1 if (self.tpp <= 16 and all(rp is None or rp.nsplit <= 4 for _, rp, _ in self.parts)) else 0   # few_splits: one reduce workgroup per output channel
+        a = make_op(_lib.OP_WGRAD, flops=float(getattr(self, 'flops', 0.0)), parts_dev=self.w_dev.data_ptr(), nparts=len(self.parts), nsplit=self.nsplit,
+                    kh=self.kh, stride=self.stride, f32=self.parts[0][0].g_f32 | (2 if getattr(self, 'f16', False) else 0))
         gs = getattr(self, 'g_scale', 0.0)
-        b.f[1] = 1.0 / gs if gs else 0.0   # second factor of the reduce scale (f[0] stays the data-parallel 1/world): undoes the f16 pre-scale
+        b = make_op(_lib.OP_WGRAD_REDUCE, parts_dev=self.r_dev.data_ptr(), nparts=self.n_red, grad_flat=grad_ptr, scale=scale,
+                    # few_splits: one reduce workgroup per output channel
+                    few_splits=1 if (self.tpp <= 16 and all(rp is None or rp.nsplit <= 4 for _, rp, _ in self.parts)) else 0,
+                    inv_prescale=1.0 / gs if gs else 0.0)   # undoes the f16 pre-scale (scale stays the data-parallel 1/world)
         self.workspace.register(a, b)
         return [a, b]
 
@@ -521,17 +508,13 @@ class WgradGroup3:
         self.r_dev = torch.frombuffer(bytearray(bytes(ra)), dtype=torch.uint8).to(device)
 
     def ops(self, grad_ptr, scale=1.0):
-        a, b = Op(), Op()
-        a.op = _lib.OP_WGRAD
         f16 = getattr(self, 'f16', False)   # 16-bit f16 tensors (gradient pre-scaled by g_scale): f16 MFMA, reduce scale x 1 / g_scale
-        a.p[0], a.i[0], a.i[1], a.i[2], a.i[3], a.i[4] = (self.w_dev.data_ptr(), len(self.parts), self.nsplit | (getattr(self, 'ppu', 0) << 16), 33, 1,
-                                                          (2 if f16 else self.parts[0][0].g_f32))
-        a.flops = float(getattr(self, 'flops', 0.0))
-        b.op = _lib.OP_WGRAD_REDUCE
-        b.p[0], b.i[0], b.p[2], b.f[0] = self.r_dev.data_ptr(), self.n_red, grad_ptr, scale
-        b.i[1] = 1 if self.nsplit <= 4 else 0   # few_splits (9 taps): one reduce workgroup per output channel
+        a = make_op(_lib.OP_WGRAD, flops=float(getattr(self, 'flops', 0.0)), parts_dev=self.w_dev.data_ptr(), nparts=len(self.parts),
+                    nsplit=self.nsplit | (getattr(self, 'ppu', 0) << 16), kh=33, stride=1, f32=2 if f16 else self.parts[0][0].g_f32)
         gs = getattr(self, 'g_scale', 0.0)
-        b.f[1] = 1.0 / gs if (f16 and gs) else 0.0
+        b = make_op(_lib.OP_WGRAD_REDUCE, parts_dev=self.r_dev.data_ptr(), nparts=self.n_red, grad_flat=grad_ptr, scale=scale,
+                    few_splits=1 if self.nsplit <= 4 else 0,   # (9 taps): one reduce workgroup per output channel
+                    inv_prescale=1.0 / gs if (f16 and gs) else 0.0)
         self.workspace.register(a, b)
         return [a, b]
 
@@ -554,7 +537,7 @@ class Workspace:
     def finalize(self):
         self.buf = torch.zeros(max(self.need, 1), dtype=torch.float32, device=self.device)
         for o in self.pending:
-            o.p[1] = self.buf.data_ptr()
+            o.set('ws', self.buf.data_ptr())
         self.pending = []
 
 

@@ -11,17 +11,11 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .engine import (BTensor, ParamStore, PackRegistry, OpList, WgradGroup, Workspace, conv_op, ceil_div, NULL_T)
-from ._lib import Op, Tensor
+from .engine import (BTensor, ParamStore, PackRegistry, OpList, WgradGroup, Workspace, conv_op, ceil_div)
+from ._lib import Tensor, make_op
 
 SLOPE = 0.2
 IN_EPS = 1e-5
-
-
-def _op(kind):
-    o = Op()
-    o.op = kind
-    return o
 
 
 def nlayer_d_spec(input_nc, ndf=64, n_layers=2):
@@ -320,15 +314,11 @@ class _DPlan:
                 ops.add(conv_op(pack, L['fwd'], src.view(), True, L['cin_pad'], hi, wi, ho, wo, N, bias=bias, kh=L['kh'], stride=L['stride'],
                                 pad=L['pad'], out_f32=self.zs[i].view()))
                 if L['norm'] == 'batch':
-                    o = _op(_lib.OP_BNORM_FWD)
-                    o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.i[4] = self.zs[i].view(), N, L['cout'], ho, wo, self.group
-                    o.f[0], o.f[1], o.p[0], o.p[1], o.t[1], o.p[2] = BN_EPS, SLOPE, P.ptr(L['bn'] + 'weight'), P.ptr(L['bn'] + 'bias'), self.acts[i].view(), \
-                        self.stats[i].data_ptr()
+                    ops.add(make_op(_lib.OP_BNORM_FWD, x=self.zs[i].view(), N=N, C=L['cout'], H=ho, W=wo, group=self.group, eps=BN_EPS, slope=SLOPE,
+                                    gamma=P.ptr(L['bn'] + 'weight'), beta=P.ptr(L['bn'] + 'bias'), y=self.acts[i].view(), stats=self.stats[i].data_ptr()))
                 else:
-                    o = _op(_lib.OP_INORM_FWD)
-                    o.t[0], o.i[0], o.i[1], o.i[2], o.i[3] = self.zs[i].view(), N, L['cout'], ho, wo
-                    o.f[0], o.f[1], o.t[1], o.p[0] = IN_EPS, SLOPE, self.acts[i].view(), self.stats[i].data_ptr()
-                ops.add(o)
+                    ops.add(make_op(_lib.OP_INORM_FWD, x=self.zs[i].view(), N=N, C=L['cout'], H=ho, W=wo, eps=IN_EPS, slope=SLOPE, y=self.acts[i].view(),
+                                    stats=self.stats[i].data_ptr()))
             else:
                 ops.add(conv_op(pack, L['fwd'], src.view(), True, L['cin_pad'], hi, wi, ho, wo, N, bias=bias, kh=L['kh'], stride=L['stride'],
                                 pad=L['pad'], act=0 if L.get('last') else 1, slope=SLOPE, out_f32=self.acts[i].view()))
@@ -363,27 +353,20 @@ class _DPlan:
             (hi, wi), (ho, wo) = self.dims[i], self.dims[i + 1]
             gz = self.gz[i]
             if L['norm'] == 'batch':  # dL/da -> dL/dz through BatchNorm (per-half statistics) + LeakyReLU; dgamma / dbeta in the discriminator step
-                o = _op(_lib.OP_BNORM_BWD)
-                o.t[0], o.t[1], o.i[0], o.i[1], o.i[2], o.i[3], o.i[4] = self.zs[i].view(), self.ga[i].view(), N, L['cout'], ho, wo, self.group
-                o.f[0], o.p[0], o.p[1], o.p[2], o.t[2] = SLOPE, P.ptr(L['bn'] + 'weight'), P.ptr(L['bn'] + 'bias'), self.stats[i].data_ptr(), gz.view()
-                o.p[3] = P.ptr(L['bn'] + 'weight', P.grad) if wgrad else None
-                o.l[0] = P.ptr(L['bn'] + 'bias', P.grad) if wgrad else 0
-                o.f[1] = 1.0
-                ops.add(o)
+                ops.add(make_op(_lib.OP_BNORM_BWD, x=self.zs[i].view(), ga=self.ga[i].view(), N=N, C=L['cout'], H=ho, W=wo, group=self.group, slope=SLOPE,
+                                gamma=P.ptr(L['bn'] + 'weight'), beta=P.ptr(L['bn'] + 'bias'), stats=self.stats[i].data_ptr(), gx=gz.view(),
+                                dgamma=P.ptr(L['bn'] + 'weight', P.grad) if wgrad else None, dbeta=P.ptr(L['bn'] + 'bias', P.grad) if wgrad else None,
+                                pscale=1.0))
             elif L['norm']:  # dL/da -> dL/dz through InstanceNorm + LeakyReLU
-                o = _op(_lib.OP_INORM_BWD)
-                o.t[0], o.t[1], o.i[0], o.i[1], o.i[2], o.i[3] = self.acts[i].view(), self.ga[i].view(), N, L['cout'], ho, wo
-                o.f[0], o.p[0], o.t[2] = SLOPE, self.stats[i].data_ptr(), gz.view()
-                ops.add(o)
+                ops.add(make_op(_lib.OP_INORM_BWD, a=self.acts[i].view(), ga=self.ga[i].view(), N=N, C=L['cout'], H=ho, W=wo, slope=SLOPE,
+                                stats=self.stats[i].data_ptr(), gx=gz.view()))
             inp = self.x if i == 0 else self.acts[i - 1]
             if wgrad:
                 split = None
                 if getattr(net, 'split_wgrad', False) and net.prec == 4:
                     g_lo, x_lo = BTensor(N, gz.C, gz.H, gz.W, True, net.device), BTensor(N, inp.C, inp.H, inp.W, True, net.device)
                     for src, dst, sc in ((gz, g_lo, 4096.0), (inp, x_lo, 1.0)):
-                        o = _op(_lib.OP_CVT_F16)
-                        o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.f[0], o.t[1], o.i[4] = src.view(), N, src.C, src.H, src.W, sc, dst.view(), 3
-                        ops.add(o)
+                        ops.add(make_op(_lib.OP_CVT_F16, x=src.view(), N=N, C=src.C, H=src.H, W=src.W, scale=sc, y=dst.view(), form=3))
                     ops.keep += [g_lo, x_lo]
                     split = (g_lo.view, x_lo.view)
                 grp = WgradGroup(L['kh'], L['stride'])
@@ -413,10 +396,9 @@ class _DPlan:
             if L['norm'] == 'batch':
                 ho, wo = self.dims[i + 1]
                 B = self.net.buffers
-                o = _op(_lib.OP_BNORM_RUNNING)
-                o.p[0], o.i[0], o.i[1], o.i[2], o.f[0] = self.stats[i].data_ptr(), g, L['cout'], self.group * ho * wo, BN_MOMENTUM
-                o.p[1], o.p[2], o.p[3] = B[L['bn'] + 'running_mean'].data_ptr(), B[L['bn'] + 'running_var'].data_ptr(), B[L['bn'] + 'num_batches_tracked'].data_ptr()
-                ops.add(o)
+                ops.add(make_op(_lib.OP_BNORM_RUNNING, stats=self.stats[i].data_ptr(), g=g, C=L['cout'], count=self.group * ho * wo, momentum=BN_MOMENTUM,
+                                running_mean=B[L['bn'] + 'running_mean'].data_ptr(), running_var=B[L['bn'] + 'running_var'].data_ptr(),
+                                num_batches_tracked=B[L['bn'] + 'num_batches_tracked'].data_ptr()))
         return ops
 
     def bwd_data_ops(self, n):
@@ -562,10 +544,8 @@ class _VGGPlan:
             else:
                 h, w = h // 2, w // 2
                 out = BTensor(N, cout, h, w, True, dev)
-                o = _op(_lib.OP_MAXPOOL)
-                o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.i[4], o.t[1] = src.view(), N, cout, h, w, 1, out.view()
-                o.i[6] = src.W   # input width (odd widths: the last column is dropped)
-                fwd.add(o)
+                # Win: input width (odd widths: the last column is dropped)
+                fwd.add(make_op(_lib.OP_MAXPOOL, x=src.view(), N=N, C=cout, Ho=h, Wo=w, is_f32=1, y=out.view(), Win=src.W))
             self.outs.append(out)
             src = out
         self.feat = src
@@ -592,24 +572,16 @@ class _VGGPlan:
                 bwd.add(conv_op(pack, net.pk[(idx, 'b')], g.view(), True, cout, inp.H, inp.W, inp.H, inp.W, n,
                                 mask=inp.view() if prev_relu else None, mask_f32=1, slope=0.0, out_f32=gin.view(), in_scale=gsc))
             else:
-                o = _op(_lib.OP_MAXPOOL_BWD)
-                o.t[0], o.t[1], o.i[0], o.i[1], o.i[2], o.i[3], o.i[4], o.i[5], o.t[2] = inp.view(), g.view(), n, cout, g.H, g.W, 1, 1, gin.view()
-                o.i[6] = inp.W
-                bwd.add(o)
+                bwd.add(make_op(_lib.OP_MAXPOOL_BWD, x=inp.view(), gy=g.view(), N=n, C=cout, Ho=g.H, Wo=g.W, is_f32=1, relu_mask=1, gx=gin.view(), Win=inp.W))
             g = gin
         self.bwd = bwd.tag(8)
 
     def input_copy_op(self, src_view, n0, n, H, W):
         """op that writes `n` images of a blocked f32 tensor (<= 16 channels) into x[n0 : n0 + n] (DSN: no input normalisation)"""
         dst = Tensor(self.x.view().p + n0 * self.x.view().n_stride * self.x.esz, self.x.view().n_stride, self.x.view().cb_stride)
-        o = _op(_lib.OP_CVT_F16 if (self.net.f16s or self.net.split) else _lib.OP_AXPBY)
         if self.net.f16s or self.net.split:
-            o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.f[0], o.t[1], o.i[4] = src_view, n, 16, H, W, 1.0, dst, int(self.net.split)
-        else:
-            o.t[0], o.f[0], o.t[1], o.f[1] = src_view, 1.0, NULL_T, 0.0
-            o.i[0], o.i[1], o.i[2], o.i[3] = n, 16, H, W
-            o.t[2], o.t[3], o.f[2], o.t[4] = dst, NULL_T, 1.0, NULL_T
-        return o
+            return make_op(_lib.OP_CVT_F16, x=src_view, N=n, C=16, H=H, W=W, scale=1.0, y=dst, form=int(self.net.split))
+        return make_op(_lib.OP_AXPBY, x=src_view, a=1.0, N=n, C=16, H=H, W=W, out_f32=dst, gamma=1.0)
 
     def _init_split(self, N, n_g, H, W):
         """split-f16 storage (prec 5): every activation up to the last conv and every gradient below it is a SPLIT tensor -- K planes of f16 `hi`
@@ -648,14 +620,12 @@ class _VGGPlan:
                     fwd.add(conv_op(pack, net.pk[(idx, 'r')], _nview_t(src, n_g), False, c16(cin), h, w, h, w, N - n_g, bias=bias,
                                     act=1 if relu else 0, slope=0.0, out_f32=_nview_t(out, n_g) if last else None,
                                     out_bf16=None if last else _nview_t(out, n_g), out16_f16=0 if last else 1))
-                    fwd.ops[-1].i[7] = 7
+                    fwd.ops[-1].set('tag', 7)
             else:
                 h, w = h // 2, w // 2
                 out = Bf(cout, h, w) if li > lc else Bs(cout, h, w)
-                o = _op(_lib.OP_MAXPOOL)
-                o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.i[4], o.t[1] = src.view(), N, cout, h, w, (1 if li > lc else 3), out.view()
-                o.i[6] = src.W   # input width (odd widths: the last column is dropped)
-                fwd.add(o)
+                # Win: input width (odd widths: the last column is dropped)
+                fwd.add(make_op(_lib.OP_MAXPOOL, x=src.view(), N=N, C=cout, Ho=h, Wo=w, is_f32=1 if li > lc else 3, y=out.view(), Win=src.W))
             self.outs.append(out)
             src = out
         self.feat = src
@@ -676,9 +646,7 @@ class _VGGPlan:
             if kind == 'conv':
                 if li == lc:   # f32 gradient of the last conv's output -> pre-scaled split (or plain f16) tensor
                     gs = Bg(cout, g.H, g.W)
-                    o = _op(_lib.OP_CVT_F16)
-                    o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.f[0], o.t[1], o.i[4] = g.view(), n, cout, g.H, g.W, self.gscale, gs.view(), int(gsplit)
-                    bwd.add(o)
+                    bwd.add(make_op(_lib.OP_CVT_F16, x=g.view(), N=n, C=cout, H=g.H, W=g.W, scale=self.gscale, y=gs.view(), form=int(gsplit)))
                     g = gs
                 prev_relu = li > 0 and net.layers[li - 1][0] == 'conv' and net.layers[li - 1][4]
                 kg = c16(cout) // 16
@@ -696,10 +664,8 @@ class _VGGPlan:
             else:
                 f32 = li > lc
                 gin = Bf(cout, inp.H, inp.W) if f32 else Bg(cout, inp.H, inp.W)
-                o = _op(_lib.OP_MAXPOOL_BWD)
-                o.t[0], o.t[1], o.i[0], o.i[1], o.i[2], o.i[3], o.i[4], o.i[5], o.t[2] = inp.view(), g.view(), n, cout, g.H, g.W, (1 if f32 else (3 if gsplit else 5)), 1, gin.view()
-                o.i[6] = inp.W
-                bwd.add(o)
+                bwd.add(make_op(_lib.OP_MAXPOOL_BWD, x=inp.view(), gy=g.view(), N=n, C=cout, Ho=g.H, Wo=g.W, is_f32=1 if f32 else (3 if gsplit else 5),
+                                relu_mask=1, gx=gin.view(), Win=inp.W))
             g = gin
         self.bwd = bwd.tag(8)
 
@@ -732,10 +698,8 @@ class _VGGPlan:
             else:
                 h, w = h // 2, w // 2
                 out = Bf(cout, h, w) if li > lc else Bh(cout, h, w)
-                o = _op(_lib.OP_MAXPOOL)
-                o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.i[4], o.t[1] = src.view(), N, cout, h, w, (1 if li > lc else 2), out.view()
-                o.i[6] = src.W   # input width (odd widths: the last column is dropped)
-                fwd.add(o)
+                # Win: input width (odd widths: the last column is dropped)
+                fwd.add(make_op(_lib.OP_MAXPOOL, x=src.view(), N=N, C=cout, Ho=h, Wo=w, is_f32=1 if li > lc else 2, y=out.view(), Win=src.W))
             self.outs.append(out)
             src = out
         self.feat = src
@@ -754,9 +718,7 @@ class _VGGPlan:
             if kind == 'conv':
                 if li == lc:   # f32 gradient of the last conv's output -> pre-scaled f16
                     g16 = Bh(g.C, g.H, g.W)
-                    o = _op(_lib.OP_CVT_F16)
-                    o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.f[0], o.t[1] = g.view(), n, g.C, g.H, g.W, self.gscale, g16.view()
-                    bwd.add(o)
+                    bwd.add(make_op(_lib.OP_CVT_F16, x=g.view(), N=n, C=g.C, H=g.H, W=g.W, scale=self.gscale, y=g16.view()))
                     g = g16
                 prev_relu = li > 0 and net.layers[li - 1][0] == 'conv' and net.layers[li - 1][4]
                 if li == 0:   # dL/d(normalised input): f32, un-scaled
@@ -769,9 +731,7 @@ class _VGGPlan:
             else:
                 f32 = li > lc
                 gin = Bf(inp.C, inp.H, inp.W) if f32 else Bh(inp.C, inp.H, inp.W)
-                o = _op(_lib.OP_MAXPOOL_BWD)
-                o.t[0], o.t[1], o.i[0], o.i[1], o.i[2], o.i[3], o.i[4], o.i[5], o.t[2] = inp.view(), g.view(), n, cout, g.H, g.W, (1 if f32 else 2), 1, gin.view()
-                o.i[6] = inp.W
-                bwd.add(o)
+                bwd.add(make_op(_lib.OP_MAXPOOL_BWD, x=inp.view(), gy=g.view(), N=n, C=cout, Ho=g.H, Wo=g.W, is_f32=1 if f32 else 2, relu_mask=1, gx=gin.view(),
+                                Win=inp.W))
             g = gin
         self.bwd = bwd.tag(8)

@@ -16,7 +16,6 @@ forward + backward, against ~610 for the VGG19-54 feature loss: with LPIPS the c
 Weights: `load_state_dict` takes torchvision's alexnet keys (`features.{0,3,6,8,10}.{weight,bias}`) and the reference's linear heads
 (`lin{0..4}.model.1.weight`, codes/PerceptualSimilarity/models/weights/v0.1/alex.pth).  Neither can be downloaded here: without files the
 caller seeds them (`lpips_random_state_dict`) and says so in the log."""
-import ctypes as C
 import logging
 import math
 from collections import OrderedDict
@@ -24,8 +23,8 @@ from collections import OrderedDict
 import torch
 
 from . import _lib
-from .engine import BTensor, ParamStore, PackRegistry, OpList, conv_op, ceil_div, NULL_T
-from ._lib import Op, Tensor
+from .engine import BTensor, ParamStore, PackRegistry, OpList, conv_op, ceil_div
+from ._lib import Tensor, make_op
 
 SHIFT = (-.030, -.088, -.188)     # ScalingLayer, networks_basic.py:94-101
 SCALE = (.458, .448, .450)
@@ -35,12 +34,6 @@ PREC = 4                          # split-f16 conv operands (f16 hi + lo pairs, 
 #          key           cout cin  k  pad  followed by a MaxPool2d(3, 2)
 CONVS = (('features.0', 64, 3, 11, 2, True), ('features.3', 192, 64, 5, 2, True), ('features.6', 384, 192, 3, 1, False),
          ('features.8', 256, 384, 3, 1, False), ('features.10', 256, 256, 3, 1, False))
-
-
-def _op(kind):
-    o = Op()
-    o.op = kind
-    return o
 
 
 def lpips_keys():
@@ -189,12 +182,8 @@ class LPIPSAlexHIP:
             nchw = torch.zeros((2 * n, 3, H, W), dtype=torch.float32, device=self.device)
             acc = torch.zeros(1, dtype=torch.float32, device=self.device)
             ops = OpList()
-            o = _op(_lib.OP_FILL)
-            o.p[0], o.l[0], o.f[0] = acc.data_ptr(), 1, 0.0
-            ops.add(o)
-            o = _op(_lib.OP_NCHW2B)
-            o.p[0], o.i[0], o.i[1], o.i[2], o.i[3], o.t[0], o.t[1] = nchw.data_ptr(), 2 * n, 3, H, W, img.view(), NULL_T
-            ops.add(o)
+            ops.add(make_op(_lib.OP_FILL, p=acc.data_ptr(), n=1, value=0.0))
+            ops.add(make_op(_lib.OP_NCHW2B, src=nchw.data_ptr(), N=2 * n, C=3, H=H, W=W, dst_f32=img.view()))
             ops.add(p.input_op(img.view(), 0, 2 * n))
             ops.extend(p.fwd)
             for o in p.head_ops(acc.data_ptr(), 0.0):
@@ -236,9 +225,7 @@ class _LPIPSPlan:
             if pool:
                 hp, wp = (h - 3) // 2 + 1, (w - 3) // 2 + 1
                 pl = BTensor(N, cout, hp, wp, True, dev)
-                o = _op(_lib.OP_MAXPOOL3)
-                o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.t[1] = src.view(), N, cout, h, w, pl.view()
-                fwd.add(o)
+                fwd.add(make_op(_lib.OP_MAXPOOL3, x=src.view(), N=N, C=cout, H=h, W=w, y=pl.view()))
                 self.pool.append(pl)
                 src, h, w = pl, hp, wp
             else:
@@ -258,10 +245,8 @@ class _LPIPSPlan:
                 pl = self.pool[li - 1]
                 gp = BTensor(n, pl.C, pl.H, pl.W, True, dev)
                 bwd.add(conv_op(pack, net.pk[(key, 'b')], g.view(), True, cout, pl.H, pl.W, pl.H, pl.W, n, kh=k, pad=pad, out_f32=gp.view(), in_scale=gsc))
-                o = _op(_lib.OP_MAXPOOL3_BWD)
-                o.t[0], o.t[1], o.i[0], o.i[1], o.i[2], o.i[3], o.t[2], o.i[4], o.i[5] = below.view(), gp.view(), n, below.C, below.H, below.W, \
-                    self.ghead[li - 1].view(), 1, 1
-                bwd.add(o)
+                bwd.add(make_op(_lib.OP_MAXPOOL3_BWD, x=below.view(), gy=gp.view(), N=n, C=below.C, H=below.H, W=below.W, gx=self.ghead[li - 1].view(),
+                                relu_mask=1, accumulate=1))
                 bwd.keep.append(gp)
                 g = self.ghead[li - 1]
             else:                                           # relu -> conv: ReLU' mask in the epilogue, head gradient added behind it
@@ -278,12 +263,7 @@ class _LPIPSPlan:
         self._sh = [-(1.0 + sh) / s for sh, s in zip(SHIFT, SCALE)] + [0.0]
 
     def _s2d(self, img_view, n_imgs, y_view, mode):
-        o = _op(_lib.OP_LPIPS_S2D)
-        o.t[0], o.i[0], o.i[1], o.i[2], o.t[1], o.i[3] = img_view, n_imgs, self.H, self.W, y_view, mode
-        for j in range(4):
-            o.f[j] = self._sc[j]
-        C.memmove(C.addressof(o.l), (C.c_float * 4)(*self._sh), 16)
-        return o
+        return make_op(_lib.OP_LPIPS_S2D, x=img_view, N=n_imgs, H=self.H, W=self.W, y=y_view, mode=mode, scale4=self._sc, shift4=self._sh)
 
     def input_op(self, img_view, n0, n_imgs):
         """blocked f32 image (3 channels in plane 0, values in [0,1]) -> scaled space-to-depth input of images [n0, n0 + n_imgs)"""
@@ -299,9 +279,7 @@ class _LPIPSPlan:
         ops = []
         P = self.net.params
         for i, r in enumerate(self.relu):
-            o = _op(_lib.OP_LPIPS_HEAD)
             cnt = float(self.n * r.H * r.W)
-            o.t[0], o.l[0], o.i[0], o.i[1], o.i[2], o.i[3] = r.view(), self.n, self.n, r.C, r.H, r.W
-            o.p[0], o.f[0], o.f[1], o.f[2], o.p[1], o.t[1], o.i[4] = P.ptr('lin%d' % i), EPS, 1.0 / cnt, float(weight) / cnt, loss_ptr, self.ghead[i].view(), 1
-            ops.append(o)
+            ops.append(make_op(_lib.OP_LPIPS_HEAD, f=r.view(), pair_off=self.n, N=self.n, C=r.C, H=r.H, W=r.W, lin=P.ptr('lin%d' % i), eps=EPS,
+                               coef=1.0 / cnt, gcoef=float(weight) / cnt, loss_acc=loss_ptr, g0=self.ghead[i].view(), relu_mask=1))
         return ops

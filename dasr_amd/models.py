@@ -15,7 +15,8 @@ from collections import Counter, OrderedDict
 import torch
 
 from . import _lib
-from .engine import Op, OpList, NULL_T, ensure_runtime_ready, _stream, run_parallel
+from ._lib import make_op
+from .engine import OpList, ensure_runtime_ready, _stream, run_parallel
 from .init import kaiming_state_dict
 from .rrdbnet import RRDBNetHIP, rrdbnet_param_spec
 
@@ -264,17 +265,11 @@ class SRModel(BaseModel):
             N, C_, H, W = plan.N, self.real_H.shape[1], self.real_H.shape[2], self.real_H.shape[3]
             hr_buf = torch.zeros((N, C_, H, W), dtype=torch.float32, device=self.device)
             ops = OpList()
-            o = Op()
-            o.op = _lib.OP_L1LOSS
-            o.t[0], o.p[0], o.p[1] = plan.sr.view(), hr_buf.data_ptr(), None
-            o.i[0], o.i[1], o.i[2], o.i[3], o.i[4] = N, C_, H, W, (2 if self.pix_l2 else 0)
-            o.f[0] = float(self.l_pix_w) / float(n_total * C_ * H * W)
-            o.p[2], o.t[1] = self.loss_acc.data_ptr() + 4 * (plan.replica % 8), plan.g_sr.view()
             fused = plan.take_f16_loss_gradient()   # (f16 HR tail: dL/dSR goes straight into its f16 input, pre-scaled; no fp32 image, no conversion pass)
-            if fused is not None:
-                o.t[1], o.f[1] = fused
-                o.i[4] |= 4
-            ops.add(o)
+            grad, grad_scale = fused if fused is not None else (plan.g_sr.view(), 0.0)
+            ops.add(make_op(_lib.OP_L1LOSS, sr=plan.sr.view(), hr_nchw=hr_buf.data_ptr(), N=N, C=C_, H=H, W=W,
+                            accumulate=(2 if self.pix_l2 else 0) | (4 if fused is not None else 0), coef=float(self.l_pix_w) / float(n_total * C_ * H * W),
+                            loss_acc=self.loss_acc.data_ptr() + 4 * (plan.replica % 8), grad=grad, grad_scale=grad_scale))
             self._step_ops[key] = (ops, hr_buf)
         return self._step_ops[key]
 
@@ -303,7 +298,6 @@ class SRModel(BaseModel):
         """forward + loss + backward of one sub-batch replica as ONE recorded list; an event is recorded on the replica's stream at
         every gradient-bucket boundary of the backward list (plan.buckets: [(event, lo, hi)] in completion order)"""
         if not hasattr(plan, 'whole_step'):
-            from .rrdbnet import _sched
             ws = OpList()
             ws.extend(plan.fwd)
             ws.extend(loss_ops)
@@ -311,7 +305,7 @@ class SRModel(BaseModel):
             for idx, lo, hi in plan._marks:
                 ws.ops.extend(plan.bwd.ops[prev:idx])
                 ev = plan._event()
-                ws.ops.append(_sched(_lib.OP_EVENT_RECORD, ev))
+                ws.ops.append(make_op(_lib.OP_EVENT_RECORD, event=ev))
                 plan.buckets.append((ev, lo, hi))
                 prev = idx
             ws.ops.extend(plan.bwd.ops[prev:])
@@ -326,19 +320,15 @@ class SRModel(BaseModel):
         gradient slices of replicas 1.. into params.grad[lo:hi]"""
         key = tuple((id(p), p.whole_step_gen) for p in plans)
         if getattr(self, '_bucket_key', None) != key:
-            from .rrdbnet import _sched
             g, out = self.netG.params.grad, []
             for k in range(len(plans[0].buckets)):
                 _, lo, hi = plans[0].buckets[k]
                 ol = OpList()
                 for p in plans:
-                    ol.add(_sched(_lib.OP_STREAM_WAIT, p.buckets[k][0]))
+                    ol.add(make_op(_lib.OP_STREAM_WAIT, event=p.buckets[k][0]))
                 for p in plans[1:]:
-                    o = Op()
-                    o.op = _lib.OP_ADD_FLAT
-                    o.p[0], o.p[1], o.l[0] = g.data_ptr() + 4 * lo, p.grad.data_ptr() + 4 * lo, hi - lo
                     if hi > lo:
-                        ol.add(o)
+                        ol.add(make_op(_lib.OP_ADD_FLAT, y=g.data_ptr() + 4 * lo, x=p.grad.data_ptr() + 4 * lo, n=hi - lo))
                 out.append((ol, lo, hi))
             self._bucket_list, self._bucket_key = out, key
         return self._bucket_list

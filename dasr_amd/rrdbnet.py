@@ -12,8 +12,8 @@ from collections import OrderedDict
 import torch
 
 from . import _lib
-from .engine import (BTensor, ParamStore, PackRegistry, OpList, WgradGroup, WgradGroup3, Workspace, conv_op, ceil_div, SLOPE, NULL_T, ConvChain)
-from ._lib import Op, Tensor
+from .engine import (BTensor, ParamStore, PackRegistry, OpList, WgradGroup, WgradGroup3, Workspace, conv_op, ceil_div, SLOPE, ConvChain)
+from ._lib import Op, Tensor, make_op
 
 GC = 32  # growth channels are hard-wired to 32 in the reference (architecture.py:183)
 
@@ -291,13 +291,6 @@ class RRDBNetHIP:
         return p.read_output()
 
 
-def _sched(kind, handle):
-    o = Op()
-    o.op = kind
-    o.p[0] = handle
-    return o
-
-
 def _sub_batch_conv(o, n0, n, N):
     """copy of a dense-block conv Op restricted to images [n0, n0 + n) of its N: every tensor view moves by n0 images (the chained launches of a batch that is a
     multiple of the 512-tile fit run one sub-batch after the other, RRDBNetHIP.chain_split)"""
@@ -447,7 +440,7 @@ class TrunkStore:
                 o.conv.alpha = 1.0 / s
         for o in self.phase.ops:
             if o.op == _lib.OP_WGRAD_REDUCE:
-                o.f[1] = 1.0 / s
+                o.set('inv_prescale', 1.0 / s)
         self.phase._arr = None
         for pl in self._plans:   # every recorded list that holds copies of the patched ops
             pl.bwd._arr = None
@@ -459,8 +452,8 @@ class TrunkStore:
     def set_grad_scale(self, scale):
         changed = False
         for o in self.phase.ops:
-            if o.op == _lib.OP_WGRAD_REDUCE and o.f[0] != scale:
-                o.f[0] = scale
+            if o.op == _lib.OP_WGRAD_REDUCE and o.get('scale') != scale:
+                o.set('scale', scale)
                 changed = True
         if changed:
             self.phase._arr = None
@@ -541,7 +534,7 @@ class _Plan:
         if self.g_sr16 is None or getattr(self, '_loss16_taken', False) or hasattr(self, 'whole_step'):
             return None
         o = self.bwd.ops[0]
-        assert o.op == _lib.OP_CVT_F16 and o.t[1].p == self.g_sr16.view().p
+        assert o.op == _lib.OP_CVT_F16 and o.get('y').p == self.g_sr16.view().p
         del self.bwd.ops[0]
         self.bwd._arr = None
         self.tail_end -= 1
@@ -585,11 +578,7 @@ class _Plan:
         nf, nb, P, pack, pk = net.nf, net.nb, net.params, net.pack, net.pk
         H2, W2, H4, W4 = 2 * h, 2 * w, 4 * h, 4 * w
         ops = OpList()
-        o = Op()
-        o.op = _lib.OP_NCHW2B
-        o.p[0], o.i[0], o.i[1], o.i[2], o.i[3] = self.x_nchw.data_ptr(), N, net.in_nc, h, w
-        o.t[0], o.t[1] = self.x_in.view(), NULL_T
-        ops.add(o)
+        ops.add(make_op(_lib.OP_NCHW2B, src=self.x_nchw.data_ptr(), N=N, C=net.in_nc, H=h, W=w, dst_f32=self.x_in.view()))
         # fea_conv: fp32 stream + bf16 shadow into the first dense slab
         f16 = int(net.rdb_f16)   # dense slabs in f16 storage: every 16-bit output of the trunk is f16
         ops.add(conv_op(pack, pk['fea'], self.x_in.view(), True, 16, h, w, h, w, N, bias=P.ptr('model.0.bias'),
@@ -636,12 +625,7 @@ class _Plan:
             if i in getattr(net, 'debug_taps', ()):   # tests: fp32 copy of this RRDB's output (the stream buffers rotate)
                 self.taps = getattr(self, 'taps', {})
                 self.taps[i] = BTensor(N, nf, h, w, True, net.device)
-                o = Op()
-                o.op = _lib.OP_AXPBY
-                o.t[0], o.f[0], o.t[1], o.f[1] = X.view(), 1.0, NULL_T, 0.0
-                o.i[0], o.i[1], o.i[2], o.i[3] = N, nf, h, w
-                o.t[2], o.t[3], o.f[2] = self.taps[i].view(), NULL_T, 1.0
-                ops.add(o)
+                ops.add(make_op(_lib.OP_AXPBY, x=X.view(), a=1.0, N=N, C=nf, H=h, W=w, out_f32=self.taps[i].view(), gamma=1.0))
         ops = main_ops
         self.chain = None
         if chain is not None:
@@ -683,20 +667,14 @@ class _Plan:
             if net.ps:   # pixelshuffle_block (block.py:838-851): conv nf -> 4 nf, PixelShuffle(2), LeakyReLU (applied before the shuffle: it is elementwise)
                 for name, bkey, src, pre, dst, hi, wi in (('up1', 'model.2.bias', self.t0h, self.ps1, self.u1, h, w), ('up2', 'model.5.bias', self.u1, self.ps2, self.u2, H2, W2)):
                     ops.add(conv_op(pack, pk[name], src.view(), False, nf, hi, wi, hi, wi, N, bias=P.ptr(bkey), act=1, slope=sl, out_bf16=pre.view(), out16_f16=1))
-                    o = Op()
-                    o.op = _lib.OP_PIXSHUF
-                    o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.t[1] = pre.view(), N, 4 * nf, hi, wi, dst.view()
-                    ops.add(o)
+                    ops.add(make_op(_lib.OP_PIXSHUF, src=pre.view(), N=N, C4=4 * nf, H=hi, W=wi, dst=dst.view()))
             for name, bkey, src, dst, hi, wi in (() if net.ps else (('up1', 'model.3.bias', self.t0h, self.u1, h, w), ('up2', 'model.6.bias', self.u1, self.u2, H2, W2))):
                 ops.add(conv_op(pack, pk[name], src.view(), False, nf, hi, wi, 2 * hi, 2 * wi, N, bias=P.ptr(bkey), ups=1, act=1, out_bf16=dst.view(),
                                 out16_f16=1))
             ops.add(conv_op(pack, pk['hr0'], self.u2.view(), False, nf, H4, W4, H4, W4, N, bias=P.ptr('model.8.bias'), act=1, slope=sl, out_bf16=self.h0.view(),
                             out16_f16=1))
             ops.add(conv_op(pack, pk['hr1'], self.h0.view(), False, nf, H4, W4, H4, W4, N, bias=P.ptr('model.10.bias'), out_f32=self.sr.view()))
-            o = Op()
-            o.op = _lib.OP_B2NCHW
-            o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.p[0] = self.sr.view(), N, net.out_nc, H4, W4, self.sr_nchw.data_ptr()
-            self._add_output_op(ops, o)
+            self._add_output_op(ops, make_op(_lib.OP_B2NCHW, src=self.sr.view(), N=N, C=net.out_nc, H=H4, W=W4, dst=self.sr_nchw.data_ptr()))
             self.fwd = ops.tag(2)
             return
         ops.add(conv_op(pack, pk['lr'], X.view(), True, nf, h, w, h, w, N, bias=P.ptr(lrb), res1=self.fea.view(), beta1=1.0,
@@ -715,10 +693,7 @@ class _Plan:
                         out_f32=self.h0.view()))
         ops.add(conv_op(pack, pk['hr1'], self.h0.view(), True, nf, H4, W4, H4, W4, N, bias=P.ptr('model.10.bias'),
                         out_f32=self.sr.view()))
-        o = Op()
-        o.op = _lib.OP_B2NCHW
-        o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.p[0] = self.sr.view(), N, net.out_nc, H4, W4, self.sr_nchw.data_ptr()
-        self._add_output_op(ops, o)
+        self._add_output_op(ops, make_op(_lib.OP_B2NCHW, src=self.sr.view(), N=N, C=net.out_nc, H=H4, W=W4, dst=self.sr_nchw.data_ptr()))
         self.fwd = ops.tag(2)
 
     # ---- backward (input: self.g_sr filled by a loss kernel) -----------------------------------------------
@@ -809,17 +784,10 @@ class _Plan:
         sl = net.act_slope
 
         def downsum(src, hl, wl, mask, dst_f32, dst_f16, out_scale):
-            o = Op()
-            o.op = _lib.OP_DOWNSUM_F16
-            o.t[0], o.i[0], o.i[1], o.i[2], o.i[3] = src.view(), N, nf, hl, wl
-            o.t[1], o.f[0], o.f[1] = (mask.view() if mask is not None else NULL_T), sl, out_scale
-            o.t[2], o.t[3] = (dst_f32.view() if dst_f32 is not None else NULL_T), (dst_f16.view() if dst_f16 is not None else NULL_T)
-            ops.add(o)
+            ops.add(make_op(_lib.OP_DOWNSUM_F16, src=src.view(), N=N, C=nf, H=hl, W=wl, mask=mask and mask.view(), slope=sl, out_scale=out_scale,
+                            dst_f32=dst_f32 and dst_f32.view(), dst_f16=dst_f16 and dst_f16.view()))
 
-        o = Op()
-        o.op = _lib.OP_CVT_F16
-        o.t[0], o.i[0], o.i[1], o.i[2], o.i[3], o.f[0], o.t[1] = self.g_sr.view(), N, net.out_nc, H4, W4, gs, self.g_sr16.view()
-        ops.add(o)
+        ops.add(make_op(_lib.OP_CVT_F16, x=self.g_sr.view(), N=N, C=net.out_nc, H=H4, W=W4, scale=gs, y=self.g_sr16.view()))
         # HR_conv1
         self._wg3(ops, 'model.10.', self.g_sr16, self.h0, net.out_nc, nf, H4, W4, H4, W4)
         ops.add(conv_op(pack, pk['hr1_b'], self.g_sr16.view(), False, 16, H4, W4, H4, W4, N, mask=self.h0.view(), mask_f32=0, slope=sl, out_bf16=g_h0.view(),
@@ -832,11 +800,7 @@ class _Plan:
             # (g_u2 already carries the LeakyReLU' of u2: HR_conv0's data-gradient applied it as its mask; g_u1 comes out of a plain conv)
             for key, name, g_hi, pre, g_pre, src, g_lo, hl, wl, last in (('model.5.', 'up2', g_u2, None, self.g_ps2, self.u1, g_u1, H2, W2, False),
                                                                           ('model.2.', 'up1', g_u1, self.ps1, self.g_ps1, self.t0h, None, h, w, True)):
-                o = Op()
-                o.op = _lib.OP_PIXUNSHUF
-                o.t[0], o.t[1], o.f[0], o.i[0], o.i[1], o.i[2], o.i[3], o.t[2] = (g_hi.view(), pre.view() if pre is not None else NULL_T, sl, N, 4 * nf,
-                                                                                  hl, wl, g_pre.view())
-                ops.add(o)
+                ops.add(make_op(_lib.OP_PIXUNSHUF, gsrc=g_hi.view(), mask=pre and pre.view(), slope=sl, N=N, C4=4 * nf, H=hl, W=wl, gdst=g_pre.view()))
                 self._wg3(ops, key, g_pre, src, 4 * nf, nf, hl, wl, hl, wl)
                 if last:   # dL/d(trunk output) leaves the f16 / scaled domain
                     ops.add(conv_op(pack, pk[name + '_b'], g_pre.view(), False, 4 * nf, hl, wl, hl, wl, N, alpha=1.0 / gs, out_f32=self.g_t0.view()))
@@ -872,11 +836,7 @@ class _Plan:
             self._subpixel_dgrad(ops, 'up2_b', g_u2, g_u1, H2, W2, mask=self.u1)
         else:
             ops.add(conv_op(pack, pk['up2_b'], g_u2.view(), True, nf, H4, W4, H4, W4, N, out_f32=g_up2.view(), in_scale=gs))
-            o = Op()
-            o.op = _lib.OP_DOWNSUM
-            o.t[0], o.i[0], o.i[1], o.i[2], o.i[3] = g_up2.view(), N, nf, H2, W2
-            o.t[1], o.i[4], o.f[0], o.t[2], o.t[3] = self.u1.view(), 1, SLOPE, g_u1.view(), NULL_T
-            ops.add(o)
+            ops.add(make_op(_lib.OP_DOWNSUM, src=g_up2.view(), N=N, C=nf, H=H2, W=W2, mask=self.u1.view(), mask_f32=1, slope=SLOPE, dst_f32=g_u1.view()))
         # upconv1 (model.3)
         self._wg(ops, 'model.3.', g_u1, True, self.t0, True, nf, nf, h, w, H2, W2, ups=1, f16=f16)
         if net.subpixel:
@@ -884,11 +844,7 @@ class _Plan:
         else:
             g_up1 = self.g2b
             ops.add(conv_op(pack, pk['up1_b'], g_u1.view(), True, nf, H2, W2, H2, W2, N, out_f32=g_up1.view(), in_scale=gs))
-            o = Op()
-            o.op = _lib.OP_DOWNSUM
-            o.t[0], o.i[0], o.i[1], o.i[2], o.i[3] = g_up1.view(), N, nf, h, w
-            o.t[1], o.i[4], o.f[0], o.t[2], o.t[3] = NULL_T, 0, SLOPE, self.g_t0.view(), NULL_T
-            ops.add(o)
+            ops.add(make_op(_lib.OP_DOWNSUM, src=g_up1.view(), N=N, C=nf, H=h, W=w, slope=SLOPE, dst_f32=self.g_t0.view()))
 
     def _build_backward_trunk(self, ops):
         net, N, h, w = self.net, self.N, self.h, self.w
@@ -978,12 +934,7 @@ class _Plan:
             ops.keep.append(st)
             ops._arr = None
         # ShortcutBlock: g_fea = g_chain + g_t0
-        o = Op()
-        o.op = _lib.OP_AXPBY
-        o.t[0], o.f[0], o.t[1], o.f[1] = G.view(), 1.0, self.g_t0.view(), 1.0
-        o.i[0], o.i[1], o.i[2], o.i[3] = N, nf, h, w
-        o.t[2], o.t[3], o.f[2] = self.g_fea.view(), NULL_T, 1.0
-        ops.add(o)
+        ops.add(make_op(_lib.OP_AXPBY, x=G.view(), a=1.0, z=self.g_t0.view(), b=1.0, N=N, C=nf, H=h, W=w, out_f32=self.g_fea.view(), gamma=1.0))
         self._wg(ops, 'model.0.', self.g_fea, True, self.x_in, True, nf, net.in_nc, h, w, h, w)
         self._marks.append((len(ops.ops), 0, rrdb0))
         ops.tag(11)
@@ -994,8 +945,8 @@ class _Plan:
         """fold 1/world_size into the deterministic wgrad reduction (data-parallel mean gradient); True if anything changed"""
         changed = False
         for o in self.bwd.ops:
-            if o.op == _lib.OP_WGRAD_REDUCE and o.f[0] != scale:
-                o.f[0] = scale
+            if o.op == _lib.OP_WGRAD_REDUCE and o.get('scale') != scale:
+                o.set('scale', scale)
                 changed = True
         if changed:
             self.bwd._arr = None

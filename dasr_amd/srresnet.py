@@ -20,7 +20,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import Op
+from ._lib import make_op
 from .engine import BTensor, ParamStore, PackRegistry, OpList, Workspace, conv_op, NULL_T
 from .rrdbnet import RRDBNetHIP, _Plan as _RRDBPlan
 
@@ -103,7 +103,7 @@ class _TrunkScale:
             if has_alpha:
                 o.conv.alpha = 1.0 / s
         for o in self._reduces:
-            o.f[1] = 1.0 / s
+            o.set('inv_prescale', 1.0 / s)
         for pl in self._plans:   # every recorded list that holds the patched ops
             pl.bwd._arr = None
             pl._segments = None
@@ -238,21 +238,13 @@ class _Plan(_RRDBPlan):
         prm.y32, prm.y16 = Y.view(), xs_out.view()
         prm.h = hb.view() if hb is not None else NULL_T
         prm.N, prm.H, prm.W, prm.res_scale, prm.slope = self.N, self.h, self.w, 1.0, 0.0
-        o = Op()
-        o.op = _lib.OP_RESBLOCK
-        o.p[0] = C.addressof(prm)
-        o.flops = 2 * 2.0 * self.N * self.h * self.w * 9 * net.nf * net.nf
-        return o, prm
+        return make_op(_lib.OP_RESBLOCK, flops=2 * 2.0 * self.N * self.h * self.w * 9 * net.nf * net.nf, p=C.addressof(prm)), prm
 
     def _build_forward(self):
         net, N, h, w = self.net, self.N, self.h, self.w
         nf, nb, P, pack, pk = net.nf, net.nb, net.params, net.pack, net.pk
         ops = OpList()
-        o = Op()
-        o.op = _lib.OP_NCHW2B
-        o.p[0], o.i[0], o.i[1], o.i[2], o.i[3] = self.x_nchw.data_ptr(), N, net.in_nc, h, w
-        o.t[0], o.t[1] = self.x_in.view(), NULL_T
-        ops.add(o)
+        ops.add(make_op(_lib.OP_NCHW2B, src=self.x_nchw.data_ptr(), N=N, C=net.in_nc, H=h, W=w, dst_f32=self.x_in.view()))
         f16 = int(net.rdb_f16)
         ops.add(conv_op(pack, pk['fea'], self.x_in.view(), True, 16, h, w, h, w, N, bias=P.ptr('model.0.bias'),
                         out_f32=self.fea.view(), out_bf16=self.xs16[0].view(), out16_f16=f16))
@@ -278,12 +270,7 @@ class _Plan(_RRDBPlan):
             if i in getattr(net, 'debug_taps', ()):   # tests: fp32 copy of this block's output (the stream buffers alternate)
                 self.taps = getattr(self, 'taps', {})
                 self.taps[i] = BTensor(N, nf, h, w, True, net.device)
-                o = Op()
-                o.op = _lib.OP_AXPBY
-                o.t[0], o.f[0], o.t[1], o.f[1] = Y.view(), 1.0, NULL_T, 0.0
-                o.i[0], o.i[1], o.i[2], o.i[3] = N, nf, h, w
-                o.t[2], o.t[3], o.f[2] = self.taps[i].view(), NULL_T, 1.0
-                ops.add(o)
+                ops.add(make_op(_lib.OP_AXPBY, x=Y.view(), a=1.0, N=N, C=nf, H=h, W=w, out_f32=self.taps[i].view(), gamma=1.0))
             X = Y
         self._build_tail_forward(ops, X)
 
@@ -327,12 +314,7 @@ class _Plan(_RRDBPlan):
             G, G16 = Gn, G16n
         ops.tag(4)
         # ShortcutBlock: g_fea = g_trunk + g_t0
-        o = Op()
-        o.op = _lib.OP_AXPBY
-        o.t[0], o.f[0], o.t[1], o.f[1] = G.view(), 1.0, self.g_t0.view(), 1.0
-        o.i[0], o.i[1], o.i[2], o.i[3] = N, nf, h, w
-        o.t[2], o.t[3], o.f[2] = self.g_fea.view(), NULL_T, 1.0
-        ops.add(o)
+        ops.add(make_op(_lib.OP_AXPBY, x=G.view(), a=1.0, z=self.g_t0.view(), b=1.0, N=N, C=nf, H=h, W=w, out_f32=self.g_fea.view(), gamma=1.0))
         self._wg(ops, 'model.0.', self.g_fea, True, self.x_in, True, nf, net.in_nc, h, w, h, w)
         self._marks.append((len(ops.ops), 0, P.off('model.1.sub.0.res.0.weight' if nb else lrk + 'weight')))
         ops.tag(11)

@@ -452,26 +452,27 @@ typedef struct {
 int dasr_gather_crops(const dasr_crop_desc* descs_dev, int32_t n, int32_t C, int32_t size, float* dst, void* stream);
 
 /* ---- executor: run a recorded list of ops in one call (keeps the host out of the step) ----------*/
+/* Which slot of dasr_op carries which argument of an op kind: the dasr_run_ops switch (csrc/misc.hip), mirrored by the table OP_ARGS of
+ * dasr_amd/_lib.py (tests/test_host.py checks the two against each other and against the parameter names below). */
 enum { DASR_OP_CONV = 1, DASR_OP_WGRAD = 2, DASR_OP_WGRAD_REDUCE = 3, DASR_OP_PACK = 4, DASR_OP_DOWNSUM = 5,
        DASR_OP_AXPBY = 6, DASR_OP_FILL = 7, DASR_OP_L1LOSS = 8, DASR_OP_NCHW2B = 9, DASR_OP_B2NCHW = 10,
        DASR_OP_INORM_FWD = 11, DASR_OP_INORM_BWD = 12, DASR_OP_BCE = 13, DASR_OP_DWT_FWD = 14, DASR_OP_DWT_BWD = 15,
        DASR_OP_LOWPASS = 16, DASR_OP_MAXPOOL = 17, DASR_OP_MAXPOOL_BWD = 18, DASR_OP_L1DIFF = 19, DASR_OP_AFFINE4 = 20,
        DASR_OP_BILINEAR = 21, DASR_OP_LOGLOSS = 22, DASR_OP_SIGMOID_BWD = 23, DASR_OP_PRELU_GRAD = 24, DASR_OP_LOWPASS_VALID = 25,
        DASR_OP_ADD_FLAT = 26, DASR_OP_SIGMOID_FWD = 27,
-       /* scheduling ops: p[0] = event from dasr_event_create / a hipStream_t (NULL: back to the stream dasr_run_ops was called with) */
+       /* scheduling ops: an event from dasr_event_create / a hipStream_t (NULL: back to the stream dasr_run_ops was called with) */
        DASR_OP_EVENT_RECORD = 28, DASR_OP_STREAM_WAIT = 29, DASR_OP_SET_STREAM = 30,
        DASR_OP_CVT_F16 = 31, DASR_OP_DOWNSUM_F16 = 32, DASR_OP_PIXSHUF = 33, DASR_OP_PIXUNSHUF = 34,
        DASR_OP_LPIPS_S2D = 35, DASR_OP_MAXPOOL3 = 36, DASR_OP_MAXPOOL3_BWD = 37, DASR_OP_LPIPS_HEAD = 38, DASR_OP_RAGAN = 39,
        DASR_OP_BNORM_FWD = 40, DASR_OP_BNORM_BWD = 41, DASR_OP_BNORM_RUNNING = 42, DASR_OP_DDM_SPREAD = 43,
        /* --wgan gradient penalty (round 4) */
        DASR_OP_INORM_JVP = 44, DASR_OP_INORM_SECOND = 45, DASR_OP_GRAD_PENALTY = 46, DASR_OP_FILL_SCALED = 47,
-       DASR_OP_CONV_CHAIN = 48,  /* p[0] device layers, p[1] host layers, p[2] device dep_chunk, i[0] nlayers, p[3] device flags; l[0] device err word */
-       DASR_OP_RDB_CHAIN = 49,   /* dasr_rdb_chain: p[0] device layers, p[1] host layers, i[0] nlayers, p[3] device flags; l[0] device err word */
-       /* --wgan with BatchNorm discriminators (round 6).  JVP: t[0] x, t[1] t, i[0..3] N C H W, i[4] group, f[0] slope, p[0] gamma, p[1] beta, p[2] stats, t[2] out.
-        * SECOND: t[0] x, t[1] t, t[2] ga, i[0..4] as above, f[0] slope, p[0..2] as above, t[3] out, i[5] accumulate, p[3] dgamma, f[1] pscale */
+       DASR_OP_CONV_CHAIN = 48,  /* dasr_conv_chain */
+       DASR_OP_RDB_CHAIN = 49,   /* dasr_rdb_chain */
+       /* --wgan with BatchNorm discriminators (round 6): dasr_bnorm_lrelu_jvp, dasr_bnorm_second */
        DASR_OP_BNORM_JVP = 50, DASR_OP_BNORM_SECOND = 51,
-       DASR_OP_PRELU_FINAL = 52,  /* dasr_prelu_final: p[0] partial, i[0] nblocks, l[0] stride, i[1] count, p[1] slopes, p[2] dsts, f[0] scale */
-       DASR_OP_RESBLOCK = 53      /* dasr_resblock: p[0] host dasr_resblock_params (kept alive by the plan) */ };
+       DASR_OP_PRELU_FINAL = 52,  /* dasr_prelu_final */
+       DASR_OP_RESBLOCK = 53      /* dasr_resblock (host dasr_resblock_params, kept alive by the plan) */ };
 
 typedef struct {
     int32_t op;  int32_t i[8];  float f[4];  int64_t l[4];  void* p[4];  dasr_tensor t[5];

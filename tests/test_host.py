@@ -463,3 +463,101 @@ def test_crc32c_fast_path_equals_the_byte_loop():
         d = bytes(rng.getrandbits(8) for _ in range(n))
         assert t.crc32c(d) == (t._crc_bytes(0xFFFFFFFF, d) ^ 0xFFFFFFFF), n
     assert t.crc32c(bytearray(b'x' * 20000)) == t.crc32c(b'x' * 20000)   # (any bytes-like object)
+
+
+def _op_layout_errors(op_args):
+    """differences between a slot-layout table (dasr_amd._lib.OP_ARGS) and the dasr_run_ops switch (csrc/misc.hip) / the entry points it calls
+    (include/dasr_hip.h): (a) OP_* numbers, (b) the slots each case reads, (c) the parameter name each plain slot argument lands on, (d) coverage"""
+    from dasr_amd import _lib
+    strip = lambda s: re.sub(r'//[^\n]*', '', re.sub(r'/\*.*?\*/', ' ', s, flags=re.S))
+    hdr = strip(open(os.path.join(ROOT, 'include', 'dasr_hip.h')).read())
+    params = {fn: [re.findall(r'(\w+)\s*(?:\[\d*\])?$', a.strip())[0] for a in args.split(',') if a.strip() not in ('', 'void')]
+              for fn, args in re.findall(r'\b(dasr_\w+)\s*\(([^;{)]*)\)\s*;', hdr)}
+    enum = {'OP_' + k: int(v) for k, v in re.findall(r'\bDASR_OP_(\w+)\s*=\s*(\d+)', hdr)}
+    src = strip(open(os.path.join(ROOT, 'dasr_amd', 'csrc', 'misc.hip')).read())
+    body = src[src.index('int dasr_run_ops('):]
+    body = body[body.index('switch'):body.index('default:')]
+    errors = []
+    ours = {k: v for k, v in vars(_lib).items() if re.fullmatch(r'OP_[A-Z0-9_]+', k) and isinstance(v, int)}
+    if ours != enum:   # (a)
+        errors.append('OP_* numbers differ from the header enum: %s' % sorted(set(ours.items()) ^ set(enum.items())))
+    errors += ['%s has no slot-layout entry' % k for k, v in ours.items() if v != _lib.OP_CONV and v not in op_args]   # (d)
+
+    def covers(code):   # the slots one table code occupies
+        return {'f*': {'f0', 'f1', 'f2', 'f3'}, 'l*': {'l0', 'l1'}}.get(code, {code[:2]})
+
+    def split_args(s):
+        out, depth, cur = [], 0, ''
+        for ch in s:
+            depth += {'(': 1, ')': -1}.get(ch, 0)
+            if ch == ',' and depth == 0:
+                out.append(cur.strip())
+                cur = ''
+            else:
+                cur += ch
+        return out + [cur.strip()]
+
+    plain = re.compile(r'(?:\([\w\s*]+\)\s*)?(\*\s*\([\w\s*]+\)\s*)?(&)?\s*o\.([iflpt])(?:\[(\d)\])?')
+    for case in re.split(r'\bcase\s+DASR_OP_', body)[1:]:
+        kind_name, code = case.split(':', 1)
+        kind = enum['OP_' + kind_name.strip()]
+        if kind == _lib.OP_CONV:
+            continue
+        table = op_args.get(kind, {})
+        read = set()
+        for amp, arr, k in re.findall(r'(&?)\s*o\.([iflpt])\b(?:\[(\d)\])?', code):
+            read |= covers('f*' if (amp and arr == 'f') else ('l*' if not k else arr + k))
+        named = set().union(*[covers(c) for c in table.values()]) if table else set()
+        if read != named:   # (b)
+            errors.append('OP_%s: the switch reads %s, the table names %s' % (kind_name.strip(), sorted(read), sorted(named)))
+        by_code = {c: n for n, c in table.items()}
+        for m in re.finditer(r'\b(dasr_\w+)\s*\(', code):
+            depth, j = 1, m.end()
+            while depth:
+                depth += {'(': 1, ')': -1}.get(code[j], 0)
+                j += 1
+            for arg, pname in zip(split_args(code[m.end():j - 1]), params[m.group(1)]):
+                a = plain.fullmatch(arg)
+                if a is None:
+                    continue   # an expression of slots (f[1] scale factors, the i[4] / i[5] selectors): named in the table, checked by (b) only
+                deref, amp, arr, k = a.groups()
+                c = arr + k + 'f' if deref else ('f*' if amp else (arr + k if k else 'l*'))
+                if by_code.get(c) != pname:   # (c)
+                    errors.append('OP_%s: %s argument %r is %s, the table calls it %r' % (kind_name.strip(), m.group(1), pname, c, by_code.get(c)))
+    return errors
+
+
+def test_op_slot_table_matches_the_switch_and_the_header():
+    from dasr_amd import _lib
+    assert _op_layout_errors(_lib.OP_ARGS) == []
+    for kind, table in _lib.OP_ARGS.items():   # make_op keywords of its own
+        assert not {'tag', 'flops', 'bytes'} & set(table), kind
+
+
+def test_op_slot_check_catches_a_swapped_slot_pair():
+    from dasr_amd import _lib
+    t = {k: dict(v) for k, v in _lib.OP_ARGS.items()}
+    lp = t[_lib.OP_LOWPASS]
+    lp['H'], lp['W'] = lp['W'], lp['H']
+    errs = _op_layout_errors(t)
+    assert len(errs) == 2 and all('dasr_lowpass' in e for e in errs), errs
+    t = {k: dict(v) for k, v in _lib.OP_ARGS.items()}
+    del t[_lib.OP_RAGAN]['score_coef']
+    assert any('OP_RAGAN: the switch reads' in e for e in _op_layout_errors(t))
+
+
+def test_make_op_writes_named_slots():
+    from dasr_amd import _lib
+    from dasr_amd.engine import OpList
+    o = _lib.make_op(_lib.OP_RAGAN, eps=1e-6, score_coef=0.5, score_b=0x1000, tag=3, flops=2.0)
+    assert (o.l[0], o.l[1], o.l[2] >> 32, o.i[7], o.flops) == (0x1000, 0x3f000000, 0, 3, 2.0)
+    assert (o.get('score_coef'), o.get('eps')) == (0.5, _lib.c_f32(1e-6).value)
+    o = _lib.make_op(_lib.OP_AFFINE4, scale4=[1, 2, 3, 4], shift4=[5, 6, 7, 8])
+    assert (list(o.f), o.get('shift4')) == ([1.0, 2.0, 3.0, 4.0], [5.0, 6.0, 7.0, 8.0])
+    with pytest.raises(TypeError, match='no argument'):
+        _lib.make_op(_lib.OP_LOWPASS, mask=None)
+    ol = OpList()
+    ol.add(_lib.make_op(_lib.OP_LPIPS_S2D, mode=1))
+    ol._arr = (_lib.Op * 1)(*ol.ops)
+    ol.set(0, 'mode', 1 | (5 << 4))   # patched in the recorded op and in its ctypes image
+    assert ol.ops[0].i[3] == ol._arr[0].i[3] == 81

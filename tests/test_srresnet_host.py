@@ -112,7 +112,7 @@ def test_plans_record_on_the_host(trunk_prec, fused):
     assert all(a[0] == b[1] for a, b in zip(spans, spans[1:]))
     if trunk_prec == 2:   # a new scale reaches every scaled op and reduction of every plan of the shape
         st.set_gscale_from(3e-6)
-        assert st.gscale == 2.0 ** 18 and st._scaled and all(o.conv.gamma == st.gscale for o, _ in st._scaled) and all(o.f[1] == 2.0 ** -18 for o in st._reduces)
+        assert st.gscale == 2.0 ** 18 and st._scaled and all(o.conv.gamma == st.gscale for o, _ in st._scaled) and all(o.get('inv_prescale') == 2.0 ** -18 for o in st._reduces)
 
 
 @pytest.mark.parametrize('model', ['DASR', 'DASR_FS_ESRGAN_patchGAN'])
