@@ -331,6 +331,14 @@ extern "C" int dasr_downsum2x(dasr_tensor src, int32_t N, int32_t C, int32_t H, 
 
 // ---- f16-storage helpers of the generator's HR tail ---------------------------------------------------------------------------
 // y16 = f16(scale * x) over a blocked f32 tensor (dL/dSR -> pre-scaled f16 gradient)
+// In the three converters `scale * x` is rounded to f32 before the 16-bit rounding, as documented (and as torch's half() / bfloat16() of the f32 product).
+// Left to itself the compiler folds product and f16 rounding into v_fma_mixlo_f16 with a +0 addend (fp contract off does not stop it): -0 came out as +0,
+// and a product that is not exact in f32 was rounded once instead of twice.  The empty asm makes the f32 product a value the rounding cannot look through.
+__device__ __forceinline__ float f32_rounded(float v) {
+    asm("" : "+v"(v));
+    return v;
+}
+
 __global__ void cvt_f16_kernel(dasr_tensor x, int N, int C, int H, int W, float scale, dasr_tensor y) {
     const int ncb = (C + 15) >> 4;
     const long long per_plane = (long long)H * W * 4, total = (long long)N * ncb * per_plane;
@@ -341,7 +349,7 @@ __global__ void cvt_f16_kernel(dasr_tensor x, int N, int C, int H, int W, float 
     const int cb = t % ncb, n = t / ncb;
     const f32x4 v = *(const f32x4*)((const float*)x.p + (size_t)n * x.n_stride + (size_t)cb * x.cb_stride + e);
     f16x4 o;
-    for (int j = 0; j < 4; ++j) o[j] = (f16_t)(v[j] * scale);
+    for (int j = 0; j < 4; ++j) o[j] = (f16_t)f32_rounded(v[j] * scale);
     *(f16x4*)((f16_t*)y.p + (size_t)n * y.n_stride + (size_t)cb * y.cb_stride + e) = o;
 }
 
@@ -358,7 +366,7 @@ __global__ void f16_residual_kernel(dasr_tensor x, int N, int C, int H, int W, f
     const f32x4 v = *(const f32x4*)((const float*)x.p + (size_t)n * x.n_stride + (size_t)cb * x.cb_stride + e);
     const float inv = 1.f / scale;
     f32x4 o;
-    for (int j = 0; j < 4; ++j) o[j] = v[j] - (float)(f16_t)(v[j] * scale) * inv;
+    for (int j = 0; j < 4; ++j) o[j] = v[j] - (float)(f16_t)f32_rounded(v[j] * scale) * inv;
     *(f32x4*)((float*)y.p + (size_t)n * y.n_stride + (size_t)cb * y.cb_stride + e) = o;
 }
 
@@ -377,7 +385,7 @@ __global__ void cvt_split16_kernel(dasr_tensor x, int N, int C, int H, int W, fl
     const size_t lo = (size_t)ncb * y.cb_stride;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const float vv = v[j] * scale;
+        const float vv = f32_rounded(v[j] * scale);
         const T h = (T)vv;
         yp[j] = h;
         yp[lo + j] = (T)(vv - (float)h);

@@ -468,14 +468,15 @@ class WgradGroup3:
         wp.kh, wp.stride, wp.pad, wp.want_bias = 3, 1, 1, int(bool(want_bias))
         self.parts.append((wp, [(i, t) for i, t in enumerate(tiles) if t is not None]))
 
-    def finalize(self, workspace, device, target_wgs=256, ppu=0):
+    def finalize(self, workspace, device, target_wgs=256, ppu=0, nsplit=None):
         """ppu: the parts come in units of `ppu` consecutive parts that read the same tensors (one dense block); when the split count is not
-        a multiple of 8 the kernel then places each (unit, split) on one XCD (csrc/wgrad.hip, w3_block_map)"""
+        a multiple of 8 the kernel then places each (unit, split) on one XCD (csrc/wgrad.hip, w3_block_map).
+        nsplit: this split count instead of the one derived from target_wgs (tests: more splits than pixel tiles, whose surplus splits write zeros)"""
         wp0 = self.parts[0][0]
         ntiles = wp0.N * ceil_div(wp0.Hout, 8) * ceil_div(wp0.Wout, 16)
         nparts = len(self.parts)
-        self.nsplit = max(1, min(ntiles, target_wgs // nparts))
-        if self.nsplit >= 8:
+        self.nsplit = max(1, min(ntiles, target_wgs // nparts)) if nsplit is None else int(nsplit)
+        if nsplit is None and self.nsplit >= 8:
             # a multiple of 8: workgroup b runs on XCD b % 8, so with block = part * nsplit + split every part's workgroup of a given pixel split
             # lands on the same XCD and the G / X tiles the parts share are fetched once per XCD.  17 splits (255 workgroups instead of 240)
             # was 3 % faster on the launch but fetched 60 % more (351 vs 220 MB raw FETCH_SIZE per RRDB launch): not kept
