@@ -275,6 +275,10 @@ _SIGS = {
     'dasr_maxpool3s2': [Tensor, c_i32, c_i32, c_i32, c_i32, Tensor, c_vp],
     'dasr_maxpool3s2_bwd': [Tensor, Tensor, c_i32, c_i32, c_i32, c_i32, Tensor, c_i32, c_i32, c_vp],
     'dasr_lpips_head': [Tensor, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, c_f32, c_f32, c_vp, Tensor, c_i32, c_vp],
+    'dasr_img_ws_bytes': [c_i32, c_i32, c_i32, c_i32, c_i32],
+    'dasr_tensor2img_u8': [c_vp, c_i32, c_i32, c_i32, c_i32, C.c_double, C.c_double, c_vp, c_vp, c_vp, c_vp],
+    'dasr_img_sse': [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp],
+    'dasr_img_ssim': [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp],
     'dasr_prof_begin': [c_i32],
     'dasr_prof_end': [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp],
 }
@@ -289,7 +293,7 @@ _BENCH_SIGS = {
 }
 BENCH_LIB_PATH = os.path.join(HERE, 'libdasr_bench.so')
 
-ABI_VERSION = 21
+ABI_VERSION = 22
 _lib = None
 _bench = None
 

@@ -1,0 +1,141 @@
+"""Device-side image quality of the SRN validation / evaluation drivers (opt-in: top-level option `device_metrics: true`).
+
+What `test.evaluate` / `train.validate` otherwise do on the host with numpy (util.tensor2img, calculate_psnr, calculate_ssim, bgr2ycbcr;
+reference codes/SRN/utils/util.py:180-204, :236-291, data/util.py:169-190) runs here on csrc/metrics.hip: the fp32 SR / HR images the trainer holds
+after test() are quantised to uint8 on the device, the squared-error sums (integer for RGB, fp64 for Y) and the fp64 SSIM means are formed there,
+and ONE small read-back per call brings them to the host, where PSNR is formed in double with util.calculate_psnr's formula.  Numerics: DESIGN.md.
+"""
+import ctypes as C
+import logging
+import math
+
+import torch
+
+from . import _lib, util
+
+SSIM_WINDOW = 11
+_bufs = {}
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _as_batch(t):
+    """fp32 contiguous [N, C, H, W] view of a 4-D batch, a 3-D image or a 2-D plane"""
+    if t.dim() == 2:
+        t = t[None, None]
+    elif t.dim() == 3:
+        t = t[None]
+    if t.dim() != 4 or t.shape[1] not in (1, 3):
+        raise TypeError('expected [N, 3|1, H, W], [3|1, H, W] or [H, W], got shape %s' % (tuple(t.shape),))
+    return t.detach().float().contiguous()
+
+
+def tensor2img_device(t, min_max=(0, 1)):
+    """util.tensor2img on the device: [1, 3|1, H, W] / [3|1, H, W] / [H, W] fp32 device tensor -> uint8 device tensor, HWC BGR for 3 channels, HW for one,
+    byte for byte what the host function returns.  (A batch of several images is the host function's make_grid case and stays there.)"""
+    t = t.squeeze()
+    if t.dim() not in (2, 3):
+        raise TypeError('tensor2img_device takes one image (3D or 2D after squeeze()); the make_grid case of a batch stays on util.tensor2img. '
+                        'Received dimension: {:d}'.format(t.dim()))
+    x = _as_batch(t)
+    n, c, h, w = x.shape
+    out = torch.empty((h, w, c) if c == 3 else (h, w), dtype=torch.uint8, device=x.device)
+    _lib.check(_lib.lib().dasr_tensor2img_u8(x.data_ptr(), n, c, h, w, float(min_max[0]), float(min_max[1]), out.data_ptr(), None, None, _stream()),
+               'dasr_tensor2img_u8')
+    return out
+
+
+def _buffers(shape, crop, device):
+    """per (shape, crop, device): the two planar uint8 images, the partial-sum workspace and the result words.
+    res (int64 words): [0, N) integer squared-error sums, [N, 2N) fp64 Y squared-error sums, [2N, 3N) SSIM, [3N, 4N) SSIM_Y, word 4N: the two int32 NaN counts (SR, HR)"""
+    key = (tuple(shape), crop, str(device))
+    b = _bufs.get(key)
+    if b is None:
+        n, c, h, w = shape
+        ws_bytes = _lib.lib().dasr_img_ws_bytes(n, c, h, w, crop)
+        if ws_bytes < 0:
+            raise _lib.DasrHipError('dasr_img_ws_bytes refuses N %d C %d H %d W %d crop %d' % (n, c, h, w, crop))
+        b = (torch.empty(shape, dtype=torch.uint8, device=device), torch.empty(shape, dtype=torch.uint8, device=device),
+             torch.empty(max(ws_bytes // 8, 1), dtype=torch.int64, device=device), torch.zeros(4 * n + 1, dtype=torch.int64, device=device))
+        _bufs[key] = b
+    return b
+
+
+def _psnr(sse, count):
+    """util.calculate_psnr from the sum of squared differences"""
+    mse = float(sse) / count
+    if mse == 0:
+        return float('inf')
+    return 20 * math.log10(255.0 / math.sqrt(mse))
+
+
+def _host_metrics(sr, hr, crop, ssim, y, min_max):
+    """the drivers' host sequence (test.py), image by image: where the device SSIM has no valid region the host function decides what happens"""
+    out = {'psnr': [], 'ssim': [], 'psnr_y': [], 'ssim_y': []}
+    c = crop
+    for i in range(sr.shape[0]):
+        a, b = util.tensor2img(sr[i], min_max=min_max) / 255., util.tensor2img(hr[i], min_max=min_max) / 255.
+        a3, b3 = (a, b) if a.ndim == 3 else (a[:, :, None], b[:, :, None])
+        ca, cb = a3[c:a.shape[0] - c, c:a.shape[1] - c, :], b3[c:a.shape[0] - c, c:a.shape[1] - c, :]
+        out['psnr'].append(util.calculate_psnr(ca * 255, cb * 255))
+        if ssim:
+            out['ssim'].append(util.calculate_ssim(ca * 255, cb * 255))
+        if y and a.ndim == 3:
+            ay, by = util.bgr2ycbcr(a, only_y=True), util.bgr2ycbcr(b, only_y=True)
+            cay, cby = ay[c:a.shape[0] - c, c:a.shape[1] - c], by[c:a.shape[0] - c, c:a.shape[1] - c]
+            out['psnr_y'].append(util.calculate_psnr(cay * 255, cby * 255))
+            if ssim:
+                out['ssim_y'].append(util.calculate_ssim(cay * 255, cby * 255))
+    return {k: v for k, v in out.items() if v}
+
+
+def batch_metrics(sr, hr, crop, ssim=True, y=True, min_max=(0, 1)):
+    """dict of lists (one entry per image of the batch) of Python floats: 'psnr', 'ssim' (if `ssim`), and for 3 channels 'psnr_y' (if `y`) and
+    'ssim_y' (if both), of the uint8 images tensor2img makes of `sr` and `hr`, each cropped by `crop` pixels per side.  One device -> host
+    synchronisation.  A cropped side under 11 pixels with `ssim`: the host functions are used for the whole call."""
+    sr, hr = _as_batch(sr), _as_batch(hr)
+    if sr.shape != hr.shape:
+        raise ValueError('SR %s and HR %s must have the same shape' % (tuple(sr.shape), tuple(hr.shape)))
+    n, c, h, w = sr.shape
+    crop = int(crop)
+    ch, cw = h - 2 * crop, w - 2 * crop
+    if crop < 0 or ch < 1 or cw < 1:
+        raise ValueError('crop %d leaves nothing of a %d x %d image' % (crop, h, w))
+    if ssim and (ch < SSIM_WINDOW or cw < SSIM_WINDOW):
+        return _host_metrics(sr, hr, crop, ssim, y, min_max)
+    if not (sr.is_cuda and hr.is_cuda and sr.device == hr.device):
+        raise _lib.DasrHipError('batch_metrics needs both images on one GPU (the host path is dasr_amd.util)')
+    L, st = _lib.lib(), _stream()
+    y = bool(y) and c == 3
+    with torch.cuda.device(sr.device):
+        pa, pb, ws, res = _buffers(sr.shape, crop, sr.device)
+        r0, ws_bytes = res.data_ptr(), ws.numel() * 8
+        lo, hi = float(min_max[0]), float(min_max[1])
+        _lib.check(L.dasr_tensor2img_u8(sr.data_ptr(), n, c, h, w, lo, hi, None, pa.data_ptr(), r0 + 32 * n, st), 'dasr_tensor2img_u8')
+        _lib.check(L.dasr_tensor2img_u8(hr.data_ptr(), n, c, h, w, lo, hi, None, pb.data_ptr(), r0 + 32 * n + 4, st), 'dasr_tensor2img_u8')
+        _lib.check(L.dasr_img_sse(pa.data_ptr(), pb.data_ptr(), n, c, h, w, crop, r0, (r0 + 8 * n) if y else None, ws.data_ptr(), ws_bytes, st), 'dasr_img_sse')
+        if ssim:
+            _lib.check(L.dasr_img_ssim(pa.data_ptr(), pb.data_ptr(), n, c, h, w, crop, 0, r0 + 16 * n, ws.data_ptr(), ws_bytes, st), 'dasr_img_ssim')
+            if y:
+                _lib.check(L.dasr_img_ssim(pa.data_ptr(), pb.data_ptr(), n, c, h, w, crop, 1, r0 + 24 * n, ws.data_ptr(), ws_bytes, st), 'dasr_img_ssim')
+        host = res.cpu()   # the one synchronisation
+    f64 = host.view(torch.float64)
+    nan_sr, nan_hr = host[4 * n:].view(torch.int32).tolist()
+    if nan_sr or nan_hr:
+        logging.getLogger('base').warning('image metrics: %d NaN in the SR image(s), %d in the HR image(s) (quantised to 0)' % (nan_sr, nan_hr))
+    out = {'psnr': [_psnr(v, c * ch * cw) for v in host[:n].tolist()]}
+    if ssim:
+        out['ssim'] = f64[2 * n:3 * n].tolist()
+    if y:
+        out['psnr_y'] = [_psnr(v, ch * cw) for v in f64[n:2 * n].tolist()]
+        if ssim:
+            out['ssim_y'] = f64[3 * n:4 * n].tolist()
+    return out
+
+
+def image_metrics(sr, hr, crop, ssim=True, y=True, min_max=(0, 1)):
+    """batch_metrics for image 0 of the batch (what get_current_visuals hands the drivers): dict of Python floats"""
+    sr, hr = _as_batch(sr), _as_batch(hr)
+    return {k: v[0] for k, v in batch_metrics(sr[:1], hr[:1], crop, ssim=ssim, y=y, min_max=min_max).items()}

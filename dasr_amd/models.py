@@ -162,6 +162,32 @@ class BaseModel:
     def get_current_learning_rate(self):
         return self.schedulers[0].get_lr()
 
+    # ---- device-side image quality (option `device_metrics`; dasr_amd/metrics.py) ---------------------------------------------
+    def _device_metrics(self):
+        from . import metrics
+        if not getattr(self, '_device_metrics_announced', False):
+            self._device_metrics_announced = True
+            logger.info('device_metrics: SR images are quantised and PSNR / SSIM (RGB and Y) evaluated on the GPU (csrc/metrics.hip)')
+        return metrics
+
+    def current_sr_u8(self):
+        """the SR image of the last test() as util.tensor2img returns it (host uint8, HWC BGR or HW), quantised on the device: one byte per sample
+        crosses to the host instead of four"""
+        return self._device_metrics().tensor2img_device(self.fake_H.detach()[0]).cpu().numpy()
+
+    def current_metrics(self, crop):
+        """PSNR / SSIM (and their Y forms for 3 channels) of image 0 of the last test() against the ground truth of the last feed_data, on the device:
+        dict of floats 'psnr', 'ssim', 'psnr_y', 'ssim_y' (metrics.image_metrics)"""
+        hr = getattr(self, 'real_H', None)          # SRModel
+        if hr is None and getattr(self, 'needHR', True):
+            hr = getattr(self, 'var_H', None)       # DASR_Model
+        sr = self.fake_H
+        if hr is None or sr is None:
+            raise RuntimeError('current_metrics needs test() on a batch that carried an HR image (feed_data was given no HR)')
+        if hr.shape[1:] != sr.shape[1:]:
+            raise RuntimeError('current_metrics: HR %s does not belong to SR %s (the last feed_data carried no HR?)' % (tuple(hr.shape), tuple(sr.shape)))
+        return self._device_metrics().image_metrics(sr.detach()[:1], hr.detach()[:1], crop)
+
     def get_network_description(self, network):
         n = network.params.total
         s = '%s(%s)' % (network.__class__.__name__, ', '.join('%s%s' % (k, list(v[1])) for k, v in list(network.params.spec.items())[:4]) + ', ...')

@@ -100,15 +100,22 @@ def validate(model, val_set, opt, current_step, logger):
         util.mkdir(img_dir)
         model.feed_data(val_data, False)
         model.test()
-        visuals = model.get_current_visuals()
-        sr_img = util.tensor2img(visuals['SR'])
+        dev = bool(opt['device_metrics'])   # image quantised and PSNR formed on the GPU (dasr_amd/metrics.py); absent: the host path below
+        if dev:
+            sr_img, lpips = model.current_sr_u8(), (model.LPIPS if opt['val_lpips'] else None)
+        else:
+            visuals = model.get_current_visuals()
+            sr_img, lpips = util.tensor2img(visuals['SR']), (visuals['LPIPS'] if opt['val_lpips'] else None)
         log_info = '{}'.format(val_data['HR_path'][0].split('/')[-1])
         if opt['val_lpips']:      # train.py:194-197
-            avg_lpips += float(visuals['LPIPS'])
-            log_info += '         {}:{:.3f}'.format(model.lpips_label, float(visuals['LPIPS']))
+            avg_lpips += float(lpips)
+            log_info += '         {}:{:.3f}'.format(model.lpips_label, float(lpips))
         logger.info(log_info)
         util.save_img(sr_img, os.path.join(img_dir, '{:s}_{:d}.png'.format(img_name, current_step)))
-        if 'HR' in visuals:
+        if dev:
+            if 'HR' in val_data:
+                avg_psnr += model.current_metrics(opt['scale'])['psnr']
+        elif 'HR' in visuals:
             gt_img = util.tensor2img(visuals['HR'])
             c = opt['scale']
             avg_psnr += util.calculate_psnr((sr_img / 255.)[c:-c, c:-c, :] * 255, (gt_img / 255.)[c:-c, c:-c, :] * 255)

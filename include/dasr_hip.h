@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define DASR_ABI_VERSION 21
+#define DASR_ABI_VERSION 22
 #define DASR_EINVAL (-22)
 #define DASR_ECAPTURE (-16)   /* a launch needed a device allocation (the scratch row of a deterministic grid sum, first use per accumulator and stream) while its stream was being captured */
 
@@ -503,6 +503,35 @@ int dasr_rccl_init(const void* id128, int32_t rank, int32_t world, void** comm_o
 int dasr_allreduce(void* comm, float* buf, int64_t count, void* stream);
 int dasr_broadcast(void* comm, float* buf, int64_t count, int32_t root, void* stream);
 int dasr_rccl_destroy(void* comm);
+
+/* ---- image-quality metrics of the validation / evaluation drivers (csrc/metrics.hip, ABI 22) -------------------------------------
+ * Replaces the host numpy of codes/SRN/utils/util.py:180-204 (tensor2img), :236-291 (calculate_psnr / ssim / calculate_ssim) and
+ * data/util.py:169-190 (bgr2ycbcr, Y only) on what the trainers hold after test(): contiguous fp32 NCHW device images, C = 3 or 1.
+ *
+ * dasr_tensor2img_u8: u = rint(((clamp(x, lo, hi) - lo) / (hi - lo)) * 255.0f) in fp32, in tensor2img's order of operations, round half to even,
+ * as uint8 -- byte for byte the host function.  Two outputs, either may be NULL (not both): hwc_bgr [N][H][W][C] with the channel order reversed
+ * (what save_img takes; C = 1: [N][H][W]) and planar [N][C][H][W] in the input's channel order (what the two entry points below read).  A NaN
+ * becomes 0 and is counted in *nan_count (device int32, may be NULL; set to zero by the call).
+ *
+ * dasr_img_sse: over rows [crop, H - crop) x columns [crop, W - crop) of two planar uint8 images, per image n: sse[n] = the INTEGER sum of the squared
+ * differences over all channels (PSNR = 20 log10(255 / sqrt(sse / count)) is left to the caller); sse_y[n] (may be NULL; C = 3 only) = the fp64 sum
+ * of the squared difference of y = (((24.966 B + 128.553 G + 65.481 R) / 255 + 16) / 255) * 255 (bgr2ycbcr's float branch and the `* 255` of the
+ * call site, unrounded), planes in R, G, B order.
+ *
+ * dasr_img_ssim: ssim[n] = mean over every channel and every pixel of the 'valid' region of the cropped images of the SSIM map: window 11 x 11,
+ * sigma 1.5, normalised, applied separably, C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2, fp64 throughout.  y_channel 1 (C = 3 only): on y as above.
+ * A cropped side under 11 pixels has no valid region: DASR_EINVAL.
+ *
+ * The grid sums are per-workgroup partials in `ws` (device, ws_size bytes >= dasr_img_ws_bytes(N, C, H, W, crop), 8-byte aligned) added in index order
+ * by a second launch: no floating-point atomics, the same bits run to run.  Calls that share `ws` must be ordered by their stream.  sse, sse_y, ssim,
+ * nan_count: device memory; nothing is synchronised.  Null pointers, N <= 0, C not 1 or 3, 2 crop >= H or W: DASR_EINVAL, nothing is launched. */
+int dasr_img_ws_bytes(int32_t N, int32_t C, int32_t H, int32_t W, int32_t crop);   /* bytes, or DASR_EINVAL */
+int dasr_tensor2img_u8(const float* x, int32_t N, int32_t C, int32_t H, int32_t W, double lo, double hi, uint8_t* hwc_bgr, uint8_t* planar,
+                       int32_t* nan_count, void* stream);
+int dasr_img_sse(const uint8_t* a, const uint8_t* b, int32_t N, int32_t C, int32_t H, int32_t W, int32_t crop, int64_t* sse, double* sse_y,
+                 void* ws, int64_t ws_size, void* stream);
+int dasr_img_ssim(const uint8_t* a, const uint8_t* b, int32_t N, int32_t C, int32_t H, int32_t W, int32_t crop, int32_t y_channel, double* ssim,
+                  void* ws, int64_t ws_size, void* stream);
 
 /* ---- profiling session (bench.py `roofline`) -----------------------------------------------------------
  * Between dasr_prof_begin and dasr_prof_end every kernel launch of the library (up to `capacity`) carries its own start/stop
