@@ -271,7 +271,8 @@ int dasr_pixel_unshuffle_f16(dasr_tensor gsrc, dasr_tensor mask /* f16 [C4 @ HxW
                              int32_t W, dasr_tensor gdst, void* stream);
 
 /* out = a*x + b*z (z optional) over blocked f32 tensors, optional bf16 copy scaled by gamma
- * (ShortcutBlock / RRDB residual bookkeeping, block.py:97-105,305-309) */
+ * (ShortcutBlock / RRDB residual bookkeeping, block.py:97-105,305-309).  Like the two down-sums, it works on whole 16-channel planes:
+ * the padding channels of the last plane are computed like real ones (zero in, zero out). */
 int dasr_axpby(dasr_tensor x, float a, dasr_tensor z, float b, int32_t N, int32_t C, int32_t H, int32_t W,
                dasr_tensor out_f32, dasr_tensor out_bf16, float gamma, dasr_tensor mask /* optional (P)ReLU' mask, f32 */, float slope,
                const float* slope_ptr, void* stream);
@@ -368,16 +369,21 @@ int dasr_lowpass(dasr_tensor x, dasr_tensor x2, const float* w, int32_t k, int32
                  int32_t mode, float a_h, float b_h, dasr_tensor out_low, dasr_tensor out_high, int32_t accumulate, void* stream);
 /* nn.MaxPool2d(2,2) of the VGG19 feature stack, forward and backward (Ho, Wo = pooled size; Win = width of the INPUT: 2 Wo or 2 Wo + 1 --
  * an odd input drops its last row / column as nn.MaxPool2d's floor does; 0 = 2 Wo.  Round 3: before, odd inputs were mis-addressed); is_f32: 0 bf16, 1 f32, 2 f16 tensors; 3 / 4: split f16 / bf16 tensors (C channels in 2 * ceil(C/16) planes: hi planes, then lo planes);
- * backward only: 5 = split f16 activations x, plain f16 gradients */
+ * backward only: 5 = split f16 activations x, plain f16 gradients.  Whole 16-channel planes are pooled, padding channels included (zero in, zero out);
+ * of tied maxima the first in scan order wins (ATen); split tensors compare hi + lo and move the (hi, lo) pair unchanged. */
 int dasr_maxpool2(dasr_tensor x, int32_t is_f32, int32_t N, int32_t C, int32_t Ho, int32_t Wo, dasr_tensor y, int32_t Win, void* stream);
-/* relu_mask: also zero the gradient where the pooled maximum is <= 0 (the ReLU' of the conv feeding the pool) */
+/* relu_mask: also zero the gradient where the pooled maximum is <= 0 (the ReLU' of the conv feeding the pool).  Every element of every 2x2 window of gx is
+ * written (the gradient or zero).  The last row / column of gx that an odd input size leaves outside every window is NOT written: the trainers rely on
+ * zero at allocation there. */
 int dasr_maxpool2_bwd(dasr_tensor x, dasr_tensor gy, int32_t is_f32, int32_t N, int32_t C, int32_t Ho, int32_t Wo, dasr_tensor gx,
                       int32_t relu_mask, int32_t Win, void* stream);
 /* L1 between two blocked tensors (feature loss DASR_model.py:224-229; LL loss :220-222): loss_acc += coef*sum|a-b|,
  * ga = gcoef*sign(a-b).  is_f32 bit 1 set: squared form (MSE of the DSN VGG16 perceptual loss, loss.py:119-130). */
 int dasr_l1_diff(dasr_tensor a, dasr_tensor b, int32_t is_f32, int32_t N, int32_t C, int32_t H, int32_t W, float coef, float gcoef,
                  float* loss_acc, dasr_tensor ga, void* stream);
-/* per-channel affine on <=4 channels (VGG input normalisation architecture.py:1086-1087 and its adjoint); y_f32: 0 bf16, 1 f32, 2 f16 output, 3 split f16 (hi in plane 0, remainder in plane 1; no accumulate) */
+/* per-channel affine on <=4 channels (VGG input normalisation architecture.py:1086-1087 and its adjoint); y_f32: 0 bf16, 1 f32, 2 f16 output, 3 split f16 (hi in plane 0, remainder in plane 1; no accumulate).
+ * accumulate 0: all 16 channels of plane 0 of y are written (both planes of the split form), zero from channel C on; accumulate != 0: y[c] += for c < C, the
+ * channels from C on keep what they held.  Planes of y past those are never touched.  scale4 / shift4: HOST pointers (read by the launcher). */
 int dasr_affine4(dasr_tensor x, int32_t N, int32_t C, int32_t H, int32_t W, const float* scale4, const float* shift4, dasr_tensor y,
                  int32_t y_f32, int32_t accumulate, void* stream);
 /* F.interpolate(bilinear, align_corners=False) of the domain-distance map (DASR_model.py:173-174), NCHW [N][1][h][w] */
