@@ -279,6 +279,8 @@ _SIGS = {
     'dasr_tensor2img_u8': [c_vp, c_i32, c_i32, c_i32, c_i32, C.c_double, C.c_double, c_vp, c_vp, c_vp, c_vp],
     'dasr_img_sse': [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp],
     'dasr_img_ssim': [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp],
+    'dasr_u8_to_planar': [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp],
+    'dasr_imresize_down': [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     'dasr_prof_begin': [c_i32],
     'dasr_prof_end': [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp],
 }

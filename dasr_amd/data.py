@@ -119,10 +119,11 @@ class DeviceUnpairedDataset:
                 yield self.batch(idx)
 
 
-def _bicubic_resample_matrix(n_in, scale):
-    """(n_out x n_in) matrix of MATLAB's imresize along one axis: bicubic kernel (a = -0.5), widened by 1 / scale and scaled by `scale` when shrinking (antialiasing), rows
-    normalised to sum 1, samples beyond the ends mirrored about the edge (the edge sample itself repeated).  Output sample k (1-based) sits at u = k / scale + (1 - 1 / scale) / 2
-    in input coordinates.  What codes/SRN/data/util.py:243-297 + the per-row products of imresize_np (:367-433) compute, as one dense matrix in float64."""
+def bicubic_taps(n_in, scale):
+    """per-output-sample taps of MATLAB's imresize along one axis, in float64: (j, w), both [n_out, taps] with taps = ceil(kernel width) + 2.  Bicubic kernel (a = -0.5),
+    widened by 1 / scale and scaled by `scale` when shrinking (antialiasing), weights normalised to sum 1 per output sample, samples beyond the ends mirrored about the edge
+    (the edge sample itself repeated): j is the 0-based source index after mirroring.  Output sample k (1-based) sits at u = k / scale + (1 - 1 / scale) / 2 in input
+    coordinates.  What codes/SRN/data/util.py:243-297 computes.  The dense matrix of imresize_matlab and the device tables of dasr_imresize_down both come from here."""
     import math
     n_out = int(math.ceil(n_in * scale))
     width = 4.0 / scale if scale < 1 else 4.0
@@ -140,7 +141,14 @@ def _bicubic_resample_matrix(n_in, scale):
     j = idx.long() - 1                                                              # 0-based; mirror: -1 -> 0, -2 -> 1, n -> n - 1, n + 1 -> n - 2
     j = torch.where(j < 0, -j - 1, j)
     j = torch.where(j >= n_in, 2 * n_in - 1 - j, j).clamp_(0, n_in - 1)
-    M = torch.zeros(n_out, n_in, dtype=torch.float64)
+    return j, w
+
+
+def _bicubic_resample_matrix(n_in, scale):
+    """(n_out x n_in) matrix of MATLAB's imresize along one axis: the taps of bicubic_taps scattered into one dense float64 matrix (the per-row products of imresize_np,
+    codes/SRN/data/util.py:367-433)."""
+    j, w = bicubic_taps(n_in, scale)
+    M = torch.zeros(j.shape[0], n_in, dtype=torch.float64)
     M.scatter_add_(1, j, w)
     return M
 
@@ -221,3 +229,145 @@ class DevicePairedDataset:
             idx = order[b * self.n:(b + 1) * self.n]
             if idx:
                 yield self.batch(idx)
+
+
+# ---- evaluation / validation folders (`mode: "LRHR"` in the val / test phase, `mode: "LR"`) -----------------------------------------
+def eval_folder_check_options(ds_opt):
+    """what the val / test datasets of the reference can be asked for and this one does not do: one NotImplementedError each, before any file is touched"""
+    mode = ds_opt.get('mode')
+    if mode not in ('LRHR', 'LR'):
+        raise NotImplementedError('EvalFolderDataset reads mode "LRHR" (val / test phase) and mode "LR", not [{}]'.format(mode))
+    if ds_opt.get('data_type') == 'lmdb':
+        raise NotImplementedError('data_type "lmdb" is not read here: unpack the database into a folder of image files')
+    if ds_opt.get('color') is not None:
+        raise NotImplementedError('color "{}": colour-space conversion of the inputs (channel_convert) is not implemented; leave `color` null'.format(ds_opt['color']))
+    if ds_opt.get('subset_file') is not None:
+        raise NotImplementedError('subset_file is a training-phase list (LRHR_dataset.py:26-31); the val / test datasets read whole folders')
+
+
+def eval_folder_pairs(ds_opt):
+    """(HR paths or None, LR paths or None) of a val / test dataset: each folder listed by image_paths (sorted), paired by index, with the reference's assertions
+    (LRHR_dataset.py:33-40, LR_dataset.py:17-18).  An LRHR set whose LR folder is missing or lists nothing makes its LR images from the HR images, like the reference."""
+    eval_folder_check_options(ds_opt)
+
+    def listing(key):
+        root = ds_opt.get(key)
+        if root is None:
+            return None
+        assert os.path.isdir(root), '{:s} is not a valid directory'.format(root)
+        return image_paths(root)
+    if ds_opt['mode'] == 'LR':
+        paths_LR = listing('dataroot_LR')
+        assert paths_LR, 'Error: LR paths are empty.'
+        return None, paths_LR
+    paths_HR, paths_LR = listing('dataroot_HR'), listing('dataroot_LR')
+    assert paths_HR, 'Error: HR path is empty.'
+    if paths_LR:
+        assert len(paths_LR) == len(paths_HR), 'HR and LR datasets have different number of images - {}, {}.'.format(len(paths_LR), len(paths_HR))
+    return paths_HR, (paths_LR or None)
+
+
+def modcrop_size(H, W, scale):
+    """size of the window util.modcrop keeps (data/util.py:133-145): H % scale bottom rows and W % scale right columns go"""
+    return H - H % scale, W - W % scale
+
+
+class EvalFolderDataset:
+    """The val / test phase of `mode: "LRHR"` (codes/SRN/data/LRHR_dataset.py:44-126) and `mode: "LR"` (LR_dataset.py) over folders of image files: an iterable with a
+    length whose items are batches of one, {'LR' [1,3,h,w], 'HR' [1,3,H,W] (LRHR only), 'LR_path', 'HR_path' (lists of one string)}, fp32 on the device.
+
+    Per item the file is decoded by PIL on the host (RGB, uint8), its BYTES are uploaded, and csrc/imgio.hip does the rest: dasr_u8_to_planar gives the planar fp32
+    image in [0, 1] (bit for bit load_image), cropped to a multiple of `scale` for HR (modcrop); without LR files the LR image is dasr_imresize_down of the cropped HR
+    (MATLAB bicubic with antialiasing, the fp64 taps of bicubic_taps, one rounding to fp32: within one fp32 unit of imresize_matlab).  .npy files (CHW or 1CHW float
+    arrays, as load_image reads them) are uploaded as they are.  Nothing is kept across items but the tap tables per (length, scale) and the fp64 intermediate per shape."""
+
+    def __init__(self, ds_opt, scale=4, device=None):
+        self.opt, self.scale = ds_opt, int(scale)
+        self.mode = ds_opt.get('mode')
+        self.paths_HR, self.paths_LR = eval_folder_pairs(ds_opt)
+        self._device = device
+        self._taps, self._tmp = {}, {}
+
+    def __len__(self):
+        return len(self.paths_HR if self.paths_HR is not None else self.paths_LR)
+
+    @property
+    def device(self):
+        if not isinstance(self._device, torch.device):   # resolved on first use: listing and pairing (the constructor) need no GPU
+            ensure_runtime_ready()
+            self._device = torch.device('cuda', torch.cuda.current_device()) if self._device is None else torch.device(self._device)
+        return self._device
+
+    @staticmethod
+    def decode(path):
+        """host part of reading one file: the uint8 [H, W, 3] RGB array PIL decodes (a .npy file: the CHW fp32 tensor load_image gives)"""
+        if path.endswith('.npy'):
+            return load_image(path)
+        from PIL import Image
+        with Image.open(path) as im:
+            return np.array(im.convert('RGB'), dtype=np.uint8)
+
+    def to_device(self, a, crop_to=None, path='image'):
+        """decoded image -> [1, 3, Hc, Wc] fp32 on the device; crop_to: the scale whose multiple the size is cut down to (modcrop), None: the whole image"""
+        H, W = a.shape[1:] if torch.is_tensor(a) else a.shape[:2]
+        Hc, Wc = modcrop_size(H, W, crop_to) if crop_to else (H, W)
+        if Hc < 1 or Wc < 1:
+            raise ValueError('{}: {} x {} is smaller than the scale {}'.format(path, H, W, crop_to))
+        if torch.is_tensor(a):
+            return a.to(self.device)[:, :Hc, :Wc].contiguous()[None]
+        u8 = torch.from_numpy(a).to(self.device)     # one byte per sample crosses to the device
+        out = torch.empty((1, 3, Hc, Wc), dtype=torch.float32, device=self.device)
+        _lib.check(_lib.lib().dasr_u8_to_planar(u8.data_ptr(), H, W, Hc, Wc, out.data_ptr(), _stream()), 'dasr_u8_to_planar')
+        return out
+
+    def _read(self, path, crop_to=None):
+        return self.to_device(self.decode(path), crop_to, path)
+
+    def _tables(self, n_in):
+        """device tap tables (int32 index, fp64 weight) of one axis, uploaded once per (n_in, scale)"""
+        t = self._taps.get(n_in)
+        if t is None:
+            j, w = bicubic_taps(n_in, 1.0 / self.scale)
+            t = (j.to(torch.int32).contiguous().to(self.device), w.contiguous().to(self.device))
+            self._taps[n_in] = t
+        return t
+
+    def downsample(self, img):
+        """[1, C, H, W] (or [C, H, W]) fp32 device image with H and W multiples of scale -> [1, C, H / scale, W / scale]: dasr_imresize_down"""
+        x = (img if img.dim() == 4 else img[None]).to(self.device, torch.float32).contiguous()
+        n, c, H, W = x.shape
+        s = self.scale
+        if n != 1:
+            raise ValueError('downsample takes one image, got a batch of %d' % n)
+        if s not in (2, 3, 4) or H % s or W % s:
+            raise NotImplementedError('LR images are made on the fly for scale 2, 3 or 4 and sizes that are multiples of it (got scale %d, %d x %d); provide LR files' % (s, H, W))
+        (jh, wh), (jw, ww) = self._tables(H), self._tables(W)
+        tmp = self._tmp.get((c, H, W))
+        if tmp is None:
+            self._tmp = {(c, H, W): torch.empty((c, H // s, W), dtype=torch.float64, device=self.device)}   # one shape at a time: a folder of mixed sizes does not pile them up
+            tmp = self._tmp[(c, H, W)]
+        out = torch.empty((1, c, H // s, W // s), dtype=torch.float32, device=self.device)
+        _lib.check(_lib.lib().dasr_imresize_down(x.data_ptr(), c, H, W, s, jh.data_ptr(), wh.data_ptr(), jw.data_ptr(), ww.data_ptr(), tmp.data_ptr(), out.data_ptr(),
+                                                 _stream()), 'dasr_imresize_down')
+        return out
+
+    def item(self, index):
+        if self.mode == 'LR':
+            return {'LR': self._read(self.paths_LR[index]), 'LR_path': [self.paths_LR[index]]}
+        s = self.scale
+        HR_path = self.paths_HR[index]
+        hr = self._read(HR_path, crop_to=s)
+        if self.paths_LR:
+            LR_path = self.paths_LR[index]
+            lr = self._read(LR_path)
+            if (lr.shape[2] * s, lr.shape[3] * s) != tuple(hr.shape[2:]):
+                raise ValueError('{} ({} x {} after the crop to a multiple of {}) is not {} x the size of {} ({} x {})'.format(
+                    HR_path, hr.shape[2], hr.shape[3], s, s, LR_path, lr.shape[2], lr.shape[3]))
+        else:
+            LR_path = HR_path            # LRHR_dataset.py:123-124
+            lr = self.downsample(hr)
+        return {'LR': lr, 'HR': hr, 'LR_path': [LR_path], 'HR_path': [HR_path]}
+
+    def __iter__(self):
+        for i in range(len(self)):
+            yield self.item(i)

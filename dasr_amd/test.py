@@ -5,8 +5,8 @@ For every dataset of the option file: feed_data -> test() -> get_current_visuals
 Y channel, per image and averaged (same log lines as the reference).  `device_metrics: true` quantises the images and evaluates the four numbers on the
 GPU (dasr_amd/metrics.py) instead of with the numpy helpers of dasr_amd/util.py; absent, the host path is unchanged.  `chop: true` runs the quadrant inference.  `val_lpips: true` adds the
 LPIPS(alex) distance of the 8-bit images (test.py:88-128; weights from `path.lpips_alexnet` / `path.lpips_lin`, seeded when absent).
-`save_RealorFake` needs the discriminator visual, not available here: NotImplementedError.  Datasets: `mode: "synthetic"` ships seeded LR/HR pairs; any iterable of the reference's batch dicts works
-through `main(loaders=...)`.
+`save_RealorFake` needs the discriminator visual, not available here: NotImplementedError.  Datasets: `mode: "LRHR"` (HR folder, LR folder or LR made by bicubic down-sampling) and `mode: "LR"` read image folders through data.EvalFolderDataset; `mode: "synthetic"` ships
+seeded LR/HR pairs; any iterable of the reference's batch dicts works through `main(loaders=...)`.
 """
 import argparse
 import logging

@@ -4,7 +4,8 @@ Same loop order as the reference: update_learning_rate -> feed_data -> optimize_
 logger.print_freq, checkpoint every logger.save_checkpoint_freq (model.save + save_training_state), final
 model.save('latest').  Data: the reference's cv2/lmdb datasets are CPU-side IO and out of the hot-path scope
 (SURVEY.md section 8, row 10); this driver accepts any iterable of batch dicts with the reference's keys and ships a
-synthetic dataset (`datasets.train.mode: "synthetic"`) used by the benchmark and the tests.  Under
+synthetic dataset (`datasets.train.mode: "synthetic"`) used by the benchmark and the tests; `datasets.val` may be a pair of image folders
+(`mode: "LRHR"`, data.EvalFolderDataset).  Under
 torch.distributed.run every rank takes its shard of each batch (dasr_amd.dist.shard_minibatch).
 """
 import argparse
@@ -85,6 +86,10 @@ def create_dataset(ds_opt, opt):
     if mode == 'LRHR' and ds_opt.get('phase', 'train') == 'train' and ds_opt.get('dataroot_LR'):
         from .data import DevicePairedDataset
         return DevicePairedDataset(ds_opt, opt['scale'])
+    if (mode == 'LRHR' and ds_opt.get('phase') in ('val', 'test')) or mode == 'LR':
+        # folders of image files in the val / test phase (data/__init__.py:29-32): decoded per item, converted / cropped / down-sampled by csrc/imgio.hip
+        from .data import EvalFolderDataset
+        return EvalFolderDataset(ds_opt, opt['scale'])
     raise NotImplementedError('Dataset [{:s}] is not recognized (the cv2/lmdb loaders of the reference stay on its side of '
                               'the boundary; feed their batch dicts to the trainer object).'.format(str(mode)))
 

@@ -539,6 +539,24 @@ int dasr_img_sse(const uint8_t* a, const uint8_t* b, int32_t N, int32_t C, int32
 int dasr_img_ssim(const uint8_t* a, const uint8_t* b, int32_t N, int32_t C, int32_t H, int32_t W, int32_t crop, int32_t y_channel, double* ssim,
                   void* ws, int64_t ws_size, void* stream);
 
+/* ---- input stage of the evaluation datasets (csrc/imgio.hip) ---------------------------------------------------------------------
+ * What data.EvalFolderDataset runs per image file in place of the host's read_img / modcrop / imresize_np (codes/SRN/data/util.py:78-96, :133-145,
+ * :243-433).  Plain vector loads and stores, no atomics, asynchronous on `stream`.
+ *
+ * dasr_u8_to_planar: src = a decoded image, uint8 [H][W][3] (interleaved, any channel order); dst = its top-left Hc x Wc window as planar fp32
+ * [3][Hc][Wc], dst[c][y][x] = (float)src[y][x][c] / 255.0f with the correctly rounded fp32 division -- bit for bit numpy's
+ * `asarray(img, float32) / 255.0` followed by modcrop (Hc = H - H % scale, Wc = W - W % scale).  Hc > H, Wc > W, a side over 65535: DASR_EINVAL.
+ *
+ * dasr_imresize_down: src planar fp32 [C][H][W] -> dst [C][H / s][W / s], MATLAB's imresize(., 1 / s) (bicubic, antialiased) for s in {2, 3, 4}.
+ * The caller supplies the per-axis tap tables of data.bicubic_taps(n, 1 / s): idx_* [n / s][4 s + 2] int32 (0-based source index, already mirrored
+ * into [0, n)), w_* [n / s][4 s + 2] fp64 (normalised per output sample), in device memory; the same pair may serve both axes when H == W.
+ * Pass 1 (along H) writes tmp (device, C * (H / s) * W doubles); pass 2 (along W) reads it.  Products and sums are fp64, in tap order, the products
+ * rounded before they are added; the result is rounded to fp32 once.  Same inputs, same bits.  H or W not a multiple of s, s outside {2, 3, 4},
+ * a null pointer, a side or C over 65535: DASR_EINVAL, nothing is launched. */
+int dasr_u8_to_planar(const uint8_t* src, int32_t H, int32_t W, int32_t Hc, int32_t Wc, float* dst, void* stream);
+int dasr_imresize_down(const float* src, int32_t C, int32_t H, int32_t W, int32_t s, const int32_t* idx_h, const double* w_h, const int32_t* idx_w,
+                       const double* w_w, double* tmp, float* dst, void* stream);
+
 /* ---- profiling session (bench.py `roofline`) -----------------------------------------------------------
  * Between dasr_prof_begin and dasr_prof_end every kernel launch of the library (up to `capacity`) carries its own start/stop
  * events on its launch stream (hipExtLaunchKernel: the dispatch's begin/end timestamps, what rocprofv3 --kernel-trace prints).
