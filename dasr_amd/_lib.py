@@ -61,6 +61,11 @@ class CropDesc(C.Structure):
     _fields_ = [('src', c_vp), ('C', c_i32), ('H', c_i32), ('W', c_i32), ('vH', c_i32), ('vW', c_i32), ('y0', c_i32), ('x0', c_i32), ('flags', c_i32)]
 
 
+class CropU8Desc(C.Structure):
+    """dasr_crop_u8_desc"""
+    _fields_ = [('src', c_vp), ('H', c_i32), ('W', c_i32), ('y0', c_i32), ('x0', c_i32), ('crop', c_i32), ('flags', c_i32), ('sub_y', c_i32), ('sub_x', c_i32)]
+
+
 class Op(C.Structure):
     """dasr_op: one recorded launch.  OP_CONV carries a ConvParams; every other kind passes its arguments in the untyped slots i / f / l / p / t,
     laid out by OP_ARGS (build with make_op, read and patch with get / set)."""
@@ -281,6 +286,8 @@ _SIGS = {
     'dasr_img_ssim': [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp],
     'dasr_u8_to_planar': [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp],
     'dasr_imresize_down': [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    'dasr_gather_crops_u8': [c_vp, c_i32, c_i32, c_vp, c_vp],
+    'dasr_crops_bicubic_down': [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp],
     'dasr_prof_begin': [c_i32],
     'dasr_prof_end': [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp],
 }

@@ -3,7 +3,11 @@
 //  * u8_to_planar: the decoded image as PIL hands it over (uint8, HWC, RGB) -> the top-left Hc x Wc window (modcrop) as planar fp32 in [0, 1]
 //  * imresize_down: MATLAB-style antialiased bicubic down-sampling by an integer s, as two gather passes over per-axis tap tables (index and fp64 weight,
 //    4 s + 2 taps per output sample) the host builds once per (length, s): rows first into an fp64 intermediate, then columns, ONE rounding to fp32 at the end
-// Both are memory-bound (about 36 multiply-adds per output sample at s = 4 against 2 x 18 gathered reads), so the kernels are plain: one thread per output
+//  * gather_crops_u8 / crops_bicubic_down: batch assembly of the DSN trainer on resident 8-bit images (reference: codes/DSN/data_loader.py:12-59, utils.py:37-160; host
+//    restatement: dasr_amd/dsn_data.py TrainDeresnetDataset).  The first cuts one transformed window per descriptor out of a decoded image and converts it, the second makes the
+//    clamped bicubic x1/4 image of every crop of the batch in ONE launch, both passes through LDS (no fp64 intermediate in device memory).  A batch is a few MB: both are
+//    bound by launch latency, so what counts is one launch per batch tensor and no host synchronisation, not bandwidth.
+// The first two are memory-bound (about 36 multiply-adds per output sample at s = 4 against 2 x 18 gathered reads), so the kernels are plain: one thread per output
 // sample, the x index on the lanes so that loads and stores of a wave are contiguous (pass 2 reads with a stride of s samples inside one row of the
 // intermediate, which the 18-tap overlap of neighbouring outputs keeps in cache), no LDS, no atomics.
 //
@@ -74,6 +78,75 @@ int imresize_launch(const float* src, int C, int H, int W, int s, const int32_t*
     return (int)hipGetLastError();
 }
 
+// one thread: one output pixel, three channels; ox on the lanes.  Output pixel (i, j) of the transformed crop (n = crop) comes from (k quarter-turns counter-clockwise undone
+// first, then the horizontal, then the vertical flip): k = 1: (j, n-1-i), k = 2: (n-1-i, n-1-j), k = 3: (n-1-j, i).  For k odd a wave walks down a column of the source.
+// Every source coordinate is clamped into the image: a damaged descriptor reads a wrong pixel, never outside the allocation.  grid (ceil(size^2 / 256), n)
+__global__ __launch_bounds__(256) void gather_crops_u8_kernel(const dasr_crop_u8_desc* __restrict__ descs, int size, float* __restrict__ dst) {
+    const int gi = blockIdx.x * 256 + threadIdx.x;
+    if (gi >= size * size) return;
+    const dasr_crop_u8_desc d = descs[blockIdx.y];
+    const int oy = gi / size, ox = gi - oy * size;
+    const int n1 = d.crop - 1, i = d.sub_y + oy, j = d.sub_x + ox, k = (d.flags >> 2) & 3;
+    int r = k == 0 ? i : k == 1 ? j : k == 2 ? n1 - i : n1 - j;
+    int c = k == 0 ? j : k == 1 ? n1 - i : k == 2 ? n1 - j : i;
+    if (d.flags & 2) c = n1 - c;
+    if (d.flags & 1) r = n1 - r;
+    const int y = min(max(d.y0 + r, 0), max(d.H - 1, 0)), x = min(max(d.x0 + c, 0), max(d.W - 1, 0));
+    const uint8_t* p = d.src + ((size_t)y * (size_t)max(d.W, 1) + x) * 3;
+    float* o = dst + (size_t)blockIdx.y * 3 * size * size + gi;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) o[(size_t)ch * size * size] = d.src ? (float)p[ch] / 255.0f : 0.f;   // (a descriptor left zeroed: a black sample, no access)
+}
+
+// Both passes of the x1/4 resize of one plane's tile of BD_ROWS output rows in one workgroup.  Output row oy takes the 18 input rows 4 oy - 7 .. 4 oy + 10 (mirrored at the ends), so
+// the tile needs the BD_IN = 4 BD_ROWS + 14 consecutive input rows from `base` on -- whole rows of a c-wide plane, ONE contiguous run of memory, staged with 16-byte loads.
+//   LDS: in [BD_IN][c] fp32, then mid [BD_ROWS][4][c / 4 + 8] fp64 = c x 152 + 1024 bytes: 39 KB at c = 256 (four workgroups per CU), 153 KB at the largest c = 1024.
+//   BD_ROWS = 4: a batch of 8 crops of 256 x 256 is 24 planes x 16 tiles = 384 workgroups for 256 CUs, and the staged rows overlap 30 / 16; 8 rows would halve the workgroups
+//   (192 < 256 CUs) and no longer fit c = 1024.  The tile only groups outputs: every output sample is the same sequence of operations for any tile.
+//   mid is stored de-interleaved by x mod 4 (row r, column x at [r][x & 3][x >> 2]): the column pass reads x = 4 ox - 7 + t, consecutive doubles over the lanes for a fixed tap.
+// Arithmetic as in the two-pass kernels above: fp64 products and sums in tap order, the row-pass result kept in fp64, clamped in fp64 (a NaN stays a NaN), one rounding to fp32.
+constexpr int BD_ROWS = 4, BD_TAPS = 18, BD_IN = 4 * BD_ROWS + 14;
+__global__ __launch_bounds__(256) void crops_bicubic_down_kernel(const float* __restrict__ hr, int c, int tiles, const int32_t* __restrict__ idx, const double* __restrict__ wt,
+                                                                 float* __restrict__ dst) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int co = c >> 2, qs = co + 8;
+    const int nin = min(BD_IN, c);
+    float* in = (float*)smem;
+    double* mid = (double*)(smem + (size_t)BD_IN * c * sizeof(float));
+    const int plane = blockIdx.x / tiles, oy0 = (blockIdx.x - plane * tiles) * BD_ROWS;
+    const int base = min(max(4 * oy0 - 7, 0), c - nin);
+    const float4* src = (const float4*)(hr + ((size_t)plane * c + base) * c);
+    for (int e = threadIdx.x; e < nin * co; e += 256) ((float4*)in)[e] = src[e];
+    __syncthreads();
+    const int rows = min(BD_ROWS, co - oy0);
+    for (int e = threadIdx.x; e < rows * c; e += 256) {
+        const int r = e / c, x = e - r * c;
+        const int32_t* ji = idx + (size_t)(oy0 + r) * BD_TAPS;
+        const double* jw = wt + (size_t)(oy0 + r) * BD_TAPS;
+        double acc = 0.0;
+#pragma unroll
+        for (int t = 0; t < BD_TAPS; ++t) {
+            const int j = min(max(ji[t] - base, 0), nin - 1);   // (a damaged table reads a wrong staged row, never outside the tile)
+            acc += jw[t] * (double)in[j * c + x];
+        }
+        mid[(r * 4 + (x & 3)) * qs + (x >> 2)] = acc;
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < rows * co; e += 256) {
+        const int r = e / co, ox = e - r * co;
+        const int32_t* ji = idx + (size_t)ox * BD_TAPS;
+        const double* jw = wt + (size_t)ox * BD_TAPS;
+        double acc = 0.0;
+#pragma unroll
+        for (int t = 0; t < BD_TAPS; ++t) {
+            const int j = min(max(ji[t], 0), c - 1);
+            acc += jw[t] * mid[(r * 4 + (j & 3)) * qs + (j >> 2)];
+        }
+        acc = acc < 0.0 ? 0.0 : acc > 1.0 ? 1.0 : acc;
+        dst[((size_t)plane * co + oy0 + r) * co + ox] = (float)acc;
+    }
+}
+
 }  // namespace
 
 extern "C" int dasr_u8_to_planar(const uint8_t* src, int32_t H, int32_t W, int32_t Hc, int32_t Wc, float* dst, void* stream) {
@@ -90,4 +163,20 @@ extern "C" int dasr_imresize_down(const float* src, int32_t C, int32_t H, int32_
     return s == 2 ? imresize_launch<10>(src, C, H, W, s, idx_h, w_h, idx_w, w_w, tmp, dst, stream)
          : s == 3 ? imresize_launch<14>(src, C, H, W, s, idx_h, w_h, idx_w, w_w, tmp, dst, stream)
                   : imresize_launch<18>(src, C, H, W, s, idx_h, w_h, idx_w, w_w, tmp, dst, stream);
+}
+
+extern "C" int dasr_gather_crops_u8(const dasr_crop_u8_desc* descs_dev, int32_t n, int32_t size, float* dst, void* stream) {
+    if (!descs_dev || !dst || n <= 0 || n > 65535 || size <= 0 || size > 4096) return DASR_EINVAL;
+    DASR_LAUNCH(gather_crops_u8_kernel, dim3((unsigned)((size * size + 255) / 256), (unsigned)n), dim3(256), 0, as_stream(stream), descs_dev, size, dst);
+    return (int)hipGetLastError();
+}
+
+extern "C" int dasr_crops_bicubic_down(const float* hr, int32_t n, int32_t c, int32_t s, const int32_t* idx, const double* wt, float* dst, void* stream) {
+    if (!hr || !idx || !wt || !dst || n <= 0 || n > 65535 || s != 4 || c < 4 || c > 1024 || c % 4 || ((uintptr_t)hr & 15)) return DASR_EINVAL;
+    const int tiles = (c / 4 + BD_ROWS - 1) / BD_ROWS;
+    const size_t lds = (size_t)BD_IN * c * sizeof(float) + (size_t)BD_ROWS * 4 * (c / 4 + 8) * sizeof(double);
+    // per call: the attribute belongs to the current device, and the call is cheap next to a launch.  The largest c: 1024 x 152 + 1024 bytes of the 160 KB of a CU
+    HIP_TRY(hipFuncSetAttribute((const void*)crops_bicubic_down_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BD_IN * 1024 * 4 + BD_ROWS * 4 * (256 + 8) * 8));
+    DASR_LAUNCH(crops_bicubic_down_kernel, dim3((unsigned)(3 * n * tiles)), dim3(256), lds, as_stream(stream), hr, (int)c, tiles, idx, wt, dst);
+    return (int)hipGetLastError();
 }

@@ -11,7 +11,15 @@ CHW float tensors in [0, 1] (`to_tensor` semantics); flips / crops / quarter-tur
 reference's transforms draw from torch's and python's global generators: the crops are random either way, no stream is reproduced).  `imresize`
 is evaluated as two dense resampling matrices (rows = output pixels, symmetric boundary folded into the columns) instead of the reference's
 per-row loops: same weights, same result up to fp32 summation order (tests/test_dsn_data.py pins it against vectors of the reference function).
+
+`--device_data` (DeviceTrainDeresnet, DeviceValDeresnet, DeviceDeresnetLoader): the same batches assembled on the GPU.  Every file is decoded ONCE and its
+bytes stay resident in device memory; per item the host only draws the random numbers (`plan_item`, the calls of the host datasets in their order, so equal
+seeds give equal batches) and a batch is one descriptor upload and three launches of csrc/imgio.hip (clean crops, source crops, the bicubic image), with no
+host synchronisation.  hr and real are bit-equal to the host path, bicubic is the fp64 evaluation rounded once (within one fp32 unit of it, and of the host's image within that
+plus the host's own fp32 error).
 """
+import collections
+import ctypes
 import math
 import os
 import random
@@ -214,17 +222,264 @@ def load_paths(path):
         return yaml.safe_load(f)
 
 
-def make_datasets(o, paths):
-    """train.py:84-115: the four `Train_Deresnet_Dataset` branches.  camerasr takes its target folder from aim2019 (train.py:110)"""
+def _dataset_folders(o, paths):
+    """(folders of the dataset's paths.yml entry, its target folder): camerasr takes its target folder from aim2019 (train.py:110)"""
     ds = o.dataset
     if ds not in DERESNET_DATASETS:
         raise NotImplementedError("dataset [%s]: the reference's training loop unpacks (hr, bicubic, real) triples, which only its aim2019 / ntire2020 / "
                                   "realsr / camerasr branches provide (train.py:84-115, 204); built in here: those four and 'synthetic'" % ds)
     src = paths[ds][o.artifacts]
-    target = paths['aim2019'][o.artifacts]['target'] if ds == 'camerasr' else src['target']
+    return src, paths['aim2019'][o.artifacts]['target'] if ds == 'camerasr' else src['target']
+
+
+def make_datasets(o, paths):
+    """train.py:84-115: the four `Train_Deresnet_Dataset` branches"""
+    src, target = _dataset_folders(o, paths)
     kw = dict(crop_size=o.crop_size, upscale_factor=o.upscale_factor, flips=o.flips, rotations=o.rotations)
     train_set = TrainDeresnetDataset(src['source'], target, cropped=True, **kw)
     val_set = ValDeresnetDataset(src['valid_hr'], o.upscale_factor, lr_dir=src['valid_lr'], crop_size_val=o.crop_size_val)
+    return train_set, val_set
+
+
+# ---- --device_data: the same datasets on images resident in device memory -------------------------------------------------------------
+MAX_DECODE_THREADS = 16
+
+# one window of a resident image as dasr_gather_crops_u8 cuts it: `image` uint8 [H, W, 3]; the crop x crop window at (y0, x0), flipped vertically (flags bit 0),
+# then horizontally (bit 1), then turned by k = bits 2-3 quarter-turns (torch.rot90(., k, (1, 2))); of that the size x size window at (sub_y, sub_x)
+CropPlan = collections.namedtuple('CropPlan', 'image y0 x0 crop flags sub_y sub_x size')
+
+
+def _plan_window(h, w, crop, flips, rotations):
+    """(y0, x0, flags) of one augmented crop, drawn like load_augmented_crop draws them"""
+    y, x = random.randint(0, h - crop), random.randint(0, w - crop)
+    vflip = flips and random.random() < 0.5
+    hflip = flips and random.random() < 0.5
+    k = random.choice([0, 1, 2, 3]) if rotations else 0
+    return y, x, int(vflip) | (int(hflip) << 1) | (k << 2)
+
+
+def _image_size(path):
+    """(H, W) from the file header, without decoding"""
+    from PIL import Image
+    with Image.open(path) as im:
+        w, h = im.size
+    return h, w
+
+
+def _decode_u8(path):
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.array(im.convert('RGB'), dtype=np.uint8)
+
+
+def _device_of(device):
+    """the device the images live on (None: the current GPU); 'cpu' touches no GPU"""
+    if device is not None and torch.device(device).type == 'cpu':
+        return torch.device('cpu')
+    from .engine import ensure_runtime_ready
+    ensure_runtime_ready()
+    dev = torch.device('cuda') if device is None else torch.device(device)
+    return dev if dev.index is not None else torch.device('cuda', torch.cuda.current_device())
+
+
+def load_resident(file_lists, device=None, threads=6, max_bytes=None, min_size=0):
+    """the files of every list decoded once (PIL, RGB, uint8 [H, W, 3]) on a pool of at most 16 threads and uploaded to `device`: (the device, lists of uint8 tensors).
+    The sizes are read from the file headers and summed BEFORE anything is decoded or the device is touched: an image with a side under `min_size` is a
+    ValueError naming the file, a total of H W 3 bytes above `max_bytes` (default: half of the device memory free right now) a MemoryError.  Nothing spills
+    to the host.  (The default cap is taken per call: a validation set loaded after its train set is held to half of what the train set left free.)
+    device 'cpu' keeps the bytes in host memory: enough for plan_item, not for assembling batches."""
+    from concurrent.futures import ThreadPoolExecutor
+    total = 0
+    for files in file_lists:
+        for path in files:
+            h, w = _image_size(path)
+            if h < min_size or w < min_size:
+                raise ValueError('%s: image %dx%d is smaller than the crop size %d' % (path, h, w, min_size))
+            total += h * w * 3
+
+    def refuse(cap):
+        raise MemoryError('the decoded images take %d bytes, above the cap of %d bytes for images resident in device memory: train with the host loader '
+                          '(without --device_data) or raise max_bytes' % (total, cap))
+    if max_bytes is not None and total > max_bytes:
+        refuse(max_bytes)
+    dev = _device_of(device)
+    if max_bytes is None and dev.type == 'cuda' and total > torch.cuda.mem_get_info(dev)[0] // 2:
+        refuse(torch.cuda.mem_get_info(dev)[0] // 2)
+    threads = max(1, min(MAX_DECODE_THREADS, int(threads)))
+    out = []
+    with ThreadPoolExecutor(max_workers=threads) as pool:
+        for files in file_lists:
+            imgs = []
+            for k in range(0, len(files), 4 * threads):   # (decoded arrays wait in host memory one chunk at a time)
+                imgs += [torch.from_numpy(a).to(dev) for a in pool.map(_decode_u8, files[k:k + 4 * threads])]
+            out.append(imgs)
+    return dev, out
+
+
+def _tap_table(c, s, device):
+    """device tap table of dasr_crops_bicubic_down for crops of side c: (int32 index, fp64 weight), both [c / s, 4 s + 2]"""
+    from .data import bicubic_taps
+    j, w = bicubic_taps(c, 1.0 / s)
+    return j.to(torch.int32).contiguous().to(device), w.contiguous().to(device)
+
+
+def _gather_u8(plan_groups, device):
+    """one output tensor [n, 3, size, size] per group of CropPlans (equal `size` inside a group): ALL descriptors in one host-to-device copy from pinned
+    memory, one dasr_gather_crops_u8 launch per group, no host synchronisation"""
+    from . import _lib
+    from .engine import _stream
+    if device.type != 'cuda':
+        raise _lib.DasrHipError('batches are assembled by HIP kernels on images resident in device memory; this dataset was built on %s' % device)
+    plans = [p for g in plan_groups for p in g]
+    descs = (_lib.CropU8Desc * len(plans))()
+    for d, p in zip(descs, plans):
+        H, W = p.image.shape[:2]
+        if not (0 <= p.y0 and p.y0 + p.crop <= H and 0 <= p.x0 and p.x0 + p.crop <= W and 0 <= p.sub_y and p.sub_y + p.size <= p.crop
+                and 0 <= p.sub_x and p.sub_x + p.size <= p.crop and p.image.device == device and p.image.dtype == torch.uint8 and p.image.is_contiguous()):
+            raise ValueError('crop descriptor outside its image: %r of %d x %d' % (p[1:], H, W))
+        d.src, d.H, d.W, d.y0, d.x0, d.crop, d.flags, d.sub_y, d.sub_x = p.image.data_ptr(), H, W, p.y0, p.x0, p.crop, p.flags, p.sub_y, p.sub_x
+    staging = torch.empty(ctypes.sizeof(descs), dtype=torch.uint8, pin_memory=True)   # (torch's pinned-memory cache hands a block out again only after the copy below is done)
+    ctypes.memmove(staging.data_ptr(), descs, ctypes.sizeof(descs))
+    dd = staging.to(device, non_blocking=True)
+    L, out, k = _lib.lib(), [], 0
+    for g in plan_groups:
+        size = g[0].size
+        dst = torch.empty((len(g), 3, size, size), dtype=torch.float32, device=device)
+        _lib.check(L.dasr_gather_crops_u8(dd.data_ptr() + k * ctypes.sizeof(_lib.CropU8Desc), len(g), size, dst.data_ptr(), _stream()), 'dasr_gather_crops_u8')
+        out.append(dst)
+        k += len(g)
+    return out
+
+
+def _check_bicubic_side(c, upscale_factor, what):
+    """what dasr_crops_bicubic_down covers, asked before anything is decoded"""
+    if int(upscale_factor) != 4 or c % 4 or c > 1024:
+        raise NotImplementedError('%s: the bicubic image is made on the device for upscale_factor 4 and crops whose side is a multiple of 4 up to 1024 '
+                                  '(got factor %d, side %d); use the host loader' % (what, upscale_factor, c))
+
+
+class _BicubicDown:
+    """dasr_crops_bicubic_down with its tap tables, one per crop side, built and uploaded on first use"""
+
+    def __init__(self, upscale_factor, device):
+        self.s, self.device, self._tables = int(upscale_factor), device, {}
+
+    def __call__(self, hr):
+        from . import _lib
+        from .engine import _stream
+        n, _, c, _ = hr.shape
+        _check_bicubic_side(c, self.s, 'crops of side %d' % c)
+        if c not in self._tables:
+            self._tables[c] = _tap_table(c, self.s, self.device)
+        j, w = self._tables[c]
+        out = torch.empty((n, 3, c // self.s, c // self.s), dtype=torch.float32, device=self.device)
+        _lib.check(_lib.lib().dasr_crops_bicubic_down(hr.data_ptr(), n, c, self.s, j.data_ptr(), w.data_ptr(), out.data_ptr(), _stream()), 'dasr_crops_bicubic_down')
+        return out
+
+
+class DeviceTrainDeresnet:
+    """TrainDeresnetDataset(cropped=True) on images resident in device memory: the same file lists, the same random draws, batches made by `batch`
+    (hr [n,3,c,c], bicubic [n,3,c/up,c/up], real [n,3,c/up,c/up] on the device).  See load_resident for `threads` and `max_bytes`."""
+
+    def __init__(self, noisy_dir, cleandir, crop_size, upscale_factor=4, flips=False, rotations=False, device=None, threads=6, max_bytes=None):
+        self.noisy_dir_files = _list_images(noisy_dir)
+        self.cleandir_files = _list_images(cleandir)
+        if not self.noisy_dir_files or not self.cleandir_files:
+            raise FileNotFoundError('no image files under %s / %s' % (noisy_dir, cleandir))
+        self.crop_size, self.upscale_factor = int(crop_size), int(upscale_factor)
+        self.flips, self.rotations = bool(flips), bool(rotations)
+        _check_bicubic_side(self.crop_size, self.upscale_factor, '--crop_size %d' % self.crop_size)
+        self.device, (self.noisy, self.clean) = load_resident([self.noisy_dir_files, self.cleandir_files], device, threads, max_bytes, min_size=self.crop_size)
+        self._down = _BicubicDown(self.upscale_factor, self.device)
+
+    def __len__(self):
+        return len(self.noisy)
+
+    def plan_item(self, index):
+        """(source-domain CropPlan, clean CropPlan) of item `index`: host only; consumes np.random and random exactly like TrainDeresnetDataset.__getitem__"""
+        c, small = self.crop_size, self.crop_size // self.upscale_factor
+        clean = self.clean[np.random.randint(0, len(self.clean))]
+        noisy = self.noisy[index]
+        ny, nx, nflags = _plan_window(noisy.shape[0], noisy.shape[1], c, self.flips, self.rotations)
+        cy, cx, cflags = _plan_window(clean.shape[0], clean.shape[1], c, self.flips, self.rotations)
+        sy, sx = random.randint(0, c - small), random.randint(0, c - small)
+        return CropPlan(noisy, ny, nx, c, nflags, sy, sx, small), CropPlan(clean, cy, cx, c, cflags, 0, 0, c)
+
+    def batch(self, indices):
+        plans = [self.plan_item(i) for i in indices]
+        hr, real = _gather_u8([[p[1] for p in plans], [p[0] for p in plans]], self.device)
+        return hr, self._down(hr), real
+
+
+class DeviceValDeresnet:
+    """ValDeresnetDataset on images resident in device memory: item -> (HR centre crop, its bicubic image, random LR crop, centre LR crop), the same
+    draws (random.randint y, x of the random LR crop).  Iterating gives batches of one ([1,3,..] tensors), what make_loader(val_set, 1, False) yields."""
+
+    def __init__(self, hr_dir, upscale_factor, lr_dir=None, crop_size_val=None, device=None, threads=6, max_bytes=None):
+        self.hr_files = sorted(_list_images(hr_dir))
+        if lr_dir is None:
+            raise NotImplementedError('Val_Deresnet_Dataset without lr_dir returns an undefined name in the reference (data_loader.py:180-181)')
+        self.lr_files = sorted(_list_images(lr_dir))
+        self.upscale_factor, self.crop_size = int(upscale_factor), crop_size_val
+        for hr_path, lr_path in zip(self.hr_files, self.lr_files):   # every item's sizes, from the file headers: refused here, not at the first validation pass
+            cs = self._crop_side(*_image_size(hr_path))
+            _check_bicubic_side(cs, self.upscale_factor, hr_path)
+            h, w = _image_size(lr_path)
+            if h < cs // self.upscale_factor or w < cs // self.upscale_factor:
+                raise ValueError('%s: image %dx%d is smaller than the crop size %d' % (lr_path, h, w, cs // self.upscale_factor))
+        self.device, (self.hr, self.lr) = load_resident([self.hr_files, self.lr_files], device, threads, max_bytes)
+        self._down = _BicubicDown(self.upscale_factor, self.device)
+
+    def _crop_side(self, h, w):
+        cs = calculate_valid_crop_size(min(h, w), self.upscale_factor)
+        return cs if self.crop_size is None else min(cs, int(self.crop_size))
+
+    def __len__(self):
+        return len(self.hr)
+
+    def __getitem__(self, index):
+        def centre(img, size):   # center_crop
+            h, w = img.shape[:2]
+            if h < size or w < size:
+                raise ValueError('image %dx%d is smaller than the crop size %d' % (h, w, size))
+            return CropPlan(img, int(round((h - size) / 2.0)), int(round((w - size) / 2.0)), size, 0, 0, 0, size)
+        hr, lr = self.hr[index], self.lr[index]
+        cs = self._crop_side(hr.shape[0], hr.shape[1])
+        small = cs // self.upscale_factor
+        hr_plan = centre(hr, cs)
+        h, w = lr.shape[:2]
+        if h < small or w < small:
+            raise ValueError('image %dx%d is smaller than the crop size %d' % (h, w, small))
+        rnd = CropPlan(lr, random.randint(0, h - small), random.randint(0, w - small), small, 0, 0, 0, small)
+        hr_t, lr_t = _gather_u8([[hr_plan], [rnd, centre(lr, small)]], self.device)
+        return hr_t[0], self._down(hr_t)[0], lr_t[0], lr_t[1]
+
+    def __iter__(self):
+        for i in range(len(self)):
+            yield tuple(t[None] for t in self[i])
+
+
+class DeviceDeresnetLoader:
+    """batches of a DeviceTrainDeresnet in the order of `sampler` (a ShardSampler: a new permutation per epoch, the rank's strided share), batch_size items
+    each, the last batch of an epoch possibly short (drop_last=False): what make_loader yields, as device tensors"""
+
+    def __init__(self, dataset, batch_size, sampler):
+        self.dataset, self.batch_size, self.sampler = dataset, max(1, int(batch_size)), sampler
+
+    def __len__(self):
+        return (len(self.sampler) + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        order = list(self.sampler)
+        for k in range(0, len(order), self.batch_size):
+            yield self.dataset.batch(order[k:k + self.batch_size])
+
+
+def make_device_datasets(o, paths, device=None):
+    """make_datasets for --device_data; --num_workers is the number of decode threads"""
+    src, target = _dataset_folders(o, paths)
+    train_set = DeviceTrainDeresnet(src['source'], target, o.crop_size, o.upscale_factor, flips=o.flips, rotations=o.rotations, device=device, threads=o.num_workers)
+    val_set = DeviceValDeresnet(src['valid_hr'], o.upscale_factor, lr_dir=src['valid_lr'], crop_size_val=o.crop_size_val, device=device, threads=o.num_workers)
     return train_set, val_set
 
 

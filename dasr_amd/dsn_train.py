@@ -9,7 +9,8 @@ default) runs LPIPS(alex) with weights from --lpips_alexnet / --lpips_lin, --per
 downloaded offline, a missing file is an error unless --allow_random_perceptual opts into a seeded random network.  Data: `--dataset aim2019 |
 ntire2020 | realsr | camerasr` read the image folders `--paths` (the reference's codes/paths.yml, train.py:82-83) names for `--artifacts`, through
 dasr_amd.dsn_data (the reference's Train_/Val_Deresnet_Dataset on PIL tensors, no torchvision); any iterable of (hr, bicubic_lr, real_lr) tuples
-passed to main(loader=, val_loader=) works too, and `--dataset synthetic` ships fixed-seed random crops for benchmarks and tests.  Every
+passed to main(loader=, val_loader=) works too (`--device_data`: the folder datasets with every image resident in device memory and the batches assembled
+there, dsn_data.DeviceTrainDeresnet), and `--dataset synthetic` ships fixed-seed random crops for benchmarks and tests.  Every
 `val_interval` epochs the validation pass of train.py:293-355 runs over the paired validation folders (mse, psnr, rgb / mean / perceptual / colour
 errors as `val/*` scalars), every `val_img_interval` epochs it also writes the `val/target_fake_crop_low_high_<i>` image strips.
 """
@@ -73,6 +74,8 @@ def build_parser():
     p.add_argument('--lpips_lin', default=None, type=str, help="the reference's codes/PerceptualSimilarity/models/weights/v0.1/alex.pth")
     p.add_argument('--allow_random_perceptual', action='store_true',
                    help='run the perceptual term on a SEEDED RANDOM network when the pretrained weight files are not supplied (the reference always uses pretrained weights)')
+    p.add_argument('--device_data', action='store_true',
+                   help='folder datasets: decode every image once, keep the bytes in device memory and assemble the batches there (--num_workers: decode threads)')
     return p
 
 
@@ -82,6 +85,9 @@ def check_supported(o, have_loader=True):
     if not have_loader and o.dataset != 'synthetic' and o.dataset not in DERESNET_DATASETS:
         raise NotImplementedError("dataset [%s]: built in are aim2019 / ntire2020 / realsr / camerasr (image folders from --paths, the reference's "
                                   "Train_Deresnet_Dataset branches) and 'synthetic'; or pass a loader of (hr, bicubic_lr, real_lr) batches to main()" % o.dataset)
+    if o.device_data and (have_loader or o.dataset == 'synthetic'):
+        raise ValueError("--device_data assembles the batches of the image-folder datasets (aim2019 / ntire2020 / realsr / camerasr) on the device; "
+                         "it has no meaning with %s" % ('a loader passed to main()' if have_loader else "--dataset synthetic"))
     if o.generator not in ('DeResnet', 'DSGAN'):
         raise NotImplementedError('Generator model [{:s}] not recognized'.format(o.generator))
     if o.discriminator.lower() not in ('fsd', 'nld_s1', 'nld_s2'):
@@ -178,6 +184,12 @@ def main(argv=None, loader=None, val_loader=None):
         log.info('Continuing training at epoch %d' % start_epoch)
     if loader is None and o.dataset == 'synthetic':
         loader = SyntheticCrops(o.batch_size // world, o.crop_size, o.iters_per_epoch, seed=1234 + rank)
+    elif loader is None and o.device_data:   # the same folders, resident in device memory (every rank keeps the whole set: the permutation changes per epoch)
+        from . import dsn_data
+        train_set, val_set = dsn_data.make_device_datasets(o, dsn_data.load_paths(o.paths), device=model.device)
+        loader = dsn_data.DeviceDeresnetLoader(train_set, o.batch_size // world, dsn_data.ShardSampler(len(train_set), True, 0, rank, world))
+        if val_loader is None:
+            val_loader = val_set
     elif loader is None:   # train.py:81-115: image folders from paths.yml
         from . import dsn_data
         train_set, val_set = dsn_data.make_datasets(o, dsn_data.load_paths(o.paths))

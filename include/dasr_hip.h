@@ -557,6 +557,32 @@ int dasr_u8_to_planar(const uint8_t* src, int32_t H, int32_t W, int32_t Hc, int3
 int dasr_imresize_down(const float* src, int32_t C, int32_t H, int32_t W, int32_t s, const int32_t* idx_h, const double* w_h, const int32_t* idx_w,
                        const double* w_w, double* tmp, float* dst, void* stream);
 
+/* ---- batch assembly of the DSN trainer on resident 8-bit images (csrc/imgio.hip) ---------------------------------------------------
+ * What dsn_data.DeviceTrainDeresnet / DeviceValDeresnet run per batch in place of the host's decode, crop, flips, rotation, to_tensor and imresize
+ * (codes/DSN/data_loader.py:12-59, :157-190, utils.py:37-160).  Asynchronous on `stream`, nothing is synchronised, same inputs give the same bits.
+ *
+ * dasr_gather_crops_u8: sample k of dst [n][3][size][size] fp32 = the size x size window at (sub_y, sub_x) of the TRANSFORMED crop x crop window at (y0, x0) of
+ * image `src` (uint8 [H][W][3], as PIL decodes it): vertical flip (flags bit 0), then horizontal flip (bit 1), then k = bits 2-3 quarter-turns counter-clockwise
+ * (torch.rot90(., k, (1, 2))), in that order; every sample is (float)byte / 255.0f, the correctly rounded fp32 division.  The clean crop has size == crop and
+ * sub_y == sub_x == 0, the source-domain crop size == crop / 4.  The descriptors are device memory and are not validated: the caller guarantees
+ * y0 + crop <= H, x0 + crop <= W, sub + size <= crop; the kernel clamps every source coordinate into the image, so a damaged descriptor reads a wrong pixel
+ * and never outside the allocation.  A null pointer, n <= 0, n > 65535, size <= 0, size > 4096: DASR_EINVAL, nothing is launched.
+ *
+ * dasr_crops_bicubic_down: hr [n][3][c][c] fp32 -> dst [n][3][c / s][c / s], MATLAB's imresize(., 1 / s) (bicubic, antialiased), rows first, then columns,
+ * clamped to [0, 1], for the whole batch in one launch and without an intermediate in device memory.  idx / wt [c / s][4 s + 2]: the tap table of
+ * data.bicubic_taps(c, 1 / s) (int32 0-based source index mirrored into [0, c), fp64 weight), one table for both axes and all 3 n planes.  fp64 products and
+ * sums in tap order, the clamp in fp64, one rounding to fp32.  s != 4, c not a multiple of 4 in [4, 1024], n <= 0, n > 65535, a null pointer, hr not 16-byte
+ * aligned: DASR_EINVAL, nothing is launched. */
+typedef struct {
+    const uint8_t* src;
+    int32_t H, W;           /* source image */
+    int32_t y0, x0, crop;   /* crop x crop window of the source */
+    int32_t flags;          /* bit 0 vertical flip, bit 1 horizontal flip, bits 2-3 quarter-turns */
+    int32_t sub_y, sub_x;   /* origin of the size x size output window inside the transformed crop */
+} dasr_crop_u8_desc;
+int dasr_gather_crops_u8(const dasr_crop_u8_desc* descs_dev, int32_t n, int32_t size, float* dst, void* stream);
+int dasr_crops_bicubic_down(const float* hr, int32_t n, int32_t c, int32_t s, const int32_t* idx, const double* wt, float* dst, void* stream);
+
 /* ---- profiling session (bench.py `roofline`) -----------------------------------------------------------
  * Between dasr_prof_begin and dasr_prof_end every kernel launch of the library (up to `capacity`) carries its own start/stop
  * events on its launch stream (hipExtLaunchKernel: the dispatch's begin/end timestamps, what rocprofv3 --kernel-trace prints).
