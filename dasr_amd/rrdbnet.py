@@ -16,6 +16,8 @@ from .engine import (BTensor, ParamStore, PackRegistry, OpList, WgradGroup, Wgra
 from ._lib import Op, Tensor, make_op
 
 GC = 32  # growth channels are hard-wired to 32 in the reference (architecture.py:183)
+# sub-pixel form of nearest-x2 + 3x3: output parity -> source taps (along one axis) of packed tap a = 0, 1 (RRDBNetHIP._register_tail_packs)
+_SUBPIXEL_ROWS = {0: ((0,), (1, 2)), 1: ((0, 1), (2,))}
 
 
 def rrdbnet_param_spec(in_nc, out_nc, nf, nb, upsample_mode='upconv'):
@@ -129,7 +131,7 @@ class RRDBNetHIP:
         # (i, i+1) with (w0+w1, w2); same along x.  The data gradient is the transpose: per parity a 2x2 conv of that parity's
         # sub-grid of the output gradient with the tap order reversed, summed over the four parities.
         self.subpixel = not self.hr_f16s   # f32-tensor tail (DASR_HR_PREC=3): the upconvs run in their sub-pixel form
-        rows = {0: ((0,), (1, 2)), 1: ((0, 1), (2,))}   # parity -> source taps of packed tap a = 0, 1
+        rows = _SUBPIXEL_ROWS   # parity -> source taps of packed tap a = 0, 1
         for name, key in (() if self.hr_f16s else (('up1', 'model.3.weight'), ('up2', 'model.6.weight'))):
             for py in (0, 1):
                 for px in (0, 1):

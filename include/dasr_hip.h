@@ -41,6 +41,11 @@ typedef struct {
  * with `mask` = forward activation (LeakyReLU'/ReLU').
  *   v = acc + bias[oc]; if act: v = v>0 ? v : slope*v; if mask.p: v *= (mask>0 ? 1 : slope)
  *   v = alpha*v + beta1*res1 + beta2*res2;  out_f32 = v;  out_bf16 = bf16(gamma*v)
+ * Corners (held by tests/test_gpu_conv.py): the mask test is `mask > 0`, so +0 and -0 both take `slope`.  Whole 16-channel planes are written up to
+ * ceil(cout/16): the padding channels of the last plane are written as exact zeros whatever bias, mask, res1 and res2 hold at those channels (they
+ * are read, never used); input padding channels must hold zeros.  With out_stride = 2 only the addressed parity of the output tensor is written.
+ * The conv5-class launches of the LDS-DMA kernel (64 output channels per workgroup, res1 given) evaluate alpha*((beta1/alpha)*res1 + acc): the same
+ * value to fp32 rounding, alpha must not be 0 there.
  */
 typedef struct {
     dasr_tensor in;  int32_t in_f32;  int32_t Hin, Win;  int32_t ups;  int32_t cin; /* cin % 16 == 0 */
