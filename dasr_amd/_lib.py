@@ -66,6 +66,11 @@ class CropU8Desc(C.Structure):
     _fields_ = [('src', c_vp), ('H', c_i32), ('W', c_i32), ('y0', c_i32), ('x0', c_i32), ('crop', c_i32), ('flags', c_i32), ('sub_y', c_i32), ('sub_x', c_i32)]
 
 
+class SrnU8Desc(C.Structure):
+    """dasr_srn_u8_desc"""
+    _fields_ = [('src', c_vp), ('H', c_i32), ('W', c_i32), ('y0', c_i32), ('x0', c_i32), ('size', c_i32), ('flags', c_i32), ('dst', c_vp)]
+
+
 class Op(C.Structure):
     """dasr_op: one recorded launch.  OP_CONV carries a ConvParams; every other kind passes its arguments in the untyped slots i / f / l / p / t,
     laid out by OP_ARGS (build with make_op, read and patch with get / set)."""
@@ -288,6 +293,8 @@ _SIGS = {
     'dasr_imresize_down': [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     'dasr_gather_crops_u8': [c_vp, c_i32, c_i32, c_vp, c_vp],
     'dasr_crops_bicubic_down': [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp],
+    'dasr_gather_srn_u8': [c_vp, c_i32, c_i32, c_vp],
+    'dasr_crops_down4_u8': [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp],
     'dasr_prof_begin': [c_i32],
     'dasr_prof_end': [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp],
 }

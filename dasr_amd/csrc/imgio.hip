@@ -7,6 +7,9 @@
 //    restatement: dasr_amd/dsn_data.py TrainDeresnetDataset).  The first cuts one transformed window per descriptor out of a decoded image and converts it, the second makes the
 //    clamped bicubic x1/4 image of every crop of the batch in ONE launch, both passes through LDS (no fp64 intermediate in device memory).  A batch is a few MB: both are
 //    bound by launch latency, so what counts is one launch per batch tensor and no host synchronisation, not bandwidth.
+//  * gather_srn_u8 / crops_down4_u8: batch assembly of the SRN trainers on resident 8-bit images (`"resident_u8": true`; reference: codes/SRN/data/LRHR_dataset.py:44-126,
+//    LRHR_wavelet_unpairEq_fake_w_dataset.py:50-166, data/util.py:116-128 augment; host side: dasr_amd/data.py).  The first writes every 3-channel tensor of a batch in one launch
+//    (per-descriptor window size and destination), the second the augmented LR crops of an HR-only set: samples of the x1/4 image of the WHOLE image, made where a crop needs them.
 // The first two are memory-bound (about 36 multiply-adds per output sample at s = 4 against 2 x 18 gathered reads), so the kernels are plain: one thread per output
 // sample, the x index on the lanes so that loads and stores of a wave are contiguous (pass 2 reads with a stride of s samples inside one row of the
 // intermediate, which the 18-tap overlap of neighbouring outputs keeps in cache), no LDS, no atomics.
@@ -147,6 +150,89 @@ __global__ __launch_bounds__(256) void crops_bicubic_down_kernel(const float* __
     }
 }
 
+// One launch for every 3-channel tensor of an SRN batch: descriptor blockIdx.y, one thread per output pixel (three channels), ox on the lanes.  The descriptors of one launch
+// have different sizes (LR and HR windows): the grid covers max_size^2 pixels and a smaller window masks the rest.  Output pixel (y, x) comes from window pixel (ci, cj):
+// the transpose was applied last, so it is undone first, then the vertical, then the horizontal flip (gather_crops_kernel of misc.hip).  For a transposed window a wave
+// walks down a column of the source.  Every source coordinate is clamped into the image.  grid (ceil(max_size^2 / 256), n)
+__global__ __launch_bounds__(256) void gather_srn_u8_kernel(const dasr_srn_u8_desc* __restrict__ descs, int max_size) {
+    const dasr_srn_u8_desc d = descs[blockIdx.y];
+    const int size = min(d.size, max_size);
+    const int gi = blockIdx.x * 256 + threadIdx.x;
+    if (!d.src || !d.dst || size <= 0 || gi >= size * size) return;   // (a descriptor left zeroed: nothing is read or written)
+    const int y = gi / size, x = gi - y * size;
+    int ci = y, cj = x;
+    if (d.flags & 4) { ci = x; cj = y; }
+    if (d.flags & 2) ci = size - 1 - ci;
+    if (d.flags & 1) cj = size - 1 - cj;
+    const int sy = min(max(d.y0 + ci, 0), max(d.H - 1, 0)), sx = min(max(d.x0 + cj, 0), max(d.W - 1, 0));
+    const uint8_t* p = d.src + ((size_t)sy * (size_t)max(d.W, 1) + sx) * 3;
+    float* o = d.dst + gi;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) o[(size_t)ch * size * size] = (float)p[ch] / 255.0f;
+}
+
+// The x1/4 image of the WHOLE 8-bit image, evaluated only where a crop needs it.  One workgroup: a D4_T x D4_T tile (before the flips) of the LR window of one descriptor,
+// the three channels one after the other.
+//   win: the D4_IN x D4_IN x 3 byte window of the image the tile's taps reach (rows 4 (y0 + oy0) - 7 on, columns likewise), loaded ONCE with the mirroring at the image's
+//        borders folded into the load -- the passes index it without a test.  The mirror is bicubic_taps': j < 0 -> -j - 1, then j >= n -> 2 n - 1 - j, then a clamp.
+//   lut: (double)((float)b / 255.0f) of the 256 byte values: the one correctly rounded fp32 division of dasr_u8_to_planar, made once per workgroup instead of once per tap.
+//   mid: the row pass of one channel, [D4_T][D4_IN] fp64, column x of row r at [r][x & 3][x >> 2] so that the column pass reads consecutive doubles over the lanes.
+//   LDS: 78 x 78 x 3 + 2 KB + 16 x 4 x 20 x 8 = 18256 + 2048 + 10240 = 30544 bytes: five workgroups on a CU (a 32 x 32 tile would need 60 KB for the bytes alone).
+// Arithmetic: that of imresize_rows_kernel / imresize_cols_kernel on the planar fp32 image: fp64 products and sums in tap order from 0.0, the row result kept in fp64, NO
+// clamp, one rounding to fp32.  The 18 weights are kernel arguments (the same for every output sample at scale 1 / 4).  grid (tiles^2, n), tiles = ceil(size / D4_T)
+constexpr int D4_T = 16, D4_TAPS = 18, D4_IN = 4 * D4_T + 14, D4_Q = D4_IN / 4 + 1;
+struct d4_weights { double w[D4_TAPS]; };
+
+__device__ __forceinline__ int d4_mirror(int j, int n) {
+    if (j < 0) j = -j - 1;
+    if (j >= n) j = 2 * n - 1 - j;
+    return min(max(j, 0), n - 1);
+}
+
+__global__ __launch_bounds__(256) void crops_down4_u8_kernel(const dasr_srn_u8_desc* __restrict__ descs, int size, int tiles, d4_weights wt) {
+    __shared__ __attribute__((aligned(16))) uint8_t win[(D4_IN * D4_IN * 3 + 15) / 16 * 16];
+    __shared__ double lut[256];
+    __shared__ double mid[D4_T * 4 * D4_Q];
+    const dasr_srn_u8_desc d = descs[blockIdx.y];
+    if (!d.src || !d.dst || d.H < 1 || d.W < 1) return;   // (uniform over the workgroup: in front of every barrier)
+    const int ty = blockIdx.x / tiles, oy0 = ty * D4_T, ox0 = (blockIdx.x - ty * tiles) * D4_T;
+    const int rows = min(D4_T, size - oy0), cols = min(D4_T, size - ox0);
+    const int nin_y = 4 * rows + 14, nin_x = 4 * cols + 14;
+    const int base_y = 4 * (d.y0 + oy0) - 7, base_x = 4 * (d.x0 + ox0) - 7;
+    lut[threadIdx.x] = (double)((float)threadIdx.x / 255.0f);
+    for (int e = threadIdx.x; e < nin_y * nin_x; e += 256) {
+        const int r = e / nin_x, x = e - r * nin_x;
+        const uint8_t* p = d.src + ((size_t)d4_mirror(base_y + r, d.H) * (size_t)d.W + d4_mirror(base_x + x, d.W)) * 3;
+        uint8_t* q = win + (r * D4_IN + x) * 3;
+        q[0] = p[0]; q[1] = p[1]; q[2] = p[2];
+    }
+    __syncthreads();
+    for (int ch = 0; ch < 3; ++ch) {
+        for (int e = threadIdx.x; e < rows * nin_x; e += 256) {
+            const int r = e / nin_x, x = e - r * nin_x;
+            double acc = 0.0;
+#pragma unroll
+            for (int t = 0; t < D4_TAPS; ++t) acc += wt.w[t] * lut[win[((4 * r + t) * D4_IN + x) * 3 + ch]];
+            mid[(r * 4 + (x & 3)) * D4_Q + (x >> 2)] = acc;
+        }
+        __syncthreads();
+        for (int e = threadIdx.x; e < rows * cols; e += 256) {
+            const int r = e / cols, ox = e - r * cols;
+            double acc = 0.0;
+#pragma unroll
+            for (int t = 0; t < D4_TAPS; ++t) {
+                const int x = 4 * ox + t;
+                acc += wt.w[t] * mid[(r * 4 + (x & 3)) * D4_Q + (x >> 2)];
+            }
+            const int ci = oy0 + r, cj = ox0 + ox;                 // position in the window before the flips -> position in the augmented crop
+            const int a = (d.flags & 2) ? size - 1 - ci : ci, b = (d.flags & 1) ? size - 1 - cj : cj;
+            const int y = (d.flags & 4) ? b : a, x = (d.flags & 4) ? a : b;
+            d.dst[((size_t)ch * size + y) * size + x] = (float)acc;
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace
 
 extern "C" int dasr_u8_to_planar(const uint8_t* src, int32_t H, int32_t W, int32_t Hc, int32_t Wc, float* dst, void* stream) {
@@ -178,5 +264,25 @@ extern "C" int dasr_crops_bicubic_down(const float* hr, int32_t n, int32_t c, in
     // per call: the attribute belongs to the current device, and the call is cheap next to a launch.  The largest c: 1024 x 152 + 1024 bytes of the 160 KB of a CU
     HIP_TRY(hipFuncSetAttribute((const void*)crops_bicubic_down_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BD_IN * 1024 * 4 + BD_ROWS * 4 * (256 + 8) * 8));
     DASR_LAUNCH(crops_bicubic_down_kernel, dim3((unsigned)(3 * n * tiles)), dim3(256), lds, as_stream(stream), hr, (int)c, tiles, idx, wt, dst);
+    return (int)hipGetLastError();
+}
+
+extern "C" int dasr_gather_srn_u8(const dasr_srn_u8_desc* descs_dev, int32_t n, int32_t max_size, void* stream) {
+    if (!descs_dev || n <= 0 || n > 65535 || max_size <= 0 || max_size > 4096) return DASR_EINVAL;
+    DASR_LAUNCH(gather_srn_u8_kernel, dim3((unsigned)((max_size * max_size + 255) / 256), (unsigned)n), dim3(256), 0, as_stream(stream), descs_dev, (int)max_size);
+    return (int)hipGetLastError();
+}
+
+extern "C" int dasr_crops_down4_u8(const dasr_srn_u8_desc* descs_dev, const dasr_srn_u8_desc* descs_host, int32_t n, int32_t size, const double* w18, void* stream) {
+    if (!descs_dev || !descs_host || !w18 || n <= 0 || n > 65535 || size <= 0 || size > 128) return DASR_EINVAL;
+    for (int k = 0; k < n; ++k) {
+        const dasr_srn_u8_desc& d = descs_host[k];
+        if (!d.src || !d.dst || d.H <= 0 || d.W <= 0 || d.H % 4 || d.W % 4 || d.size != size) return DASR_EINVAL;
+        if (d.y0 < 0 || d.x0 < 0 || d.y0 > d.H / 4 - size || d.x0 > d.W / 4 - size) return DASR_EINVAL;
+    }
+    d4_weights wt;
+    for (int t = 0; t < D4_TAPS; ++t) wt.w[t] = w18[t];
+    const int tiles = (size + D4_T - 1) / D4_T;
+    DASR_LAUNCH(crops_down4_u8_kernel, dim3((unsigned)(tiles * tiles), (unsigned)n), dim3(256), 0, as_stream(stream), descs_dev, (int)size, tiles, wt);
     return (int)hipGetLastError();
 }

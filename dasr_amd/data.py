@@ -7,10 +7,18 @@ uploaded ONCE as a CHW fp32 RGB tensor; a batch is n descriptors (image, crop or
 launches that write the five batch tensors of the reference's dict directly in HBM.  Random draws are made on the host in the
 reference's order (np.random for the unpaired indices, `random` for the crop origins and the three augmentation coins), so with
 equal seeds and num_workers=0 the batches coincide.  Image decoding (PIL) stays on the host and happens once per file.
+
+`"resident_u8": true` in `datasets.train` (both training datasets): the files are decoded once on `n_workers` threads (dsn_data.load_resident) and stay in device
+memory as the BYTES PIL decodes (uint8 [H][W][3], a quarter of the fp32 store); the domain-distance maps stay fp32.  A batch is one descriptor block in pinned memory,
+one asynchronous upload and at most three launches: dasr_gather_srn_u8 (every 3-channel tensor of the batch), dasr_gather_crops (fake_w) and, for `mode: "LRHR"` without
+LR files, dasr_crops_down4_u8 (the LR crops, straight from the HR bytes).  The random draws are the same calls in the same order, so equal seeds give equal batches with
+and without the key: bit for bit, except the LR images made on the device (one rounding to fp32 of the fp64 evaluation: within 2^-23 of imresize_matlab).
 """
 import ctypes as C
+import logging
 import os
 import random
+import time
 
 import numpy as np
 import torch
@@ -41,27 +49,131 @@ def load_image(path):
     return torch.from_numpy(a).permute(2, 0, 1).contiguous()
 
 
+def _hw(t):
+    """(H, W) of a stored image: planar fp32 [C, H, W], or the decoded bytes [H, W, 3] of `resident_u8`"""
+    return (t.shape[0], t.shape[1]) if t.dtype == torch.uint8 else (t.shape[1], t.shape[2])
+
+
+def _u8_header(path):
+    """(H, W) of an image file that can be stored as the bytes PIL decodes, from its header; ValueError naming the file otherwise"""
+    if path.endswith('.npy'):
+        raise ValueError('%s: a .npy file in an image folder cannot be kept as 8-bit samples; drop "resident_u8" or convert the file' % path)
+    from PIL import Image
+    with Image.open(path) as im:
+        if im.mode != 'RGB':
+            raise ValueError("%s: mode '%s' (grey, palette or alpha), which convert('RGB') would have to change; \"resident_u8\" takes 8-bit RGB files only" % (path, im.mode))
+        w, h = im.size
+    return h, w
+
+
+def load_resident_u8(lists, ds_opt, device=None, max_bytes=None, t0=None):
+    """`resident_u8` store: lists {name: [paths]} -> (device, {name: [uint8 [H, W, 3] tensors]}), decoded once on `n_workers` threads (16 at most) by
+    dsn_data.load_resident.  Cap: max_bytes, else `resident_max_bytes` of the options, else half of the device memory free right now; over it: MemoryError.  Logs once
+    (logger 'base') the number of files, the bytes resident on this rank (every rank holds the whole set) and the construction time since t0."""
+    from .dsn_data import load_resident
+    t0 = time.perf_counter() if t0 is None else t0
+    cap = max_bytes if max_bytes is not None else ds_opt.get('resident_max_bytes')
+    dev, out = load_resident(list(lists.values()), device, threads=ds_opt.get('n_workers') or 1, max_bytes=cap,
+                             remedy='drop "resident_u8" from datasets.train')
+    if dev.type == 'cuda':
+        torch.cuda.synchronize(dev)
+    nbytes = sum(t.numel() for imgs in out for t in imgs)
+    logging.getLogger('base').info('resident_u8 [{}]: {:d} files, {:,d} bytes resident in device memory on this rank, built in {:.2f} s'.format(
+        ds_opt.get('name'), sum(len(v) for v in out), nbytes, time.perf_counter() - t0))
+    return dev, dict(zip(lists, out)), nbytes
+
+
+_W18 = None
+
+
+def down4_weights():
+    """the 18 weights of MATLAB's antialiased bicubic at scale 1 / 4 as a ctypes array: ONE row of bicubic_taps(n, 0.25)[1] -- the sample positions u = 4 k - 1.5 have the
+    same fractional part for every k, so every output sample has bit-equal weights (tests/test_srn_device_data_host.py)"""
+    global _W18
+    if _W18 is None:
+        _W18 = (C.c_double * 18)(*bicubic_taps(32, 0.25)[1][0].tolist())
+    return _W18
+
+
+def assemble_u8(device, gather, ddm=None, down=None):
+    """the launches of one `resident_u8` batch.  gather / down: lists of (uint8 image [H, W, 3], y0, x0, size, flags, destination [3, size, size] fp32 view) for
+    dasr_gather_srn_u8 / dasr_crops_down4_u8 (for `down` the window is given in the x1/4 image); ddm: (CropDesc array, channels, size, destination) for dasr_gather_crops.
+    ALL descriptors go into one block of pinned memory and cross in one asynchronous copy; no host synchronisation.  Returns the device block (kept by the caller)."""
+    if device.type != 'cuda':
+        raise _lib.DasrHipError('batches are assembled by HIP kernels on images resident in device memory; this dataset was built on %s' % device)
+    n_g, n_d = len(gather), len(down or ())
+    descs = (_lib.SrnU8Desc * (n_g + n_d))()
+    for k, (img, y0, x0, size, flags, dst) in enumerate(list(gather) + list(down or ())):
+        H, W = img.shape[:2]
+        Hv, Wv = (H, W) if k < n_g else (H // 4, W // 4)
+        if not (0 <= y0 and y0 + size <= Hv and 0 <= x0 and x0 + size <= Wv and img.device == device and img.dtype == torch.uint8 and img.is_contiguous()
+                and tuple(dst.shape) == (3, size, size) and dst.is_contiguous()):
+            raise ValueError('crop descriptor outside its image: window %r of %d x %d' % ((y0, x0, size), Hv, Wv))
+        d = descs[k]
+        d.src, d.H, d.W, d.y0, d.x0, d.size, d.flags, d.dst = img.data_ptr(), H, W, y0, x0, size, flags, dst.data_ptr()
+    sz = C.sizeof(_lib.SrnU8Desc)
+    off_w = C.sizeof(descs)
+    total = off_w + (C.sizeof(ddm[0]) if ddm else 0)
+    staging = torch.empty(total, dtype=torch.uint8, pin_memory=True)   # (torch's pinned-memory cache hands a block out again only after the copy below is done)
+    C.memmove(staging.data_ptr(), descs, off_w)
+    if ddm:
+        C.memmove(staging.data_ptr() + off_w, ddm[0], C.sizeof(ddm[0]))
+    dd = staging.to(device, non_blocking=True)
+    L = _lib.lib()
+    if n_g:
+        _lib.check(L.dasr_gather_srn_u8(dd.data_ptr(), n_g, max(g[3] for g in gather), _stream()), 'dasr_gather_srn_u8')
+    if ddm:
+        _lib.check(L.dasr_gather_crops(dd.data_ptr() + off_w, len(ddm[0]), ddm[1], ddm[2], ddm[3].data_ptr(), _stream()), 'gather_crops')
+    if n_d:
+        _lib.check(L.dasr_crops_down4_u8(dd.data_ptr() + n_g * sz, staging.data_ptr() + n_g * sz, n_d, down[0][3], C.addressof(down4_weights()), _stream()),
+                   'dasr_crops_down4_u8')
+    return dd
+
+
 class DeviceUnpairedDataset:
     """Iterable of batch dicts {'LR_fake','LR_real','HR','HR_unpair','fake_w'} (CUDA tensors) built on the device.
 
     images: dict with lists of CHW fp32 tensors 'fake_LR', 'real_LR', 'HR' and 'fake_w' ([1,h',w'] domain-distance maps, any size)
     -- or None to read `dataroot_*` folders of `ds_opt` (PNG / .npy files)."""
 
-    def __init__(self, ds_opt, scale=4, images=None, device=None, shuffle=None, drop_last=True):
-        ensure_runtime_ready()
+    def __init__(self, ds_opt, scale=4, images=None, device=None, shuffle=None, drop_last=True, max_bytes=None):
         self.opt, self.scale = ds_opt, scale
-        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         self.n = int(ds_opt['batch_size'])
         self.hr_size = int(ds_opt['HR_size'])
         self.use_flip, self.use_rot = bool(ds_opt.get('use_flip')), bool(ds_opt.get('use_rot'))
         self.shuffle = bool(ds_opt.get('use_shuffle')) if shuffle is None else shuffle
-        if images is None:
-            images = {k: [load_image(p) for p in image_paths(ds_opt[r])] for k, r in
-                      (('fake_LR', 'dataroot_fake_LR'), ('real_LR', 'dataroot_real_LR'), ('HR', 'dataroot_HR'), ('fake_w', 'dataroot_fake_weights'))}
-        self.img = {k: [t.to(self.device, torch.float32).contiguous() for t in v] for k, v in images.items()}
+        self.resident = bool(ds_opt.get('resident_u8'))
+        folders = (('fake_LR', 'dataroot_fake_LR'), ('real_LR', 'dataroot_real_LR'), ('HR', 'dataroot_HR'), ('fake_w', 'dataroot_fake_weights'))
+        if self.resident:
+            self._load_u8(folders, images, device, max_bytes)
+        else:
+            ensure_runtime_ready()
+            self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+            if images is None:
+                images = {k: [load_image(p) for p in image_paths(ds_opt[r])] for k, r in folders}
+            self.img = {k: [t.to(self.device, torch.float32).contiguous() for t in v] for k, v in images.items()}
         assert self.img['HR'], 'Error: HR path is empty.'
         assert len(self.img['fake_LR']) == len(self.img['HR']) == len(self.img['fake_w'])
         self.drop_last = drop_last
+
+    def _load_u8(self, folders, images, device, max_bytes):
+        """the `resident_u8` store: the three image folders as bytes, the domain-distance maps as fp32 (dasr_gather_crops resizes them bilinearly).  The u8 kernel clamps
+        a window that leaves its image where the fp32 one writes zeros, so files smaller than their window are refused here."""
+        t0 = time.perf_counter()
+        if images is not None:
+            raise ValueError('images=: "resident_u8" reads the dataroot_* folders itself (decoded bytes); pass images without the key')
+        s, HRs = self.scale, self.hr_size
+        lists = {k: image_paths(self.opt[r]) for k, r in folders[:3]}
+        sizes = {k: [_u8_header(p) for p in v] for k, v in lists.items()}
+        for k, least in (('fake_LR', HRs // s), ('real_LR', HRs // s), ('HR', HRs)):
+            for p, (h, w) in zip(lists[k], sizes[k]):
+                if h < least or w < least:
+                    raise ValueError('%s: image %dx%d is smaller than the crop size %d' % (p, h, w, least))
+        for p, (h, w), (hl, wl) in zip(lists['HR'], sizes['HR'], sizes['fake_LR']):
+            if h < s * hl or w < s * wl:
+                raise ValueError('%s: %dx%d is smaller than %d x its LR image (%dx%d)' % (p, h, w, s, hl, wl))
+        self.device, self.img, self.resident_bytes = load_resident_u8(lists, self.opt, device, max_bytes, t0)
+        self.img['fake_w'] = [load_image(p).to(self.device, torch.float32).contiguous() for p in image_paths(self.opt[folders[3][1]])]
 
     def __len__(self):
         m = len(self.img['fake_LR'])
@@ -75,11 +187,11 @@ class DeviceUnpairedDataset:
         index_unpair = np.random.randint(0, len(self.img['HR']))
         lf, lr_, hr, hu, fw = (self.img['fake_LR'][index], self.img['real_LR'][index_real], self.img['HR'][index], self.img['HR'][index_unpair],
                                self.img['fake_w'][index])
-        H, W = lf.shape[1:]
-        Hr, Wr = lr_.shape[1:]
+        H, W = _hw(lf)
+        Hr, Wr = _hw(lr_)
         y_f, x_f = random.randint(0, max(0, H - LRs)), random.randint(0, max(0, W - LRs))
         y_r, x_r = random.randint(0, max(0, Hr - LRs)), random.randint(0, max(0, Wr - LRs))
-        Hu, Wu = hu.shape[1:]
+        Hu, Wu = _hw(hu)
         y_u, x_u = random.randint(0, max(0, Hu - HRs)), random.randint(0, max(0, Wu - HRs))
         hflip = self.use_flip and random.random() < 0.5
         vflip = self.use_rot and random.random() < 0.5
@@ -88,8 +200,24 @@ class DeviceUnpairedDataset:
         return {'LR_fake': (lf, None, y_f, x_f), 'LR_real': (lr_, None, y_r, x_r), 'HR': (hr, None, y_f * s, x_f * s), 'HR_unpair': (hu, None, y_u, x_u),
                 'fake_w': (fw, (H, W), y_f, x_f), 'flags': flags}
 
+    def _batch_u8(self, samples):
+        n, LRs, HRs = len(samples), self.hr_size // self.scale, self.hr_size
+        out = {key: torch.empty((n, 1 if key == 'fake_w' else 3, size, size), dtype=torch.float32, device=self.device)
+               for key, size in (('LR_fake', LRs), ('LR_real', LRs), ('HR', HRs), ('HR_unpair', HRs), ('fake_w', LRs))}
+        gather = [(smp[key][0], smp[key][2], smp[key][3], out[key].shape[2], smp['flags'], out[key][k])
+                  for key in ('LR_fake', 'LR_real', 'HR', 'HR_unpair') for k, smp in enumerate(samples)]
+        descs = (_lib.CropDesc * n)()
+        for d, smp in zip(descs, samples):
+            t, virt, y0, x0 = smp['fake_w']
+            d.src, d.C, d.H, d.W = t.data_ptr(), t.shape[0], t.shape[1], t.shape[2]
+            d.vH, d.vW, d.y0, d.x0, d.flags = virt[0], virt[1], y0, x0, smp['flags']
+        out['_keep'] = [assemble_u8(self.device, gather, ddm=(descs, 1, LRs, out['fake_w']))]
+        return out
+
     def batch(self, indices):
         samples = [self.sample(i) for i in indices]
+        if self.resident:
+            return self._batch_u8(samples)
         out = {}
         L = _lib.lib()
         for key, size in (('LR_fake', self.hr_size // self.scale), ('LR_real', self.hr_size // self.scale), ('HR', self.hr_size), ('HR_unpair', self.hr_size),
@@ -169,46 +297,118 @@ class DevicePairedDataset:
     phase does the same per sample with random_scale_list = [1] (LRHR_dataset.py:63-88) whenever the HR size is a multiple of `scale` -- the case taken here; other sizes
     go through cv2.resize(INTER_LINEAR) there first, and an HR image smaller than HR_size is resized: both stay on the reference's side (NotImplementedError)."""
 
-    def __init__(self, ds_opt, scale=4, images=None, device=None, shuffle=None, drop_last=True):
-        ensure_runtime_ready()
+    def __init__(self, ds_opt, scale=4, images=None, device=None, shuffle=None, drop_last=True, max_bytes=None):
         self.opt, self.scale = ds_opt, scale
-        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         self.n, self.hr_size = int(ds_opt['batch_size']), int(ds_opt['HR_size'])
         self.use_flip, self.use_rot = bool(ds_opt.get('use_flip')), bool(ds_opt.get('use_rot'))
         self.shuffle = bool(ds_opt.get('use_shuffle')) if shuffle is None else shuffle
-        if images is None:
-            hr = [load_image(p) for p in image_paths(ds_opt['dataroot_HR'])]
-            images = {'HR': hr, 'LR': [load_image(p) for p in image_paths(ds_opt['dataroot_LR'])] if ds_opt.get('dataroot_LR') else None}
-        if images.get('LR') is None:   # down-sampling on the fly (LRHR_dataset.py:63-88)
-            for t in images['HR']:
-                if t.shape[1] % scale or t.shape[2] % scale:
-                    raise NotImplementedError('LRHR without dataroot_LR: HR image of %d x %d is not a multiple of scale %d (the reference resizes it with cv2 first); '
-                                              'crop the HR images or provide LR files' % (t.shape[1], t.shape[2], scale))
-            images = dict(images, LR=[imresize_matlab(t.float().cpu(), 1.0 / scale) for t in images['HR']])
-        self.img = {k: [t.to(self.device, torch.float32).contiguous() for t in v] for k, v in images.items()}
+        self.resident = bool(ds_opt.get('resident_u8'))
+        if self.resident:
+            self._load_u8(images, device, max_bytes)
+        else:
+            paths_HR = self.hr_paths(ds_opt) if images is None else None
+            ensure_runtime_ready()
+            self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+            if images is None:
+                hr = [load_image(p) for p in paths_HR]
+                images = {'HR': hr, 'LR': [load_image(p) for p in image_paths(ds_opt['dataroot_LR'])] if ds_opt.get('dataroot_LR') else None}
+            if images.get('LR') is None:   # down-sampling on the fly (LRHR_dataset.py:63-88)
+                for t in images['HR']:
+                    self._check_multiple(t.shape[1], t.shape[2])
+                images = dict(images, LR=[imresize_matlab(t.float().cpu(), 1.0 / scale) for t in images['HR']])
+            self.img = {k: [t.to(self.device, torch.float32).contiguous() for t in v] for k, v in images.items()}
         assert self.img['HR'], 'Error: HR path is empty.'
-        assert len(self.img['LR']) == len(self.img['HR']), 'HR and LR datasets have different number of images - {}, {}.'.format(
-            len(self.img['LR']), len(self.img['HR']))
+        if self.img['LR'] is not None:
+            assert len(self.img['LR']) == len(self.img['HR']), 'HR and LR datasets have different number of images - {}, {}.'.format(
+                len(self.img['LR']), len(self.img['HR']))
         self.drop_last = drop_last
+
+    @staticmethod
+    def hr_paths(ds_opt):
+        """the HR files: the folder, or the names `subset_file` lists under it (LRHR_dataset.py:26-31: train phase, and only when the LR images are made on the fly)"""
+        if ds_opt.get('subset_file') is not None and ds_opt.get('phase', 'train') == 'train':
+            with open(ds_opt['subset_file']) as f:
+                paths = sorted([os.path.join(ds_opt['dataroot_HR'], line.rstrip('\n')) for line in f])
+            if ds_opt.get('dataroot_LR') is not None:
+                raise NotImplementedError('Now subset only supports generating LR on-the-fly.')
+            return paths
+        return image_paths(ds_opt['dataroot_HR'])
+
+    def _check_multiple(self, H, W):
+        if H % self.scale or W % self.scale:
+            raise NotImplementedError('LRHR without dataroot_LR: HR image of %d x %d is not a multiple of scale %d (the reference resizes it with cv2 first); '
+                                      'crop the HR images or provide LR files' % (H, W, self.scale))
+
+    def _load_u8(self, images, device, max_bytes):
+        """the `resident_u8` store: HR (and LR, when there is a folder of them) as bytes.  Without LR files nothing is made at construction: dasr_crops_down4_u8 makes
+        the LR crops per batch from the HR bytes (img['LR'] is None)."""
+        t0 = time.perf_counter()
+        if images is not None:
+            raise ValueError('images=: "resident_u8" reads the dataroot_* folders itself (decoded bytes); pass images without the key')
+        s, HRs = self.scale, self.hr_size
+        lists = {'HR': self.hr_paths(self.opt)}
+        if self.opt.get('dataroot_LR'):
+            lists['LR'] = image_paths(self.opt['dataroot_LR'])
+        elif s != 4 or HRs // s > 128:
+            raise NotImplementedError('"resident_u8" without dataroot_LR: the LR crops are made on the device for scale 4 and LR crops up to 128 x 128 (got scale %d, '
+                                      'HR_size %d); provide LR files or drop "resident_u8"' % (s, HRs))
+        sizes = {k: [_u8_header(p) for p in v] for k, v in lists.items()}
+        if 'LR' in lists:
+            for (p, (h, w)), ph, (hh, wh) in zip(zip(lists['LR'], sizes['LR']), lists['HR'], sizes['HR']):
+                if h < HRs // s or w < HRs // s:
+                    raise ValueError('%s: image %dx%d is smaller than the crop size %d' % (p, h, w, HRs // s))
+                if hh < s * h or wh < s * w:
+                    raise ValueError('%s: %dx%d is smaller than %d x its LR image (%dx%d)' % (ph, hh, wh, s, h, w))
+        else:
+            for h, w in sizes['HR']:
+                self._check_multiple(h, w)
+        self.device, self.img, self.resident_bytes = load_resident_u8(lists, self.opt, device, max_bytes, t0)
+        self.img.setdefault('LR', None)
 
     def __len__(self):
         m = len(self.img['HR'])
         return m // self.n if self.drop_last else (m + self.n - 1) // self.n
 
+    def _draw(self, idx):
+        """(y0, x0, flags) of sample idx: the crop origin in the LR image, then util.augment's three coins"""
+        s, HRs = self.scale, self.hr_size
+        LRs = HRs // s
+        Hh, Wh = _hw(self.img['HR'][idx])
+        if Hh < HRs or Wh < HRs:
+            raise NotImplementedError('HR image smaller than HR_size (the reference resizes it and re-derives LR by imresize on the host)')
+        Hl, Wl = _hw(self.img['LR'][idx]) if self.img['LR'] is not None else (Hh // s, Wh // s)
+        y0, x0 = random.randint(0, max(0, Hl - LRs)), random.randint(0, max(0, Wl - LRs))
+        hflip = self.use_flip and random.random() < 0.5
+        vflip = self.use_rot and random.random() < 0.5
+        rot90 = self.use_rot and random.random() < 0.5
+        return y0, x0, int(hflip) | (int(vflip) << 1) | (int(rot90) << 2)
+
+    def _batch_u8(self, indices):
+        s, HRs = self.scale, self.hr_size
+        LRs, n = HRs // s, len(indices)
+        out = {'LR': torch.empty((n, 3, LRs, LRs), dtype=torch.float32, device=self.device),
+               'HR': torch.empty((n, 3, HRs, HRs), dtype=torch.float32, device=self.device)}
+        gather, lr_plans = [], []
+        for k, idx in enumerate(indices):
+            y0, x0, flags = self._draw(idx)
+            gather.append((self.img['HR'][idx], y0 * s, x0 * s, HRs, flags, out['HR'][k]))
+            lr_plans.append((self.img['LR'][idx] if self.img['LR'] is not None else self.img['HR'][idx], y0, x0, LRs, flags, out['LR'][k]))
+        if self.img['LR'] is not None:
+            out['_keep'] = [assemble_u8(self.device, lr_plans + gather)]
+        else:
+            out['_keep'] = [assemble_u8(self.device, gather, down=lr_plans)]
+        return out
+
     def batch(self, indices):
+        if self.resident:
+            return self._batch_u8(indices)
         s, HRs = self.scale, self.hr_size
         LRs = HRs // s
         L = _lib.lib()
         descs = {'LR': (_lib.CropDesc * len(indices))(), 'HR': (_lib.CropDesc * len(indices))()}
         for k, idx in enumerate(indices):
             lr, hr = self.img['LR'][idx], self.img['HR'][idx]
-            if hr.shape[1] < HRs or hr.shape[2] < HRs:
-                raise NotImplementedError('HR image smaller than HR_size (the reference resizes it and re-derives LR by imresize on the host)')
-            y0, x0 = random.randint(0, max(0, lr.shape[1] - LRs)), random.randint(0, max(0, lr.shape[2] - LRs))
-            hflip = self.use_flip and random.random() < 0.5
-            vflip = self.use_rot and random.random() < 0.5
-            rot90 = self.use_rot and random.random() < 0.5
-            flags = int(hflip) | (int(vflip) << 1) | (int(rot90) << 2)
+            y0, x0, flags = self._draw(idx)
             for key, t, yy, xx in (('LR', lr, y0, x0), ('HR', hr, y0 * s, x0 * s)):
                 d = descs[key][k]
                 d.src, d.C, d.H, d.W, d.vH, d.vW = t.data_ptr(), t.shape[0], t.shape[1], t.shape[2], t.shape[1], t.shape[2]

@@ -282,12 +282,12 @@ def _device_of(device):
     return dev if dev.index is not None else torch.device('cuda', torch.cuda.current_device())
 
 
-def load_resident(file_lists, device=None, threads=6, max_bytes=None, min_size=0):
+def load_resident(file_lists, device=None, threads=6, max_bytes=None, min_size=0, remedy='train with the host loader (without --device_data)'):
     """the files of every list decoded once (PIL, RGB, uint8 [H, W, 3]) on a pool of at most 16 threads and uploaded to `device`: (the device, lists of uint8 tensors).
     The sizes are read from the file headers and summed BEFORE anything is decoded or the device is touched: an image with a side under `min_size` is a
     ValueError naming the file, a total of H W 3 bytes above `max_bytes` (default: half of the device memory free right now) a MemoryError.  Nothing spills
     to the host.  (The default cap is taken per call: a validation set loaded after its train set is held to half of what the train set left free.)
-    device 'cpu' keeps the bytes in host memory: enough for plan_item, not for assembling batches."""
+    device 'cpu' keeps the bytes in host memory: enough for plan_item, not for assembling batches.  `remedy`: what the MemoryError tells the caller to do instead."""
     from concurrent.futures import ThreadPoolExecutor
     total = 0
     for files in file_lists:
@@ -298,8 +298,7 @@ def load_resident(file_lists, device=None, threads=6, max_bytes=None, min_size=0
             total += h * w * 3
 
     def refuse(cap):
-        raise MemoryError('the decoded images take %d bytes, above the cap of %d bytes for images resident in device memory: train with the host loader '
-                          '(without --device_data) or raise max_bytes' % (total, cap))
+        raise MemoryError('the decoded images take %d bytes, above the cap of %d bytes for images resident in device memory: %s or raise max_bytes' % (total, cap, remedy))
     if max_bytes is not None and total > max_bytes:
         refuse(max_bytes)
     dev = _device_of(device)

@@ -80,10 +80,11 @@ def create_dataset(ds_opt, opt):
             return SyntheticValDataset(ds_opt, opt['scale'])
         return SyntheticDataset(ds_opt, opt['scale'], opt['model'])
     if mode == 'LRHR_wavelet_unpair_fake_weights_EQ' and ds_opt.get('phase', 'train') == 'train':
-        # the DASR training set (data/__init__.py:35-36): images resident in HBM, batches assembled by dasr_gather_crops
+        # the DASR training set (data/__init__.py:35-36): images resident in HBM, batches assembled by dasr_gather_crops (`resident_u8`: as bytes, dasr_gather_srn_u8)
         from .data import DeviceUnpairedDataset
         return DeviceUnpairedDataset(ds_opt, opt['scale'])
-    if mode == 'LRHR' and ds_opt.get('phase', 'train') == 'train' and ds_opt.get('dataroot_LR'):
+    if mode == 'LRHR' and ds_opt.get('phase', 'train') == 'train' and (ds_opt.get('dataroot_LR') or ds_opt.get('resident_u8') or ds_opt.get('subset_file') is not None):
+        # without LR files the LR images are made from the HR images: per batch on the device under `resident_u8`, else once on the host (`subset_file` lists the HR files)
         from .data import DevicePairedDataset
         return DevicePairedDataset(ds_opt, opt['scale'])
     if (mode == 'LRHR' and ds_opt.get('phase') in ('val', 'test')) or mode == 'LR':

@@ -588,6 +588,36 @@ typedef struct {
 int dasr_gather_crops_u8(const dasr_crop_u8_desc* descs_dev, int32_t n, int32_t size, float* dst, void* stream);
 int dasr_crops_bicubic_down(const float* hr, int32_t n, int32_t c, int32_t s, const int32_t* idx, const double* wt, float* dst, void* stream);
 
+/* ---- batch assembly of the SRN trainers on resident 8-bit images (csrc/imgio.hip) ---------------------------------------------------
+ * What data.DeviceUnpairedDataset / DevicePairedDataset run per batch under `"resident_u8": true` (codes/SRN/data/LRHR_wavelet_unpairEq_fake_w_dataset.py:50-166,
+ * LRHR_dataset.py:44-126, data/util.py:116-128 augment).  Asynchronous on `stream`, nothing is synchronised, same inputs give the same bits.
+ *
+ * dasr_gather_srn_u8: ONE launch writes every 3-channel tensor of a batch.  Descriptor k: the size x size window at (y0, x0) of image `src` (uint8 [H][W][3], RGB, as
+ * PIL decodes it), then horizontal flip (flags bit 0), vertical flip (bit 1), transpose (bit 2), in that order -- dasr_crop_desc's flags -- written to `dst` as planar fp32
+ * [3][size][size]; every sample is (float)byte / 255.0f, the correctly rounded fp32 division.  The sizes of the descriptors of one launch may differ (LR and HR windows):
+ * the grid is sized by max_size, a descriptor with size > max_size is cut off at max_size^2 samples, smaller windows are masked.  A descriptor with a null src or
+ * dst or size <= 0 writes nothing.  The descriptors are device memory and are not validated: the caller guarantees y0 + size <= H, x0 + size <= W; the kernel clamps every
+ * source coordinate into the image, so a damaged descriptor reads a wrong pixel and never outside the image.  A null pointer, n <= 0, n > 65535, max_size <= 0,
+ * max_size > 4096: DASR_EINVAL, nothing is launched.
+ *
+ * dasr_crops_down4_u8: the augmented LR crops of `mode: "LRHR"` without LR files, straight from the resident HR bytes, one launch per batch, no intermediate in device
+ * memory.  Descriptor k: `src` the HR image (H and W multiples of 4), (y0, x0) the origin of the size x size window in the LR image, flags and dst as above.  Before the
+ * flips, output pixel (oy, ox) is pixel (y0 + oy, x0 + ox) of MATLAB's imresize(image / 255, 1 / 4) of the WHOLE image: the 18 rows 4 (y0 + oy) - 7 ... + 10, mirrored at the
+ * image's own borders (j < 0 -> -j - 1, j >= H -> 2 H - 1 - j), with the weights w18[0 .. 17] (the one row of data.bicubic_taps(n, 0.25)[1]: at scale 1 / 4 every output
+ * sample has the same weights), then the 18 columns likewise.  fp64 products, each rounded before it is added, sums in tap order, no clamp, one rounding to fp32: bit for
+ * bit dasr_imresize_down of dasr_u8_to_planar of the image, cropped and augmented.  w18 is HOST memory (18 doubles, passed to the kernel by value).  descs_host is a host
+ * copy of the n descriptors (the staging buffer they were uploaded from) and is what is validated: a null pointer, n <= 0, n > 65535, size <= 0, size > 128, a descriptor
+ * with a null src or dst, H or W not a positive multiple of 4, size different from `size`, or a window outside the LR image: DASR_EINVAL, nothing is launched. */
+typedef struct {
+    const uint8_t* src;
+    int32_t H, W;           /* source image */
+    int32_t y0, x0, size;   /* size x size window at (y0, x0) */
+    int32_t flags;          /* bit 0 hflip, bit 1 vflip, bit 2 transpose */
+    float* dst;             /* [3][size][size] */
+} dasr_srn_u8_desc;
+int dasr_gather_srn_u8(const dasr_srn_u8_desc* descs_dev, int32_t n, int32_t max_size, void* stream);
+int dasr_crops_down4_u8(const dasr_srn_u8_desc* descs_dev, const dasr_srn_u8_desc* descs_host, int32_t n, int32_t size, const double* w18, void* stream);
+
 /* ---- profiling session (bench.py `roofline`) -----------------------------------------------------------
  * Between dasr_prof_begin and dasr_prof_end every kernel launch of the library (up to `capacity`) carries its own start/stop
  * events on its launch stream (hipExtLaunchKernel: the dispatch's begin/end timestamps, what rocprofv3 --kernel-trace prints).
