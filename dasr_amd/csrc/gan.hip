@@ -1386,7 +1386,7 @@ extern "C" int dasr_ragan(dasr_tensor a, dasr_tensor b, int32_t N, int32_t H, in
 extern "C" int dasr_dwt_fwd(dasr_tensor x, int32_t N, int32_t C, int32_t H2, int32_t W2, int32_t norm, dasr_tensor ll, dasr_tensor hc,
                             void* stream) {
     const long long total = (long long)N * H2 * W2;
-    if (total <= 0 || C > 5) return DASR_EINVAL;
+    if (total <= 0 || C <= 0 || C > 5 || !x.p || (!ll.p && !hc.p)) return DASR_EINVAL;
     DASR_LAUNCH(dwt_fwd_kernel, dim3(nblk(total)), dim3(256), 0, as_stream(stream), x, N, C, H2, W2, norm, ll, hc);
     return (int)hipGetLastError();
 }
@@ -1394,7 +1394,7 @@ extern "C" int dasr_dwt_fwd(dasr_tensor x, int32_t N, int32_t C, int32_t H2, int
 extern "C" int dasr_dwt_bwd(dasr_tensor gll, dasr_tensor ghc, int32_t N, int32_t C, int32_t H2, int32_t W2, int32_t norm, dasr_tensor gx,
                             int32_t accumulate, void* stream) {
     const long long total = (long long)N * H2 * W2;
-    if (total <= 0 || C > 5) return DASR_EINVAL;
+    if (total <= 0 || C <= 0 || C > 5 || !gx.p || (!gll.p && !ghc.p)) return DASR_EINVAL;
     DASR_LAUNCH(dwt_bwd_kernel, dim3(nblk(total)), dim3(256), 0, as_stream(stream), gll, ghc, N, C, H2, W2, norm, gx, accumulate);
     return (int)hipGetLastError();
 }
@@ -1402,7 +1402,9 @@ extern "C" int dasr_dwt_bwd(dasr_tensor gll, dasr_tensor ghc, int32_t N, int32_t
 extern "C" int dasr_lowpass(dasr_tensor x, dasr_tensor x2, const float* w, int32_t k, int32_t N, int32_t C, int32_t H, int32_t W,
                             int32_t mode, float a_h, float b_h, dasr_tensor out_low, dasr_tensor out_high, int32_t accumulate, void* stream) {
     const long long total = (long long)N * H * W;
-    if (total <= 0 || C > 4 || !(k & 1)) return DASR_EINVAL;
+    if (total <= 0 || C <= 0 || C > 4 || k <= 0 || !(k & 1) || !w) return DASR_EINVAL;
+    // the kernel reads x (mode 0) / writes out_low (mode 1) unconditionally; a call with nothing to write or nothing to read is a mistake
+    if (!(mode & 1) ? (!x.p || (!out_low.p && !out_high.p)) : (!out_low.p || (!x.p && !x2.p))) return DASR_EINVAL;
     DASR_LAUNCH(lowpass_kernel, dim3(nblk(total)), dim3(256), 0, as_stream(stream), x, x2, w, k, N, C, H, W, mode, a_h, b_h, out_low,
                        out_high, accumulate);
     return (int)hipGetLastError();
@@ -1462,7 +1464,7 @@ extern "C" int dasr_affine4(dasr_tensor x, int32_t N, int32_t C, int32_t H, int3
 
 extern "C" int dasr_bilinear_up(const float* src, int32_t N, int32_t h, int32_t w, int32_t factor, float* dst, void* stream) {
     const long long total = (long long)N * h * w * factor * factor;
-    if (total <= 0) return DASR_EINVAL;
+    if (total <= 0 || factor <= 0 || !src || !dst) return DASR_EINVAL;
     DASR_LAUNCH(bilinear_up_kernel, dim3(nblk(total)), dim3(256), 0, as_stream(stream), src, N, h, w, factor, dst);
     return (int)hipGetLastError();
 }
@@ -1519,7 +1521,7 @@ extern "C" int dasr_ddm_spread(dasr_tensor d, int32_t N, int32_t n_h, int32_t n_
 extern "C" int dasr_logloss(dasr_tensor x, int32_t N, int32_t H, int32_t W, int32_t mode, float eps, float coef, float gcoef, float* loss_acc,
                             float* score_acc, float score_coef, dasr_tensor grad, int32_t accumulate, void* stream) {
     const long long total = (long long)N * H * W;
-    if (total <= 0) return DASR_EINVAL;
+    if (total <= 0 || !x.p || (mode != 0 && mode != 1)) return DASR_EINVAL;
     const void* key = loss_acc ? (const void*)loss_acc : (const void*)score_acc;
     const dasr_red rs = dasr_red_scratch(key, as_stream(stream), nblk(total), 2);
     if (key && !rs.part) return dasr_red_error();
@@ -1530,7 +1532,7 @@ extern "C" int dasr_logloss(dasr_tensor x, int32_t N, int32_t H, int32_t W, int3
 
 extern "C" int dasr_sigmoid_bwd(dasr_tensor y, dasr_tensor g, int32_t N, int32_t C, int32_t H, int32_t W, dasr_tensor gz, void* stream) {
     const long long total = (long long)N * H * W;
-    if (total <= 0 || C > 4) return DASR_EINVAL;
+    if (total <= 0 || C > 4 || !y.p || !g.p || !gz.p) return DASR_EINVAL;
     DASR_LAUNCH(sigmoid_bwd_kernel, dim3(nblk(total)), dim3(256), 0, as_stream(stream), y, g, N, C, H, W, gz);
     return (int)hipGetLastError();
 }
@@ -1572,8 +1574,9 @@ extern "C" int dasr_prelu_grad_f16(dasr_tensor y, dasr_tensor gx, int32_t N, int
 
 extern "C" int dasr_lowpass_valid(dasr_tensor x, const float* w, int32_t k, int32_t N, int32_t C, int32_t H, int32_t W, int32_t mode,
                                   dasr_tensor out, int32_t accumulate, void* stream) {
+    if (k <= 0 || C > 4 || H < k || W < k || (mode != 0 && mode != 1) || !x.p || !out.p || !w) return DASR_EINVAL;
     const long long total = (long long)N * (mode == 0 ? (H - k + 1) * (long long)(W - k + 1) : (long long)H * W);
-    if (total <= 0 || C > 4 || H < k || W < k) return DASR_EINVAL;
+    if (total <= 0) return DASR_EINVAL;
     DASR_LAUNCH(lowpass_valid_kernel, dim3(nblk(total)), dim3(256), 0, as_stream(stream), x, w, k, N, C, H, W, mode, out, accumulate);
     return (int)hipGetLastError();
 }

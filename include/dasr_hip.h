@@ -361,15 +361,31 @@ int dasr_gan_loss(dasr_tensor x, int32_t N, int32_t C, int32_t H, int32_t W, int
 int dasr_ragan(dasr_tensor a, dasr_tensor b, int32_t N, int32_t H, int32_t W, int32_t stage, int32_t n_glob, int32_t form, float ta, float tb,
                float coef, float gcoef, float eps, float* sums, float* part, float* loss_acc, float* score_a, float* score_b, float score_coef,
                dasr_tensor ga, dasr_tensor gb, void* stream);
-/* Haar DWT level 1 as used by DASR_Model.wavelet_s (DASR_model.py:442-452): LL (C ch) and [LH|HL|HH] (3C ch), optional
- * norm (LL*0.5, Hc*0.5+0.5); and its adjoint (accumulating into gx).  H2, W2 = output size. */
+/* Haar DWT level 1 as used by DASR_Model.wavelet_s (DASR_model.py:442-452) on C (1..5) channels of plane 0 of x ([N][C][2 H2][2 W2] fp32; H2, W2 =
+ * output size): over each block [[a, b], [c, d]]  LL = (a+b+c+d)/2 -> ll (C channels), LH = (a+b-c-d)/2, HL = (a-b+c-d)/2, HH = (a-b-c+d)/2 -> hc
+ * ([LH | HL | HH], 3C channels).  norm bits: bit 0: LL * 0.5, bands * 0.5 + 0.5; bit 1: the 'sum' format of the DSN discriminator
+ * (codes/DSN/model.py:113-114), hc = (LH + HL + HH) / 3 in C channels (taken after bit 0); bit 2: the linear part only (bit 0 without its + 0.5: the
+ * tangent of the normalised bands).  ll or hc may be null (not computed), not both.  Every output given is written on all 16 channels of plane 0:
+ * zero from channel C on (ll) / from channel 3C on, C with bit 1 (hc); channels of x from C on are never read; no other plane is touched.
+ * dasr_dwt_bwd is the adjoint of the linear part: gx (+)= DWT^T (gll, ghc), with the same norm bits (bit 2 changes nothing); gll or ghc may be null
+ * (taken as zero), not both.  accumulate 0: plane 0 of gx is written on all 16 channels, zero from channel C on; accumulate != 0: channels below C
+ * are added to, the others keep their bits.
+ * DASR_EINVAL: N * H2 * W2 <= 0, C outside 1..5, x / gx null, both outputs / both inputs null. */
 int dasr_dwt_fwd(dasr_tensor x, int32_t N, int32_t C, int32_t H2, int32_t W2, int32_t norm, dasr_tensor ll, dasr_tensor hc, void* stream);
 int dasr_dwt_bwd(dasr_tensor gll, dasr_tensor ghc, int32_t N, int32_t C, int32_t H2, int32_t W2, int32_t norm, dasr_tensor gx,
                  int32_t accumulate, void* stream);
-/* depthwise k x k low-pass (GaussianFilter / AvgPool2d of FilterLow/FilterHigh, architecture.py:1177-1243), zero pad.
- * mode bit 1 set: normalise by the in-image fraction of the window (AvgPool2d(count_include_pad=False), model.py:69-74).
- * mode 0: out_low = low(x), out_high = a_h*(x - low(x)) + b_h.  mode 1 (adjoint): out_low (+)= low(x) + a_h*(x2 - low(x2))
- * with x = dL/dlow, x2 = dL/dhigh (either may be null). */
+/* depthwise k x k low-pass (GaussianFilter / AvgPool2d of FilterLow/FilterHigh, architecture.py:1177-1243) on C (1..4) channels of plane 0, k odd,
+ * w = [k][k] fp32 on the device: cross-correlation with zero padding r = (k - 1) / 2, low(x)[y][x] = sum w[ky][kx] * x[y + ky - r][x + kx - r].
+ * mode bit 1 set: normalise by the in-image fraction of the window (count of in-image taps / k^2: with w = 1 / k^2 this is
+ * AvgPool2d(count_include_pad=False), model.py:69-74); the window may be larger than the image.
+ * mode bit 0 clear (forward): out_low = low(x), out_high = a_h*(x - low(x)) + b_h; either output may be null, not both; x2 and accumulate are not
+ * read.  Each output given is written on all 16 channels of plane 0, zero from channel C on.
+ * mode bit 0 set (adjoint): out_low (+)= low(x) + a_h*(x2 - low(x2)) with x = dL/dlow, x2 = dL/dhigh (either may be null, not both); out_high and
+ * b_h are not read.  With mode bit 1 the normaliser is the one of the forward op's OUTPUT pixel.  The kernel correlates with w itself where the
+ * adjoint correlates with the flipped w: this form is the adjoint only for a SYMMETRIC w (w[ky][kx] == w[k-1-ky][k-1-kx]: every gaussian and box
+ * kernel of the trainers); the caller keeps that contract.  accumulate 0: all 16 channels written, zero from channel C on; accumulate != 0: channels
+ * below C are added to, the others keep their bits.
+ * DASR_EINVAL: N * H * W <= 0, C outside 1..4, k <= 0 or even, w null; forward: x null or both outputs null; adjoint: out_low null or both inputs null. */
 int dasr_lowpass(dasr_tensor x, dasr_tensor x2, const float* w, int32_t k, int32_t N, int32_t C, int32_t H, int32_t W,
                  int32_t mode, float a_h, float b_h, dasr_tensor out_low, dasr_tensor out_high, int32_t accumulate, void* stream);
 /* nn.MaxPool2d(2,2) of the VGG19 feature stack, forward and backward (Ho, Wo = pooled size; Win = width of the INPUT: 2 Wo or 2 Wo + 1 --
@@ -391,7 +407,8 @@ int dasr_l1_diff(dasr_tensor a, dasr_tensor b, int32_t is_f32, int32_t N, int32_
  * channels from C on keep what they held.  Planes of y past those are never touched.  scale4 / shift4: HOST pointers (read by the launcher). */
 int dasr_affine4(dasr_tensor x, int32_t N, int32_t C, int32_t H, int32_t W, const float* scale4, const float* shift4, dasr_tensor y,
                  int32_t y_f32, int32_t accumulate, void* stream);
-/* F.interpolate(bilinear, align_corners=False) of the domain-distance map (DASR_model.py:173-174), NCHW [N][1][h][w] */
+/* F.interpolate(bilinear, align_corners=False) of the domain-distance map (DASR_model.py:173-174) by the integer `factor`: src NCHW [N][1][h][w] ->
+ * dst [N][1][h * factor][w * factor], plain fp32 device buffers (h or w may be 1).  DASR_EINVAL: N * h * w <= 0, factor <= 0, src / dst null. */
 int dasr_bilinear_up(const float* src, int32_t N, int32_t h, int32_t w, int32_t factor, float* dst, void* stream);
 
 /* ---- LPIPS(alex) perceptual loss (csrc/lpips.hip) ----------------------------------------------------------------------
@@ -419,14 +436,19 @@ int dasr_lpips_head(dasr_tensor f, int64_t pair_off, int32_t N, int32_t C, int32
 /* ---- DSN (codes/DSN) kernels ---------------------------------------------------------------------------------*/
 /* domain-distance map for any discriminator conv table (receptive_cal.py:34-60, create_dataset_modified.py:14-24,119-126): D output value
  * (i, j) spread over its receptive-field window (jump / rf / start of the walk over the conv table), divided by the coverage count; d =
- * [N][1][n_h][n_w] D output, out = [N][1][H][W] map (channel 0 of 16-channel fp32 planes).  FSD uses the equivalent 17 x 17 box of dasr_lowpass. */
+ * [N][1][n_h][n_w] D output, out = [N][1][H][W] map (channel 0 of 16-channel fp32 planes: only channel 0 of d is read, channels 1..15 of plane 0 of
+ * out are written zero).  (jump, rf, start) of the walk over the WIDTH serve both axes.  FSD uses the equivalent 17 x 17 box of dasr_lowpass. */
 int dasr_ddm_spread(dasr_tensor d, int32_t N, int32_t n_h, int32_t n_w, int32_t H, int32_t W, int32_t jump, int32_t rf, float start,
                     dasr_tensor out, void* stream);
-/* -log losses of codes/DSN/loss.py:11-41 on p = sigmoid(logit) (model.py:104-105): mode 0: -log(p+eps), mode 1:
- * -log(1-p+eps); loss_acc += coef*sum, score_acc += score_coef*sum(p), grad (+)= gcoef * d/dlogit */
+/* -log losses of codes/DSN/loss.py:11-41 on p = sigmoid(logit) (model.py:104-105), logit = channel 0 of plane 0 of x: mode 0: -log(p+eps), mode 1:
+ * -log(1-p+eps); loss_acc += coef*sum, score_acc += score_coef*sum(p) (either or both may be null), grad (+)= gcoef * d/dlogit (may be null).
+ * accumulate 0: plane 0 of grad is written on all 16 channels, zero from channel 1 on; accumulate != 0: channel 0 is added to, the others keep their
+ * bits.  Saturated logits give finite values: the loss stays within [-log(1+eps), -log(eps)], the gradient goes to (signed) zero.
+ * DASR_EINVAL: N * H * W <= 0, x null, mode outside {0, 1}. */
 int dasr_logloss(dasr_tensor x, int32_t N, int32_t H, int32_t W, int32_t mode, float eps, float coef, float gcoef, float* loss_acc,
                  float* score_acc, float score_coef, dasr_tensor grad, int32_t accumulate, void* stream);
-/* backward of the generator's output sigmoid (model.py:55) */
+/* backward of the generator's output sigmoid (model.py:55): gz = g * y * (1 - y) on C (<= 4) channels of plane 0; gz is written on all 16 channels
+ * of plane 0, zero from channel C on; no other plane is touched.  DASR_EINVAL: N * H * W <= 0, C > 4, y / g / gz null. */
 int dasr_sigmoid_bwd(dasr_tensor y, dasr_tensor g, int32_t N, int32_t C, int32_t H, int32_t W, dasr_tensor gz, void* stream);
 /* y = sigmoid(x) on C (<= 4) channels of plane 0: the discriminator's output map at inference (codes/DSN/model.py:104-106,
  * consumed by create_dataset_modified.py:14-24) */
@@ -443,8 +465,11 @@ int dasr_prelu_grad_f16(dasr_tensor y, dasr_tensor gx, int32_t N, int32_t C, int
  * *dsts[k] = scale * sum / (*slopes[k])^2.  The partials are those the data-gradient conv epilogues leave in dasr_conv_params::prelu_part (slope * dL/dh * h per
  * workgroup): the DSN generator's residual blocks no longer read h and dL/dz a second time (dasr_prelu_grad_f16 did). slopes / dsts: DEVICE arrays of device pointers. */
 int dasr_prelu_final(const float* partial, int32_t nblocks, int64_t stride, int32_t count, const float* const* slopes, float* const* dsts, float scale, void* stream);
-/* un-padded low-pass of the colour loss (FilterLow(padding=False), loss.py:52-56): mode 0 forward (H-k+1 x W-k+1 out),
- * mode 1 adjoint */
+/* un-padded low-pass of the colour loss (FilterLow(padding=False), loss.py:52-56) on C (<= 4) channels of plane 0, w = [k][k] fp32 on the device
+ * (any w: nothing relies on symmetry here).  H, W are the size of the IMAGE in both modes.  mode 0 forward: out[y][x] = sum w[ky][kx] * x[y+ky][x+kx],
+ * x H x W -> out (H-k+1) x (W-k+1).  mode 1: its adjoint, x = gradient (H-k+1) x (W-k+1) -> out H x W, out[y+ky][x+kx] (+)= w[ky][kx] * x[y][x].
+ * accumulate 0: plane 0 of out is written on all 16 channels, zero from channel C on; accumulate != 0: channels below C are added to, the others
+ * keep their bits.  DASR_EINVAL: k <= 0, H < k, W < k, C > 4, mode outside {0, 1}, x / out / w null, N <= 0. */
 int dasr_lowpass_valid(dasr_tensor x, const float* w, int32_t k, int32_t N, int32_t C, int32_t H, int32_t W, int32_t mode,
                        dasr_tensor out, int32_t accumulate, void* stream);
 

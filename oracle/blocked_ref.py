@@ -1,12 +1,13 @@
-"""Plain torch-CPU references of the small kernels of csrc/misc.hip / csrc/gan.hip (elementwise, pooling, pixel losses, Adam), and the NC16HW16
-layout plumbing the GPU tests need.  No device code: tests/test_blocked_ref.py holds every function here to stock torch on a machine without a GPU;
-tests/test_gpu_elementwise.py then holds the kernels to these.
+"""Plain torch-CPU references of the small kernels of csrc/misc.hip / csrc/gan.hip (elementwise, pooling, pixel losses, Adam; the frequency-split,
+domain-distance-map and DSN loss kernels), and the NC16HW16 layout plumbing the GPU tests need.  No device code: tests/test_blocked_ref.py holds every
+function here to stock torch on a machine without a GPU; tests/test_gpu_elementwise.py and tests/test_gpu_filters.py then hold the kernels to these.
 
 Every reference computes in fp64 on NCHW tensors and returns (value, magnitude): `magnitude` is the per-element sum of the absolute values of the
 terms the kernel adds up, the quantity a rounding-error bound k * u * magnitude is relative to.  Scalars (a, b, slope, coef, ...) are taken as given:
 callers pass the fp32 value the kernel receives (f32())."""
 import struct
 
+import numpy as np
 import torch
 
 U32 = 2.0 ** -24                          # unit roundoff of fp32
@@ -241,3 +242,187 @@ def adam(p, grads, lr, beta1, beta2, eps, wd):
         p = p - upd
         Ep = Ep + Eupd + p.abs()
     return p, m, v, Ep, Em, Ev
+
+
+# ---- frequency split: Haar DWT, depthwise low-pass ----------------------------------------------------------------------------------------
+def _blocks(x):
+    """the four elements [[a, b], [c, d]] of every 2x2 block"""
+    s = x.double()
+    return s[:, :, 0::2, 0::2], s[:, :, 0::2, 1::2], s[:, :, 1::2, 0::2], s[:, :, 1::2, 1::2]
+
+
+def dwt(x, norm=0):
+    """level-1 Haar analysis (oracle/nets.py::HaarDWT): LL = (a+b+c+d)/2, LH = (a+b-c-d)/2, HL = (a-b+c-d)/2, HH = (a-b-c+d)/2.
+    norm bit 0: LL * 0.5, bands * 0.5 + 0.5; bit 1: the 'sum' format, hc = (LH + HL + HH) / 3 in C channels instead of [LH | HL | HH] in 3C;
+    bit 2: the linear part only (no + 0.5).  Returns ((ll, magnitude), (hc, magnitude))."""
+    a, b, c, d = _blocks(x)
+    s = 0.5 * (0.5 if norm & 1 else 1.0)
+    off = 0.5 if (norm & 1) and not (norm & 4) else 0.0
+    mag = (a.abs() + b.abs() + c.abs() + d.abs()) * s
+    ll = (a + b + c + d) * s
+    bands = [(a + b - c - d) * s + off, (a - b + c - d) * s + off, (a - b - c + d) * s + off]
+    if norm & 2:
+        return (ll, mag), ((bands[0] + bands[1] + bands[2]) / 3.0, mag + off)
+    return (ll, mag), (torch.cat(bands, 1), torch.cat([mag + off] * 3, 1))
+
+
+def dwt_adj(gll, ghc, C, norm=0):
+    """adjoint of the linear part of dwt: gx = DWT^T (gll, ghc); gll / ghc None: zero.  Returns (gx [N][C][2 H2][2 W2], magnitude)."""
+    ref = gll if gll is not None else ghc
+    N, _, H2, W2 = ref.shape
+    zero = torch.zeros(N, C, H2, W2, dtype=torch.float64)
+    l = zero if gll is None else gll.double()
+    if ghc is None:
+        lh = hl = hh = zero
+    elif norm & 2:
+        lh = hl = hh = ghc.double() / 3.0
+    else:
+        lh, hl, hh = ghc.double()[:, :C], ghc.double()[:, C:2 * C], ghc.double()[:, 2 * C:]
+    s = 0.5 * (0.5 if norm & 1 else 1.0)
+    gx, mag = torch.zeros(N, C, 2 * H2, 2 * W2, dtype=torch.float64), torch.zeros(N, C, 2 * H2, 2 * W2, dtype=torch.float64)
+    for (dy, dx), (s1, s2, s3) in {(0, 0): (1, 1, 1), (0, 1): (1, -1, -1), (1, 0): (-1, 1, -1), (1, 1): (-1, -1, 1)}.items():
+        gx[:, :, dy::2, dx::2] = s * (l + s1 * lh + s2 * hl + s3 * hh)
+        mag[:, :, dy::2, dx::2] = s * (l.abs() + lh.abs() + hl.abs() + hh.abs())
+    return gx, mag
+
+
+def valid_count(H, W, k):
+    """[H][W]: how many taps of the k x k window centred at (y, x) lie inside the image"""
+    r = (k - 1) // 2
+    ny = torch.tensor([min(y + r, H - 1) - max(y - r, 0) + 1 for y in range(H)], dtype=torch.float64)
+    nx = torch.tensor([min(x + r, W - 1) - max(x - r, 0) + 1 for x in range(W)], dtype=torch.float64)
+    return ny.view(H, 1) * nx.view(1, W)
+
+
+def lowpass(x, w, norm_valid=False):
+    """depthwise k x k cross-correlation with zero padding r = (k - 1) / 2: out[y, x] = sum w[ky, kx] * in[y + ky - r, x + kx - r];
+    norm_valid: divided by the in-image fraction of the window (count / k^2; with the uniform w = 1 / k^2 this is AvgPool2d(count_include_pad=False)).
+    Returns (low, sum |w * in| with the same normaliser)."""
+    k = w.shape[0]
+    r = (k - 1) // 2
+    N, C, H, W = x.shape
+    xp = torch.zeros(N, C, H + 2 * r, W + 2 * r, dtype=torch.float64)
+    xp[:, :, r:r + H, r:r + W] = x.double()
+    out, mag = torch.zeros(N, C, H, W, dtype=torch.float64), torch.zeros(N, C, H, W, dtype=torch.float64)
+    for ky in range(k):
+        for kx in range(k):
+            t = float(w[ky, kx]) * xp[:, :, ky:ky + H, kx:kx + W]
+            out, mag = out + t, mag + t.abs()
+    if norm_valid:
+        frac = valid_count(H, W, k) / float(k * k)
+        out, mag = out / frac, mag / frac
+    return out, mag
+
+
+def _lowpass_t(g, w, norm_valid):
+    """adjoint of lowpass for any w: every output pixel (y, x) of the forward op hands w[ky, kx] * g[y, x] (over ITS normaliser) back to the
+    input pixel (y + ky - r, x + kx - r) it read"""
+    k = w.shape[0]
+    r = (k - 1) // 2
+    N, C, H, W = g.shape
+    gd = g.double()
+    if norm_valid:
+        gd = gd / (valid_count(H, W, k) / float(k * k))
+    gp, mp = torch.zeros(N, C, H + 2 * r, W + 2 * r, dtype=torch.float64), torch.zeros(N, C, H + 2 * r, W + 2 * r, dtype=torch.float64)
+    for ky in range(k):
+        for kx in range(k):
+            t = float(w[ky, kx]) * gd
+            gp[:, :, ky:ky + H, kx:kx + W] += t
+            mp[:, :, ky:ky + H, kx:kx + W] += t.abs()
+    return gp[:, :, r:r + H, r:r + W], mp[:, :, r:r + H, r:r + W]
+
+
+def lowpass_adj(g_low, g_high, w, a_h, norm_valid=False):
+    """adjoint of x -> (low(x), a_h * (x - low(x))): gx = low^T(g_low) + a_h * (g_high - low^T(g_high)); either gradient may be None (zero).
+    Returns (gx, magnitude)."""
+    ref = g_low if g_low is not None else g_high
+    gx, mag = torch.zeros(ref.shape, dtype=torch.float64), torch.zeros(ref.shape, dtype=torch.float64)
+    if g_low is not None:
+        gx, mag = _lowpass_t(g_low, w, norm_valid)
+    if g_high is not None:
+        t, tm = _lowpass_t(g_high, w, norm_valid)
+        gx, mag = gx + a_h * (g_high.double() - t), mag + abs(a_h) * (g_high.double().abs() + tm)
+    return gx, mag
+
+
+def lowpass_valid(x, w):
+    """un-padded k x k cross-correlation: out[y, x] = sum w[ky, kx] * in[y + ky, x + kx], (H - k + 1) x (W - k + 1).  Returns (out, sum |w * in|)."""
+    k = w.shape[0]
+    N, C, H, W = x.shape
+    Ho, Wo = H - k + 1, W - k + 1
+    xd = x.double()
+    out, mag = torch.zeros(N, C, Ho, Wo, dtype=torch.float64), torch.zeros(N, C, Ho, Wo, dtype=torch.float64)
+    for ky in range(k):
+        for kx in range(k):
+            t = float(w[ky, kx]) * xd[:, :, ky:ky + Ho, kx:kx + Wo]
+            out, mag = out + t, mag + t.abs()
+    return out, mag
+
+
+def lowpass_valid_adj(g, w, H, W):
+    """the adjoint of lowpass_valid for any w: gx[y + ky, x + kx] += w[ky, kx] * g[y, x].  Returns (gx [H][W], magnitude)."""
+    k = w.shape[0]
+    N, C, Ho, Wo = g.shape
+    assert (Ho, Wo) == (H - k + 1, W - k + 1)
+    gx, mag = torch.zeros(N, C, H, W, dtype=torch.float64), torch.zeros(N, C, H, W, dtype=torch.float64)
+    for ky in range(k):
+        for kx in range(k):
+            t = float(w[ky, kx]) * g.double()
+            gx[:, :, ky:ky + Ho, kx:kx + Wo] += t
+            mag[:, :, ky:ky + Ho, kx:kx + Wo] += t.abs()
+    return gx, mag
+
+
+# ---- domain-distance map ---------------------------------------------------------------------------------------------------------------
+def ddm_spread(d, H, W, convnet):
+    """the scatter form of oracle/dsn_dataset.py: every value of d [N][1][n_h][n_w] added over its receptive-field window, divided by the same
+    spread of ones; (jump, rf, start) of the walk over the WIDTH serve both axes.  Returns (map, spread of |d| / count, count, (n_h, n_w, jump, rf,
+    start))."""
+    from oracle.dsn_dataset import receptive, spread
+    lay_h, lay_w = receptive(H, convnet), receptive(W, convnet)
+    dn = d.double().numpy()
+    assert dn.shape[1:] == (1, lay_h[0], lay_w[0]), (dn.shape, lay_h, lay_w)
+    shape = (dn.shape[0], 1, H, W)
+    cnt = spread(np.ones_like(dn), shape, lay_h, lay_w)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        v, mag = spread(dn, shape, lay_h, lay_w) / cnt, spread(np.abs(dn), shape, lay_h, lay_w) / cnt
+    return torch.from_numpy(v), torch.from_numpy(mag), torch.from_numpy(cnt), (lay_h[0],) + tuple(lay_w)
+
+
+def bilinear_up(src, f):
+    """F.interpolate(mode='bilinear', align_corners=False) of [N][1][h][w] by the integer factor f: source coordinate (o + 0.5) / f - 0.5, clamped at
+    0, the upper neighbour clamped at the last index.  Returns (value, sum of weight * |corner|)."""
+    N, _, h, w = src.shape
+    s = src.double()
+
+    def axis(n_in):
+        c = ((torch.arange(n_in * f, dtype=torch.float64) + 0.5) / f - 0.5).clamp_min(0.0)
+        i0 = c.floor().long().clamp_max(n_in - 1)
+        i1 = (i0 + 1).clamp_max(n_in - 1)
+        return i0, i1, c - i0.double()
+    y0, y1, ly = axis(h)
+    x0, x1, lx = axis(w)
+    ly, lx = ly.view(-1, 1), lx.view(1, -1)
+    out, mag = 0.0, 0.0
+    for yi, wy in ((y0, 1.0 - ly), (y1, ly)):
+        for xi, wx in ((x0, 1.0 - lx), (x1, lx)):
+            t = (wy * wx) * s[:, :, yi][:, :, :, xi]
+            out, mag = out + t, mag + t.abs()
+    return out, mag
+
+
+# ---- DSN losses -------------------------------------------------------------------------------------------------------------------------
+def logloss(x, mode, eps):
+    """-log losses on p = sigmoid(logit): mode 0 l = -log(p + eps), mode 1 l = -log(1 - p + eps).  Returns (l, p, dl/dlogit) per pixel."""
+    v = x.double()
+    p = 1.0 / (1.0 + torch.exp(-v))
+    dp = p * (1.0 - p)
+    if mode == 0:
+        return -torch.log(p + eps), p, -dp / (p + eps)
+    return -torch.log(1.0 - p + eps), p, dp / (1.0 - p + eps)
+
+
+def sigmoid_bwd(y, g):
+    """backward of y = sigmoid(z): gz = g * y * (1 - y)"""
+    v = g.double() * y.double() * (1.0 - y.double())
+    return v, v.abs()

@@ -1,4 +1,5 @@
-"""CPU checks of oracle/blocked_ref.py, the references tests/test_gpu_elementwise.py trusts, against stock torch: they run where no kernel can."""
+"""CPU checks of oracle/blocked_ref.py, the references tests/test_gpu_elementwise.py and tests/test_gpu_filters.py trust, against stock torch: they
+run where no kernel can."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -205,3 +206,153 @@ def test_adam_matches_torch_and_its_error_bound_is_tight(wd):
     # ... and is tighter than the rtol 1e-5 / atol 1e-7 the end-to-end test of the kernel uses
     assert bool((R.U32 * Ep <= 1e-7 + 1e-5 * p.abs()).all()) and float((R.U32 * Ep).max()) < 2e-6
     assert bool((Em >= 0).all()) and bool((Ev >= 0).all())
+
+
+# ---- the frequency-split, domain-distance-map and DSN loss references -------------------------------------------------------------------
+def dot(a, b):
+    return float((a.double() * b.double()).sum())
+
+
+def same_dot(lhs, rhs):
+    """<A x, g> == <x, A^T g> to 1e-12 relative"""
+    return abs(lhs - rhs) <= 1e-12 * max(abs(lhs), abs(rhs))
+
+
+def nonsym(k, g):
+    """a k x k kernel that is no transpose, flip or rotation of itself"""
+    w = torch.rand(k, k, generator=g, dtype=torch.float64) + 0.1
+    assert not torch.equal(w, w.t()) and not torch.equal(w, w.flip(0)) and not torch.equal(w, w.flip(1)) and not torch.equal(w, w.flip(0, 1))
+    return w
+
+
+@pytest.mark.parametrize('C', [1, 3, 5])
+@pytest.mark.parametrize('norm', [0, 1, 2, 3, 5])
+def test_dwt_matches_haar_and_its_adjoint(norm, C):
+    from oracle.nets import HaarDWT
+    g = gen(20)
+    x = torch.randn(2, C, 10, 14, generator=g, dtype=torch.float64)
+    ll0, hc0 = HaarDWT()(x)
+    (ll, llm), (hc, hcm) = R.dwt(x, norm)
+    s, off = (0.5 if norm & 1 else 1.0), (0.5 if norm in (1, 3) else 0.0)
+    want = hc0 * s + off
+    if norm & 2:
+        want = (want[:, :C] + want[:, C:2 * C] + want[:, 2 * C:]) / 3.0
+    assert torch.allclose(ll, ll0 * s, rtol=0, atol=1e-15) and torch.allclose(hc, want, rtol=0, atol=1e-15)
+    assert hc.shape[1] == (C if norm & 2 else 3 * C) and bool((llm >= ll.abs() - 1e-15).all()) and bool((hcm >= hc.abs() - 1e-15).all())
+    # the adjoint of the linear part (norm | 4 drops the offset), with both bands, one band and the other
+    (lin_ll, _), (lin_hc, _) = R.dwt(x, norm | 4)
+    gll, ghc = torch.randn(ll.shape, generator=g, dtype=torch.float64), torch.randn(hc.shape, generator=g, dtype=torch.float64)
+    for a, b in ((gll, ghc), (gll, None), (None, ghc)):
+        gx, gm = R.dwt_adj(a, b, C, norm)
+        lhs = (dot(lin_ll, a) if a is not None else 0.0) + (dot(lin_hc, b) if b is not None else 0.0)
+        assert same_dot(lhs, dot(x, gx)) and bool((gm >= gx.abs() - 1e-15).all())
+    xr = x.clone().requires_grad_(True)
+    l2, h2 = HaarDWT()(xr)
+    hs = (h2 * s).view(2, 3, C, 5, 7).sum(1) / 3.0 if norm & 2 else h2 * s
+    ((l2 * s * gll).sum() + (hs * ghc).sum()).backward()
+    assert torch.allclose(R.dwt_adj(gll, ghc, C, norm)[0], xr.grad, rtol=0, atol=1e-15)
+
+
+@pytest.mark.parametrize('hw', [(6, 9), (13, 19)])
+@pytest.mark.parametrize('k', [5, 9])
+def test_lowpass_is_padded_cross_correlation(k, hw):
+    from oracle.nets import gaussian_kernel2d
+    g = gen(21)
+    H, W = hw
+    x = torch.randn(2, 3, H, W, generator=g, dtype=torch.float64)
+    for w in (nonsym(k, g), gaussian_kernel2d(k).double()):
+        low, mag = R.lowpass(x, w)
+        want = F.conv2d(x, w.view(1, 1, k, k).repeat(3, 1, 1, 1), None, 1, (k - 1) // 2, 1, 3)
+        assert torch.allclose(low, want, rtol=0, atol=1e-14) and bool((mag >= low.abs() - 1e-14).all())
+        # a transposed or flipped kernel is a different operator: the non-symmetric w tells them apart
+        if not torch.equal(w, w.t()):
+            for other in (w.t(), w.flip(0), w.flip(1), w.flip(0, 1)):
+                assert float((R.lowpass(x, other.contiguous())[0] - low).abs().max()) > 1e-3
+        for nv in (False, True):
+            for a_h in (0.25, 1.0):
+                gl, gh = torch.randn(x.shape, generator=g, dtype=torch.float64), torch.randn(x.shape, generator=g, dtype=torch.float64)
+                lo = R.lowpass(x, w, nv)[0]
+                hi = a_h * (x - lo)
+                for a, b in ((gl, gh), (gl, None), (None, gh)):
+                    gx, gm = R.lowpass_adj(a, b, w, a_h, nv)
+                    lhs = (dot(lo, a) if a is not None else 0.0) + (dot(hi, b) if b is not None else 0.0)
+                    assert same_dot(lhs, dot(x, gx)) and bool((gm >= gx.abs() - 1e-14).all())
+
+
+@pytest.mark.parametrize('hw', [(6, 9), (20, 28)])
+@pytest.mark.parametrize('k', [5, 17])
+def test_normalised_box_is_avgpool_without_the_pad_count(k, hw):
+    H, W = hw
+    x = torch.randn(2, 1, H, W, generator=gen(22), dtype=torch.float64)
+    w = torch.full((k, k), 1.0 / (k * k), dtype=torch.float64)
+    low, mag = R.lowpass(x, w, True)
+    assert torch.allclose(low, F.avg_pool2d(x, k, 1, (k - 1) // 2, count_include_pad=False), rtol=0, atol=1e-14)
+    assert torch.allclose(R.lowpass(x, w, False)[0], F.avg_pool2d(x, k, 1, (k - 1) // 2, count_include_pad=True), rtol=0, atol=1e-14)
+    assert torch.allclose(mag, F.avg_pool2d(x.abs(), k, 1, (k - 1) // 2, count_include_pad=False), rtol=0, atol=1e-14)
+    if k == 17 and hw == (6, 9):      # the window overhangs on all four sides at once: every pixel is the mean of the whole image
+        assert float(R.valid_count(H, W, k).min()) == H * W
+        assert torch.allclose(low, x.mean((2, 3), keepdim=True).expand_as(x), rtol=0, atol=1e-14)
+    xr = x.clone().requires_grad_(True)
+    g = torch.randn(x.shape, generator=gen(23), dtype=torch.float64)
+    (F.avg_pool2d(xr, k, 1, (k - 1) // 2, count_include_pad=False) * g).sum().backward()
+    assert torch.allclose(R.lowpass_adj(g, None, w, 0.0, True)[0], xr.grad, rtol=0, atol=1e-14)
+
+
+@pytest.mark.parametrize('hw', [(5, 6), (13, 19)])
+def test_lowpass_valid_and_its_adjoint(hw):
+    g = gen(24)
+    H, W = hw
+    k = 5
+    w = nonsym(k, g)
+    x = torch.randn(2, 3, H, W, generator=g, dtype=torch.float64).requires_grad_(True)
+    want = F.conv2d(x, w.view(1, 1, k, k).repeat(3, 1, 1, 1), None, 1, 0, 1, 3)
+    out, mag = R.lowpass_valid(x.detach(), w)
+    assert out.shape == (2, 3, H - 4, W - 4) and torch.allclose(out, want.detach(), rtol=0, atol=1e-14) and bool((mag >= out.abs() - 1e-14).all())
+    gg = torch.randn(out.shape, generator=g, dtype=torch.float64)
+    (want * gg).sum().backward()
+    gx, gm = R.lowpass_valid_adj(gg, w, H, W)
+    assert torch.allclose(gx, x.grad, rtol=0, atol=1e-14) and bool((gm >= gx.abs() - 1e-14).all())
+    assert same_dot(dot(out, gg), dot(x.detach(), gx))
+    assert float((R.lowpass_valid_adj(gg, w.t().contiguous(), H, W)[0] - gx).abs().max()) > 1e-3
+
+
+@pytest.mark.parametrize('arch,hw', [('nld_s1', (24, 32)), ('nld_s1', (32, 40)), ('nld_s2', (24, 32)), ('nld_s2', (32, 40)), ('FSD', (9, 12))])
+def test_ddm_spread_is_the_dataset_step(arch, hw):
+    from oracle import dsn_dataset as D
+    H, W = hw
+    n_h, n_w = D.receptive(H, D.CONVNETS[arch])[0], D.receptive(W, D.CONVNETS[arch])[0]
+    d = torch.rand(2, 1, n_h, n_w, generator=gen(25), dtype=torch.float64)
+    v, mag, cnt, lay = R.ddm_spread(d, H, W, D.CONVNETS[arch])
+    assert torch.equal(v, torch.from_numpy(D.domain_distance_map(d.numpy(), (2, 1, H, W), 'gau', arch)))
+    assert lay == (n_h,) + tuple(D.receptive(W, D.CONVNETS[arch]))
+    assert bool(torch.isfinite(v).all()) and float(cnt.min()) >= 1 and bool((mag >= v.abs() - 1e-15).all())
+    if arch == 'FSD':   # the equivalent form the FSD path uses: the count-normalised 17 x 17 box
+        assert torch.allclose(v, R.lowpass(d, torch.full((17, 17), 1.0 / 289, dtype=torch.float64), True)[0], rtol=0, atol=1e-14)
+
+
+@pytest.mark.parametrize('hw', [(1, 7), (5, 1), (5, 7), (13, 10)])
+@pytest.mark.parametrize('f', [2, 3, 4])
+def test_bilinear_up_matches_interpolate(f, hw):
+    src = torch.randn(2, 1, *hw, generator=gen(26), dtype=torch.float64)
+    v, mag = R.bilinear_up(src, f)
+    assert torch.allclose(v, F.interpolate(src, scale_factor=f, mode='bilinear', align_corners=False), rtol=0, atol=1e-14)
+    assert torch.allclose(mag, F.interpolate(src.abs(), scale_factor=f, mode='bilinear', align_corners=False), rtol=0, atol=1e-14)
+
+
+@pytest.mark.parametrize('eps', [1e-8, 1e-3])
+@pytest.mark.parametrize('mode', [0, 1])
+def test_logloss_and_sigmoid_bwd_match_autograd(mode, eps):
+    g = gen(27)
+    x = (torch.rand(2, 1, 5, 7, generator=g, dtype=torch.float64) * 12.0 - 6.0).requires_grad_(True)
+    p = torch.sigmoid(x)
+    l = -torch.log(p + eps) if mode == 0 else -torch.log(1.0 - p + eps)
+    l.sum().backward()
+    lr, pr, gr = R.logloss(x.detach(), mode, eps)
+    assert torch.allclose(lr, l.detach(), rtol=1e-14, atol=0) and torch.allclose(pr, p.detach(), rtol=1e-15, atol=0)
+    assert torch.allclose(gr, x.grad, rtol=1e-13, atol=0) and bool((gr < 0).all() if mode == 0 else (gr > 0).all())
+    z = torch.randn(2, 3, 5, 7, generator=g, dtype=torch.float64).requires_grad_(True)
+    go = torch.randn(2, 3, 5, 7, generator=g, dtype=torch.float64)
+    y = torch.sigmoid(z)
+    (y * go).sum().backward()
+    v, mag = R.sigmoid_bwd(y.detach(), go)
+    assert torch.allclose(v, z.grad, rtol=1e-14, atol=1e-18) and torch.equal(mag, v.abs())

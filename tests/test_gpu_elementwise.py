@@ -58,6 +58,15 @@ def _entries():
         'sigmoid_fwd': (L.OP_SIGMOID_FWD, ['x', 'N', 'C', 'H', 'W', 'y']),
         'fill_f32': (L.OP_FILL, ['p', 'n', 'value']),
         'add_flat': (L.OP_ADD_FLAT, ['y', 'x', 'n']),
+        # tests/test_gpu_filters.py
+        'dwt_fwd': (L.OP_DWT_FWD, ['x', 'N', 'C', 'H2', 'W2', 'norm', 'll', 'hc']),
+        'dwt_bwd': (L.OP_DWT_BWD, ['gll', 'ghc', 'N', 'C', 'H2', 'W2', 'norm', 'gx', 'accumulate']),
+        'lowpass': (L.OP_LOWPASS, ['x', 'x2', 'w', 'k', 'N', 'C', 'H', 'W', 'mode', 'a_h', 'b_h', 'out_low', 'out_high', 'accumulate']),
+        'lowpass_valid': (L.OP_LOWPASS_VALID, ['x', 'w', 'k', 'N', 'C', 'H', 'W', 'mode', 'out', 'accumulate']),
+        'ddm_spread': (L.OP_DDM_SPREAD, ['d', 'N', 'n_h', 'n_w', 'H', 'W', 'jump', 'rf', 'start', 'out']),
+        'bilinear_up': (L.OP_BILINEAR, ['src', 'N', 'h', 'w', 'factor', 'dst']),
+        'logloss': (L.OP_LOGLOSS, ['x', 'N', 'H', 'W', 'mode', 'eps', 'coef', 'gcoef', 'loss_acc', 'score_acc', 'score_coef', 'grad', 'accumulate']),
+        'sigmoid_bwd': (L.OP_SIGMOID_BWD, ['y', 'g', 'N', 'C', 'H', 'W', 'gz']),
     }
 
 
