@@ -1258,28 +1258,28 @@ __global__ void lowpass_valid_kernel(dasr_tensor x, const float* __restrict__ w,
 
 extern "C" int dasr_inorm_lrelu_fwd(dasr_tensor x, int32_t N, int32_t C, int32_t H, int32_t W, float eps, float slope, dasr_tensor y,
                                     float* stats, void* stream) {
-    if (N <= 0 || C <= 0) return DASR_EINVAL;
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || !x.p || !y.p) return DASR_EINVAL;   // (stats may be null: not written then)
     DASR_LAUNCH(inorm_lrelu_fwd_kernel, dim3(N * ((C + 15) / 16)), dim3(256), 0, as_stream(stream), x, C, H, W, eps, slope, y, stats);
     return (int)hipGetLastError();
 }
 
 extern "C" int dasr_inorm_lrelu_bwd(dasr_tensor a, dasr_tensor ga, int32_t N, int32_t C, int32_t H, int32_t W, float slope,
                                     const float* stats, dasr_tensor gx, void* stream) {
-    if (N <= 0 || C <= 0) return DASR_EINVAL;
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || !a.p || !ga.p || !gx.p || !stats || !(slope > 0.f)) return DASR_EINVAL;   // xhat = a / slope
     DASR_LAUNCH(inorm_lrelu_bwd_kernel, dim3(N * ((C + 15) / 16)), dim3(256), 0, as_stream(stream), a, ga, C, H, W, slope, stats, gx);
     return (int)hipGetLastError();
 }
 
 extern "C" int dasr_inorm_lrelu_jvp(dasr_tensor a, dasr_tensor t, int32_t N, int32_t C, int32_t H, int32_t W, float slope, const float* stats, dasr_tensor out,
                                     void* stream) {
-    if (N <= 0 || C <= 0 || !a.p || !t.p || !out.p || !stats) return DASR_EINVAL;
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || !a.p || !t.p || !out.p || !stats || !(slope > 0.f)) return DASR_EINVAL;
     DASR_LAUNCH(inorm_lrelu_jvp_kernel, dim3(N * ((C + 15) / 16)), dim3(256), 0, as_stream(stream), a, t, C, H, W, slope, stats, out);
     return (int)hipGetLastError();
 }
 
 extern "C" int dasr_inorm_second(dasr_tensor a, dasr_tensor t, dasr_tensor ga, int32_t N, int32_t C, int32_t H, int32_t W, float slope, const float* stats,
                                  dasr_tensor out, int32_t accumulate, void* stream) {
-    if (N <= 0 || C <= 0 || !a.p || !t.p || !ga.p || !out.p || !stats) return DASR_EINVAL;
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || !a.p || !t.p || !ga.p || !out.p || !stats || !(slope > 0.f)) return DASR_EINVAL;
     DASR_LAUNCH(inorm_second_kernel, dim3(N * ((C + 15) / 16)), dim3(256), 0, as_stream(stream), a, t, ga, C, H, W, slope, stats, out, accumulate);
     return (int)hipGetLastError();
 }
@@ -1301,7 +1301,7 @@ extern "C" int dasr_fill_scaled(dasr_tensor x, int32_t N, int32_t C, int32_t H, 
 
 extern "C" int dasr_bnorm_lrelu_fwd(dasr_tensor x, int32_t N, int32_t C, int32_t H, int32_t W, int32_t group, float eps, float slope, const float* gamma,
                                     const float* beta, dasr_tensor y, float* stats, void* stream) {
-    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || group <= 0 || !gamma || !beta || !stats) return DASR_EINVAL;
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || group <= 0 || !x.p || !y.p || !gamma || !beta || !stats) return DASR_EINVAL;
     DASR_LAUNCH(bnorm_lrelu_fwd_kernel, dim3((C + 15) / 16), dim3(256), 0, as_stream(stream), x, N, C, H, W, group, eps, slope, gamma, beta, y, stats);
     return (int)hipGetLastError();
 }
@@ -1309,7 +1309,8 @@ extern "C" int dasr_bnorm_lrelu_fwd(dasr_tensor x, int32_t N, int32_t C, int32_t
 extern "C" int dasr_bnorm_lrelu_bwd(dasr_tensor x, dasr_tensor ga, int32_t N, int32_t C, int32_t H, int32_t W, int32_t group, float slope,
                                     const float* gamma, const float* beta, const float* stats, dasr_tensor gx, float* dgamma, float* dbeta,
                                     float pscale, void* stream) {
-    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || group <= 0 || !gamma || !beta || !stats || (dgamma != nullptr) != (dbeta != nullptr)) return DASR_EINVAL;
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || group <= 0 || !x.p || !ga.p || !gx.p || !gamma || !beta || !stats || (dgamma != nullptr) != (dbeta != nullptr))
+        return DASR_EINVAL;
     DASR_LAUNCH(bnorm_lrelu_bwd_kernel, dim3((C + 15) / 16), dim3(256), 0, as_stream(stream), x, ga, N, C, H, W, group, slope, gamma, beta, stats, gx,
                 dgamma, dbeta, pscale);
     return (int)hipGetLastError();
@@ -1317,7 +1318,7 @@ extern "C" int dasr_bnorm_lrelu_bwd(dasr_tensor x, dasr_tensor ga, int32_t N, in
 
 extern "C" int dasr_bnorm_lrelu_jvp(dasr_tensor x, dasr_tensor t, int32_t N, int32_t C, int32_t H, int32_t W, int32_t group, float slope, const float* gamma,
                                     const float* beta, const float* stats, dasr_tensor out, void* stream) {
-    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || group <= 0 || !gamma || !beta || !stats) return DASR_EINVAL;
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || group <= 0 || !x.p || !t.p || !out.p || !gamma || !beta || !stats) return DASR_EINVAL;
     DASR_LAUNCH(bnorm_lrelu_jvp_kernel, dim3((C + 15) / 16), dim3(256), 0, as_stream(stream), x, t, N, C, H, W, group, slope, gamma, beta, stats, out);
     return (int)hipGetLastError();
 }
@@ -1325,7 +1326,7 @@ extern "C" int dasr_bnorm_lrelu_jvp(dasr_tensor x, dasr_tensor t, int32_t N, int
 extern "C" int dasr_bnorm_second(dasr_tensor x, dasr_tensor t, dasr_tensor ga, int32_t N, int32_t C, int32_t H, int32_t W, int32_t group, float slope,
                                  const float* gamma, const float* beta, const float* stats, dasr_tensor out, int32_t accumulate, float* dgamma, float pscale,
                                  void* stream) {
-    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || group <= 0 || !gamma || !beta || !stats) return DASR_EINVAL;
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || group <= 0 || !x.p || !t.p || !ga.p || !out.p || !gamma || !beta || !stats) return DASR_EINVAL;
     DASR_LAUNCH(bnorm_second_kernel, dim3((C + 15) / 16), dim3(256), 0, as_stream(stream), x, t, ga, N, C, H, W, group, slope, gamma, beta, stats, out,
                 accumulate, dgamma, pscale);
     return (int)hipGetLastError();
@@ -1342,7 +1343,7 @@ extern "C" int dasr_bnorm_running(const float* stats, int32_t g, int32_t C, int3
 extern "C" int dasr_gan_loss(dasr_tensor x, int32_t N, int32_t C, int32_t H, int32_t W, int32_t gan_type, float target, float coef, float gcoef,
                              float* loss_acc, float* score_acc, float score_coef, dasr_tensor grad, void* stream) {
     const long long total = (long long)N * H * W;
-    if (total <= 0 || C > 16 || gan_type < 0 || gan_type > 2) return DASR_EINVAL;
+    if (total <= 0 || C <= 0 || C > 16 || !x.p || gan_type < 0 || gan_type > 2) return DASR_EINVAL;
     const dim3 g(nblk(total)), b(256);
     const void* key = loss_acc ? (const void*)loss_acc : (const void*)score_acc;
     const dasr_red rs = dasr_red_scratch(key, as_stream(stream), g.x, 2);

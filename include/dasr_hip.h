@@ -300,7 +300,14 @@ int dasr_add_flat(float* y, const float* x, int64_t n, void* stream);
 
 /* ---- GAN-step kernels (csrc/gan.hip) ---------------------------------------------------------------------*/
 /* nn.InstanceNorm2d(affine=False, eps) + LeakyReLU of NLayerDiscriminator (architecture.py:1003-1015), fused;
- * stats[N][Cpad][2] = (mean, rstd).  Backward takes the saved forward output a and dL/da, returns dL/dx. */
+ * stats[N][Cpad][2] = (mean, rstd).  Backward takes the saved forward output a and dL/da, returns dL/dx.
+ * Contracts of the InstanceNorm group (these two, dasr_inorm_lrelu_jvp, dasr_inorm_second):
+ *  - padding channels: whole 16-channel planes are processed, the padding channels of the last plane like real ones -- zero in, zero out: with zeros
+ *    in the padding channels of every input tensor (and of `out` when accumulating) every output holds exact zeros there; stats holds (0, 1/sqrt(eps)).
+ *  - the three kernels that read the saved output recover xhat = a > 0 ? a : a / slope and LeakyReLU' = a > 0 ? 1 : slope: at a == +0 and a == -0 the
+ *    slope branch (xhat = 0, derivative `slope`, as autograd has it).  They divide by slope: slope <= 0 is DASR_EINVAL (the forward takes any slope).
+ *  - stats of the forward may be null (not written); every other pointer and tensor is required.
+ *  - DASR_EINVAL, nothing launched: N, C, H or W <= 0; a required tensor or pointer null; slope <= 0 (bwd / jvp / second). */
 int dasr_inorm_lrelu_fwd(dasr_tensor x, int32_t N, int32_t C, int32_t H, int32_t W, float eps, float slope, dasr_tensor y,
                          float* stats, void* stream);
 int dasr_inorm_lrelu_bwd(dasr_tensor a, dasr_tensor ga, int32_t N, int32_t C, int32_t H, int32_t W, float slope,
@@ -325,7 +332,20 @@ int dasr_fill_scaled(dasr_tensor x, int32_t N, int32_t C, int32_t H, int32_t W, 
  * The N images are normalised in groups of `group` consecutive images with their own statistics (the reference runs the discriminator on the
  * fake and the real half in separate calls, DASR_model.py:251,288-289).  stats[N/group][Cpad][3] = (mean, rstd, biased variance).
  * Backward recomputes xhat / z from the saved conv output x: gx per group; dgamma / dbeta (optional, both or none) = pscale * sums over all groups.
- * dasr_bnorm_running: running_mean / running_var (unbiased, `count` = elements per channel of the group) / num_batches_tracked after one forward on group g */
+ * dasr_bnorm_running: running_mean / running_var (unbiased, `count` = elements per channel of the group; count 1: the biased value) / num_batches_tracked
+ * (optional; += 1) after one forward on group g (row g of stats).
+ * Contracts of the BatchNorm group (the forward, the backward, dasr_bnorm_lrelu_jvp, dasr_bnorm_second):
+ *  - groups: N need not be a multiple of `group`; the last group then holds the N % group remaining images, with statistics (and counts) of its own:
+ *    stats has ceil(N / group) rows of Cpad entries, row g for the images [g * group, min(N, (g + 1) * group)).
+ *  - padding channels: gamma, beta, dgamma and dbeta hold C entries; the kernels mask per channel (c < C), read gamma / beta below C only and take
+ *    them as 0 from C on.  The padding channels of the inputs may hold any values for which xhat = (x - mean) rstd and the group sums stay finite in
+ *    fp32 (an overflow there would meet the 0 of gamma as inf * 0): the outputs then hold zeros there (accumulating: what they held),
+ *    dgamma / dbeta are not written from C on; the padding entries of a stats row are written by the forward and carry no meaning.
+ *  - LeakyReLU' is read from the sign of z = gamma xhat + beta, recomputed in fp32 from the saved x and the stats row: z <= 0 (both zeros) is the
+ *    slope branch.  Any slope is accepted (nothing divides by it).
+ *  - optional pointers: dgamma and dbeta of the backward (both or none), dgamma of dasr_bnorm_second, num_batches_tracked; everything else is required.
+ *  - DASR_EINVAL, nothing launched: N, C, H, W or group <= 0; a required tensor or pointer null; only one of dgamma / dbeta given; dasr_bnorm_running:
+ *    g < 0, C <= 0 or count <= 0. */
 int dasr_bnorm_lrelu_fwd(dasr_tensor x, int32_t N, int32_t C, int32_t H, int32_t W, int32_t group, float eps, float slope, const float* gamma,
                          const float* beta, dasr_tensor y, float* stats, void* stream);
 int dasr_bnorm_lrelu_bwd(dasr_tensor x, dasr_tensor ga, int32_t N, int32_t C, int32_t H, int32_t W, int32_t group, float slope, const float* gamma,
@@ -343,7 +363,9 @@ int dasr_bnorm_second(dasr_tensor x, dasr_tensor t, dasr_tensor ga, int32_t N, i
 int dasr_bnorm_running(const float* stats, int32_t g, int32_t C, int32_t count, float momentum, float* running_mean, float* running_var,
                        float* num_batches_tracked, void* stream);
 /* GANLoss('vanilla') = BCEWithLogitsLoss vs a constant target (loss.py:8-40): loss_acc += coef*sum(bce),
- * score_acc += score_coef*sum(x) (the disc_Score log), grad = gcoef*(sigmoid(x)-target) */
+ * score_acc += score_coef*sum(x) (the disc_Score log), grad = gcoef*(sigmoid(x)-target) on the C (1..16) real channels of plane 0, zero on the
+ * others (the padding channels of x are never read).  loss_acc, score_acc and grad are optional, each on its own.  DASR_EINVAL: N * H * W <= 0,
+ * C outside 1..16, x null, (dasr_gan_loss) gan_type outside 0..2. */
 int dasr_bce_logits(dasr_tensor x, int32_t N, int32_t C, int32_t H, int32_t W, float target, float coef, float gcoef,
                     float* loss_acc, float* score_acc, float score_coef, dasr_tensor grad, void* stream);
 /* GANLoss(gan_type) (loss.py:8-40; DASR_model.py:35): gan_type 0 'vanilla' (= dasr_bce_logits), 1 'lsgan' (MSELoss: (x-target)^2, grad

@@ -1,6 +1,7 @@
 """Plain torch-CPU references of the small kernels of csrc/misc.hip / csrc/gan.hip (elementwise, pooling, pixel losses, Adam; the frequency-split,
-domain-distance-map and DSN loss kernels), and the NC16HW16 layout plumbing the GPU tests need.  No device code: tests/test_blocked_ref.py holds every
-function here to stock torch on a machine without a GPU; tests/test_gpu_elementwise.py and tests/test_gpu_filters.py then hold the kernels to these.
+domain-distance-map and DSN loss kernels; the normalisation, gradient-penalty and GAN-loss kernels), and the NC16HW16 layout plumbing the GPU tests
+need.  No device code: tests/test_blocked_ref.py holds every function here to stock torch on a machine without a GPU; tests/test_gpu_elementwise.py,
+tests/test_gpu_filters.py and tests/test_gpu_norm_gan.py then hold the kernels to these.
 
 Every reference computes in fp64 on NCHW tensors and returns (value, magnitude): `magnitude` is the per-element sum of the absolute values of the
 terms the kernel adds up, the quantity a rounding-error bound k * u * magnitude is relative to.  Scalars (a, b, slope, coef, ...) are taken as given:
@@ -426,3 +427,451 @@ def sigmoid_bwd(y, g):
     """backward of y = sigmoid(z): gz = g * y * (1 - y)"""
     v = g.double() * y.double() * (1.0 - y.double())
     return v, v.abs()
+
+
+# ---- normalisation, gradient-penalty and GAN-loss kernels (first half of csrc/gan.hip) ------------------------------------------------------
+# These references return Ev pairs: the fp64 value `v` and, beside it, `e`: a running first-order bound of the error of an fp32 evaluation of the
+# same expression, in units of the unit roundoff u32 (as adam's E* above): fl(x op y) = (x op y)(1 + d), |d| <= u, so every operation adds the
+# magnitude of its result and passes its operands' bounds on through its derivative (second-order products of two bounds are kept: they matter where
+# a difference cancels).  A fused multiply-add rounds once where two roundings are counted: the bound holds either way.  Division and sqrtf are
+# correctly rounded (1); expf, logf and log1pf are accurate to 1 ulp = 2 u of their result (the allowance of tests/test_gpu_filters.py for
+# dasr_logloss).  A sum is counted along the kernel's own chain: Ev.sum(dims, L) adds L u sum |terms|, L = the longest chain of roundings behind
+# the total.  What the kernels READ from memory (stats, a, x, gamma, beta, sums, part) is an input here, widened from the fp32 values: never
+# recomputed, so that a LeakyReLU branch is decided from the same bits on both sides.
+# `wrong=`: the deliberately wrong variants tests/test_blocked_ref.py uses to show that the bounds have teeth; None everywhere else.
+TINY32 = 2.0 ** -126                      # smallest normal fp32: the absolute allowance for a result that underflows (flushed or subnormal)
+
+
+def _t64(x):
+    return x.double() if torch.is_tensor(x) else torch.tensor(float(x), dtype=torch.float64)
+
+
+class Ev:
+    __slots__ = ('v', 'e')
+
+    def __init__(self, v, e=None):
+        self.v = _t64(v)
+        self.e = torch.zeros_like(self.v) if e is None else _t64(e) + torch.zeros_like(self.v)
+
+    @staticmethod
+    def of(x):
+        """an exact input (or an Ev as it is)"""
+        return x if isinstance(x, Ev) else Ev(x)
+
+    @staticmethod
+    def rounded(c):
+        """a constant the kernel computes with one rounding (1.f / count, 1.f / slope, 1.f - momentum)"""
+        return Ev(c, abs(c))
+
+    def _bin(self, v, e_in):
+        return Ev(v, e_in + v.abs() + U32 * e_in)     # the propagated bound, one rounding of the result (and of what the bound adds to it)
+
+    def __add__(self, o):
+        o = Ev.of(o)
+        return self._bin(self.v + o.v, self.e + o.e)
+
+    def __sub__(self, o):
+        o = Ev.of(o)
+        return self._bin(self.v - o.v, self.e + o.e)
+
+    def __mul__(self, o):
+        o = Ev.of(o)
+        return self._bin(self.v * o.v, self.v.abs() * o.e + o.v.abs() * self.e + U32 * self.e * o.e)
+
+    __radd__, __rmul__ = __add__, __mul__
+
+    def __rsub__(self, o):
+        return Ev.of(o) - self
+
+    def __truediv__(self, o):
+        o = Ev.of(o)
+        q = self.v / o.v
+        return self._bin(q, (self.e + q.abs() * o.e) / o.v.abs())
+
+    def __rtruediv__(self, o):
+        return Ev.of(o) / self
+
+    def __neg__(self):
+        return Ev(-self.v, self.e)
+
+    def abs(self):
+        return Ev(self.v.abs(), self.e)
+
+    def relu(self):
+        return Ev(self.v.clamp_min(0.0), self.e)
+
+    def sqrt(self):
+        r = self.v.sqrt()
+        return Ev(r, self.e / (2.0 * r) + r)
+
+    def exp(self):
+        r = self.v.exp()
+        return Ev(r, self.e * r + 2.0 * r)
+
+    def log(self, floor=None):
+        """of a positive argument.  Not the linearisation e / v: with d = u32 e the evaluated argument lies in [v - d, v + d], and in [floor, v + d]
+        when the caller knows a floor of it (s + eps >= eps (1 - u) for any fp32 s >= 0), so the result moves by at most log1p(d / v) upwards and
+        -log1p(-d / v) or log(v / floor) downwards (no bound, inf, where d >= v and there is no floor)"""
+        r = self.v.log()
+        d = U32 * self.e
+        down = torch.where(d < self.v, -torch.log1p(-(d / self.v).clamp_max(1.0 - 1e-16)), torch.full_like(r, float('inf')))
+        if floor is not None:
+            down = torch.minimum(down, (self.v / floor).log().clamp_min(0.0))
+        return Ev(r, torch.maximum(torch.log1p(d / self.v), down) / U32 + 2.0 * r.abs())
+
+    def over_plus(self, c):
+        """v / (v + c) for v >= 0 and a constant c > 0, as ONE function of v: numerator and denominator carry the same error of v, which a quotient
+        of two independently bounded operands would count twice and against each other.  d/dv = c / (v + c)^2, largest at the lower end of the
+        interval of v; then the sum (1) and the quotient (1)"""
+        r = self.v / (self.v + c)
+        lo = (self.v - U32 * self.e).clamp_min(0.0)
+        return Ev(r, self.e * c / (lo + c) ** 2 + 2.0 * r.abs())
+
+    def log1p(self):
+        r = self.v.log1p()
+        return Ev(r, self.e / (1.0 + self.v).abs() + 2.0 * r.abs())
+
+    def sum(self, dims, L):
+        """the total over `dims` (kept), reached through at most L roundings per term"""
+        return Ev(self.v.sum(dims, keepdim=True), self.e.sum(dims, keepdim=True) + L * self.v.abs().sum(dims, keepdim=True))
+
+    def where(self, cond, other):
+        other = Ev.of(other)
+        return Ev(torch.where(cond, self.v, other.v + torch.zeros_like(self.v)), torch.where(cond, self.e, other.e + torch.zeros_like(self.e)))
+
+    def __getitem__(self, i):
+        return Ev(self.v[i], self.e[i])
+
+    def tol(self):
+        """the bound |fp32 evaluation - v| <= u32 e (+ the underflow allowance)"""
+        return U32 * self.e + TINY32
+
+
+class F32(Ev):
+    """the same interface evaluated in stock torch fp32 (no bound): under fp32_arithmetic() every reference above runs in it, which is how
+    tests/test_blocked_ref.py shows that plain fp32 arithmetic in another order of summation meets the bounds"""
+    __slots__ = ()
+
+    def __init__(self, v, e=None):
+        self.v = v.float() if torch.is_tensor(v) else torch.tensor(float(v), dtype=torch.float32)
+        self.e = torch.zeros_like(self.v)
+
+    def _bin(self, v, e_in):
+        return F32(v)
+
+    def sum(self, dims, L):
+        return F32(self.v.sum(dims, keepdim=True))
+
+
+class _arithmetic:
+    kind = None
+
+    def __enter__(self):
+        self.prev = globals()['Ev']
+        globals()['Ev'] = self.kind or _Ev64
+
+    def __exit__(self, *exc):
+        globals()['Ev'] = self.prev
+
+
+class fp32_arithmetic(_arithmetic):
+    kind = F32
+
+
+class fp64_arithmetic(_arithmetic):
+    """(inside fp32_arithmetic: what builds INPUTS stays in fp64)"""
+
+
+def ev_cat(parts, dim=0):
+    return Ev(torch.cat([p.v for p in parts], dim), torch.cat([p.e for p in parts], dim))
+
+
+_Ev64 = Ev
+
+
+def lane_chain(count_per_lane):
+    """roundings behind a sum of the norm kernels (one workgroup, 64 pixel lanes per channel quad): the lane's own terms, four xor-butterfly steps
+    over lane bits 2..5, three adds over the four waves"""
+    return count_per_lane + 4 + 3
+
+
+def _lrelu_ev(v, slope):
+    """LeakyReLU of a COMPUTED value: where |v| is within its own bound the fp32 evaluation may take the other branch; both results then lie within
+    that bound of zero and of each other, so the bound passes with factor 1 there"""
+    out = v.where(v.v > 0, v * slope)
+    near = v.v.abs() <= U32 * v.e
+    return Ev(out.v, torch.where(near, v.e + out.v.abs(), out.e))
+
+
+def _norm_stats(X, dims, cnt, T, eps, wrong=None, stat_rows=None):
+    """two-pass statistics over `dims` (kept) as the forward kernels take them: mean = sum / cnt; var = sum (x - mean)^2 / cnt (biased); rstd =
+    1 / sqrt(var + eps).  sum (x - m')^2 / cnt = var + (m' - mean)^2 EXACTLY for any m': the error of the computed mean enters the variance in
+    second order only, which is what is added here (a first-order pass through 2 |d| would not see that the d sum to zero)."""
+    L = lane_chain(T)
+    Xs = X if stat_rows is None else X[stat_rows]
+    inv = Ev.rounded(1.0 / (cnt - 1 if wrong == 'mean_count-1' else cnt))
+    mean = Xs.sum(dims, L) * inv
+    d0 = Xs - mean.v                                   # (x - mean) with the exact mean: one rounding
+    inv_v = Ev.rounded(1.0 / (cnt - 1 if wrong == 'unbiased' else cnt))
+    var = (d0 * d0).sum(dims, L) * inv_v
+    var = Ev(var.v, var.e + U32 * mean.e * mean.e * (1.0 + U32 * L))
+    rstd = 1.0 / (var + (0.0 if wrong == 'no_eps' else eps)).sqrt()
+    return mean, var, rstd
+
+
+def inorm_lrelu_fwd(x, eps, slope, wrong=None):
+    """nn.InstanceNorm2d(affine=False, eps) + LeakyReLU.  Returns (y, mean, rstd) as Ev; mean / rstd [N][C][1][1]."""
+    N, C, H, W = x.shape
+    X = Ev(x)
+    mean, var, rstd = _norm_stats(X, (2, 3), H * W, (H * W + 63) // 64, eps, wrong)
+    return _lrelu_ev((X - mean) * rstd, slope), mean, rstd
+
+
+def _xhat_from_a(a, slope, wrong=None):
+    """xhat from the saved output a = lrelu(xhat), and LeakyReLU' there: a > 0 ? (a, 1) : (a / slope, slope) -- at a == +0 and -0 the slope branch"""
+    A = Ev(a)
+    pos = a.double() >= 0 if wrong == 'lrelu1_at0' else a.double() > 0
+    return pos, A.where(pos, A * Ev.rounded(1.0 / slope))
+
+
+def inorm_lrelu_bwd(a, ga, rstd, slope, wrong=None):
+    """gx = rstd (gy - mean gy - xhat mean(gy xhat)), gy = ga lrelu'(a); rstd [N][C][1][1] as the forward stored it"""
+    N, C, H, W = a.shape
+    L, inv = lane_chain((H * W + 63) // 64), Ev.rounded(1.0 / (H * W))
+    pos, xh = _xhat_from_a(a, slope, wrong)
+    G = Ev(ga)
+    gy = G.where(pos, G * slope)
+    m1, m2 = gy.sum((2, 3), L) * inv, (gy * xh).sum((2, 3), L) * inv
+    return Ev(rstd) * ((gy - m1) - xh * m2)
+
+
+def inorm_lrelu_jvp(a, t, rstd, slope, wrong=None):
+    """out = lrelu'(a) rstd (t - mean t - xhat mean(t xhat))"""
+    N, C, H, W = a.shape
+    L, inv = lane_chain((H * W + 63) // 64), Ev.rounded(1.0 / (H * W))
+    pos, xh = _xhat_from_a(a, slope, wrong)
+    T_ = Ev(t)
+    m1, m2 = T_.sum((2, 3), L) * inv, (T_ * xh).sum((2, 3), L) * inv
+    lp = Ev(torch.where(pos, torch.ones_like(xh.v), torch.full_like(xh.v, slope)))
+    return (lp * Ev(rstd)) * ((T_ - m1) - xh * m2)
+
+
+def _second(xh, w, T_, r2, dims, L, inv, out0, wrong=None):
+    """out0 - r2 [xhat k0 + pz (w - mw) + pw (t - mz)], k0 = mean(w t) - mean w mean t - 3 mean(w xhat) mean(xhat t)"""
+    mw, mz, pw, pz, qq = (s.sum(dims, L) * inv for s in (w, T_, w * xh, xh * T_, w * T_))
+    k0 = (qq - mw * mz) - ((2.0 if wrong == 'factor2' else 3.0) * pw) * pz
+    return Ev.of(out0) - r2 * ((xh * k0 + pz * (w - mw)) + pw * (T_ - mz))
+
+
+def inorm_second(a, t, ga, rstd, slope, out0=None, wrong=None):
+    """the adjoint of z -> J(z) t for fixed t, upstream w = lrelu'(a) ga; out0: what `accumulate` adds to (None: zero)"""
+    N, C, H, W = a.shape
+    L, inv = lane_chain((H * W + 63) // 64), Ev.rounded(1.0 / (H * W))
+    pos, xh = _xhat_from_a(a, slope, wrong)
+    G, R_ = Ev(ga), Ev(rstd)
+    w = G.where(pos, G * slope)
+    return _second(xh, w, Ev(t), R_ * R_, (2, 3), L, inv, torch.zeros_like(xh.v) if out0 is None else out0, wrong)
+
+
+# BatchNorm2d in training mode: groups of `group` consecutive images (the last may be ragged), statistics rows [G][C]
+def groups(N, group):
+    return [(n0, min(N, n0 + group)) for n0 in range(0, N, group)]
+
+
+def _chan(p, C):
+    return _t64(p)[:C].view(1, C, 1, 1)
+
+
+def bnorm_lrelu_fwd(x, group, eps, slope, gamma, beta, wrong=None):
+    """Returns (y [N][C][H][W], z = gamma xhat + beta, mean, rstd, var [G][C]) as Ev"""
+    N, C, H, W = x.shape
+    X, gm, bt = Ev(x), _chan(gamma, C), _chan(beta, C)
+    ys, zs, st = [], [], []
+    for n0, n1 in groups(N, group):
+        # wrong 'ragged_drop': the images of a ragged last group never enter any statistics (they are normalised with the previous group's)
+        rows = slice(n0 - group, n0) if wrong == 'ragged_drop' and n1 - n0 < group else slice(n0, n1)
+        nst = rows.stop - rows.start
+        mean, var, rstd = _norm_stats(X, (0, 2, 3), nst * H * W, nst * ((H * W + 63) // 64), eps, wrong, rows)
+        z = ((X[n0:n1] - mean) * rstd) * gm + bt
+        zs.append(z)
+        ys.append(_lrelu_ev(z, slope))
+        st.append((mean, rstd, var))
+    return (ev_cat(ys), ev_cat(zs)) + tuple(ev_cat([s[i] for s in st])[:, :, 0, 0] for i in range(3))
+
+
+def _bn_group(x, mean, rstd, gamma, beta, g, n0, n1, wrong=None):
+    """xhat and z = gamma xhat + beta of group g, recomputed from the saved x and the statistics rows as the backward kernels do"""
+    C = x.shape[1]
+    row = (mean.shape[0] - 1 - g) if wrong == 'other_row' else g
+    R_ = Ev(_t64(rstd)[row].view(1, C, 1, 1))
+    xh = (Ev(x[n0:n1]) - _t64(mean)[g].view(1, C, 1, 1)) * R_
+    return xh, xh * _chan(gamma, C) + _chan(beta, C), R_
+
+
+def bnorm_lrelu_bwd(x, ga, group, slope, gamma, beta, mean, rstd, pscale=1.0, wrong=None):
+    """per group: gx = gamma rstd (gz - mean gz - xhat mean(gz xhat)), gz = ga lrelu'(z); dgamma = pscale sum over ALL groups of sum gz xhat,
+    dbeta = pscale sum gz.  Returns (gx, dgamma [C], dbeta [C], z)."""
+    N, C, H, W = x.shape
+    gm = _chan(gamma, C)
+    outs, zs, dg, db = [], [], Ev(torch.zeros(1, C, 1, 1)), Ev(torch.zeros(1, C, 1, 1))
+    for g, (n0, n1) in enumerate(groups(N, group)):
+        cnt, L = (n1 - n0) * H * W, lane_chain((n1 - n0) * ((H * W + 63) // 64))
+        inv = Ev.rounded(1.0 / cnt)
+        xh, z, R_ = _bn_group(x, mean, rstd, gamma, beta, g, n0, n1, wrong)
+        G = Ev(ga[n0:n1])
+        gz = G.where(z.v > 0, G * slope)
+        t1, t2 = gz.sum((0, 2, 3), L), (gz * xh).sum((0, 2, 3), L)
+        if g == 0 or wrong != 'dgamma_first':
+            db, dg = (t1 if g == 0 else db + t1), (t2 if g == 0 else dg + t2)      # (0 + t is exact)
+        outs.append((gm * R_) * ((gz - t1 * inv) - xh * (t2 * inv)))
+        zs.append(z)
+    return ev_cat(outs), (dg * pscale)[0, :, 0, 0], (db * pscale)[0, :, 0, 0], ev_cat(zs)
+
+
+def bnorm_lrelu_jvp(x, t, group, slope, gamma, beta, mean, rstd, wrong=None):
+    """out = lrelu'(z) gamma rstd (t - mean t - xhat mean(xhat t)).  Returns (out, z)."""
+    N, C, H, W = x.shape
+    gm = _chan(gamma, C)
+    outs, zs = [], []
+    for g, (n0, n1) in enumerate(groups(N, group)):
+        cnt, L = (n1 - n0) * H * W, lane_chain((n1 - n0) * ((H * W + 63) // 64))
+        inv = Ev.rounded(1.0 / cnt)
+        xh, z, R_ = _bn_group(x, mean, rstd, gamma, beta, g, n0, n1, wrong)
+        T_ = Ev(t[n0:n1])
+        o = (gm * R_) * ((T_ - T_.sum((0, 2, 3), L) * inv) - xh * ((T_ * xh).sum((0, 2, 3), L) * inv))
+        outs.append(o.where(z.v > 0, o * slope))
+        zs.append(z)
+    return ev_cat(outs), ev_cat(zs)
+
+
+def bnorm_second(x, t, ga, group, slope, gamma, beta, mean, rstd, out0=None, dgamma0=None, pscale=1.0, wrong=None):
+    """u = lrelu'(z) ga, w = gamma u: out as inorm_second with group means; dgamma = dgamma0 + pscale sum over groups of
+    rstd count (mean(u t) - mean u mean t - mean(u xhat) mean(xhat t)).  Returns (out, dgamma [C], z)."""
+    N, C, H, W = x.shape
+    gm = _chan(gamma, C)
+    outs, zs, dg = [], [], None
+    for g, (n0, n1) in enumerate(groups(N, group)):
+        cnt, L = (n1 - n0) * H * W, lane_chain((n1 - n0) * ((H * W + 63) // 64))
+        inv = Ev.rounded(1.0 / cnt)
+        xh, z, R_ = _bn_group(x, mean, rstd, gamma, beta, g, n0, n1, wrong)
+        T_, G = Ev(t[n0:n1]), Ev(ga[n0:n1])
+        u = G.where(z.v > 0, G * slope)
+        mu, mz, pu, pz, qu = (s.sum((0, 2, 3), L) * inv for s in (u, T_, u * xh, xh * T_, u * T_))
+        d = (R_ * float(cnt)) * ((qu - mu * mz) - pu * pz)
+        if g == 0 or wrong != 'dgamma_first':
+            dg = d if dg is None else dg + d
+        mw, pw = gm * mu, gm * pu
+        k0 = ((gm * qu) - mw * mz) - ((2.0 if wrong == 'factor2' else 3.0) * pw) * pz
+        w = u * gm
+        o0 = torch.zeros_like(xh.v) if out0 is None else out0[n0:n1]
+        outs.append(Ev.of(o0) - (R_ * R_) * ((xh * k0 + pz * (w - mw)) + pw * (T_ - mz)))
+        zs.append(z)
+    dg = (dg * pscale)[0, :, 0, 0]
+    return ev_cat(outs), (dg if dgamma0 is None else Ev(_t64(dgamma0)[:C]) + dg), ev_cat(zs)
+
+
+def bnorm_running(mean, var, count, momentum, rmean0, rvar0, wrong=None):
+    """nn.BatchNorm2d's running statistics after one training-mode forward: r = (1 - momentum) r + momentum * (mean | UNBIASED variance =
+    biased * count / (count - 1); count 1: the biased one)"""
+    keep = Ev.rounded(1.0 - momentum)
+    corr = Ev.rounded(1.0 if wrong == 'biased' else float(count) / float(count - 1 if count > 1 else 1))
+    return keep * Ev(rmean0) + Ev(mean) * momentum, keep * Ev(rvar0) + (Ev(var) * momentum) * corr
+
+
+def _sigmoid_ev(z):
+    return 1.0 / (1.0 + (-z).exp())
+
+
+def _bce_ev(z, t):
+    """max(z, 0) - z t + log1p(exp(-|z|))"""
+    return (z.relu() - z * t) + (-z.abs()).exp().log1p()
+
+
+def gan_loss(x, gan_type, target, gcoef, wrong=None):
+    """GANLoss(gan_type) against a constant target, per element: 0 BCE-with-logits (d = sigmoid(x) - t), 1 (x - t)^2 (d = 2 (x - t)), 2 -x for t > 0.5
+    else x (d = -+1).  Returns (l, gcoef * d) as Ev; the score term is x itself."""
+    X = Ev(x)
+    if gan_type == 0:
+        return _bce_ev(X, target), gcoef * (_sigmoid_ev(X) - target)
+    if gan_type == 1:
+        d = X - target
+        return d * d, (gcoef * 2.0) * d
+    sgn = -1.0 if (target > 0.5) != (wrong == 'wgan_sign' and target <= 0.5) else 1.0
+    return Ev(sgn * X.v), Ev(torch.full_like(X.v, gcoef * sgn))
+
+
+def _rel_term(z, t, eps, form):
+    """(loss, d loss / dz, score) of one relativistic term, forms as dasr_ragan's"""
+    s = _sigmoid_ev(z)
+    if form == 0:
+        return _bce_ev(z, t), s - t, s
+    if form == 2:
+        d = z - t
+        return d * d, 2.0 * d, s
+    if form == 3:
+        q = -1.0 if t > 0.5 else 1.0
+        return Ev(q * z.v, z.e), Ev(torch.full_like(z.v, q)), s
+    if t < 0:
+        return Ev(torch.zeros_like(z.v)), Ev(torch.zeros_like(z.v)), s
+    if t > 0.5:
+        return -(s + eps).log(eps * (1.0 - U32)), -(s * (1.0 - s)) / (s + eps), s
+    # (the kernel's s (1 - s) / (1 - s + eps): the same three roundings behind s and 1 - s, in another order)
+    return -((1.0 - s) + eps).log(eps * (1.0 - U32)), s * (1.0 - s).over_plus(eps), s
+
+
+def ragan_sums(a, b):
+    """stage 0: per pixel sum_n a, sum_n b of this rank's N samples ([N][1][H][W] -> [1][1][H][W])"""
+    return Ev(a).sum((0,), a.shape[0]), Ev(b).sum((0,), b.shape[0])
+
+
+def ragan_terms(a, b, sums_a, sums_b, n_glob, form, ta, tb, eps, wrong=None):
+    """stage 1 / 2, per local sample and pixel: za = a - sums_b / n_glob, zb = b - sums_a / n_glob and their terms.  sums_*: the GLOBAL per-pixel sums
+    [1][1][H][W] as read from memory.  Returns ((la, da, sa), (lb, db, sb)) as Ev [N][1][H][W]."""
+    inv = Ev.rounded(1.0 / (a.shape[0] if wrong == 'means_N' else n_glob))
+    ma, mb = Ev(sums_a) * inv, Ev(sums_b) * inv
+    return _rel_term(Ev(a) - mb, ta, eps, form), _rel_term(Ev(b) - ma, tb, eps, form)
+
+
+def ragan_grads(da, db, part_a, part_b, n_glob, gcoef, wrong=None):
+    """stage 2: ga = gcoef (da - part_b / n_glob), gb = gcoef (db - part_a / n_glob); part_*: the GLOBAL per-pixel sums of da / db as read from memory"""
+    inv = Ev.rounded(1.0 / n_glob)
+    if wrong == 'swap_part':
+        part_a, part_b = part_b, part_a
+    return gcoef * (da - Ev(part_b) * inv), gcoef * (db - Ev(part_a) * inv)
+
+
+def grad_penalty_sumsq(g):
+    """sum of squares over all images and channels: C products and adds per pixel thread, the wave butterfly (6), the four waves (2), then the
+    non-zero workgroup partials in order (adding a zero partial is exact)"""
+    N, C, H, W = g.shape
+    G = Ev(g)
+    return (G * G).sum((0, 1, 2, 3), C + 6 + 2 + (N * H * W + 255) // 256)[0, 0, 0, 0]
+
+
+def grad_penalty_finish(s, weight, world=1, wrong=None):
+    """from the (all-reduced) sum of squares s: nrm = sqrt(s / world^2), pen = weight (nrm - 1)^2, factor = 2 weight (nrm - 1) / nrm / world (0 at nrm 0)"""
+    s = Ev.of(s)
+    if world != 1:
+        inv_w = Ev.rounded(1.0 / world)
+        s = s if wrong == 'no_world2' else (s * inv_w) * inv_w
+    else:
+        inv_w = Ev(1.0)
+    nrm = s.sqrt() if float(s.v) > 0 else Ev(0.0)
+    d = nrm - 1.0
+    pen = (weight * d) * d
+    fac = ((((2.0 * weight) * d) / nrm) * inv_w) if float(nrm.v) > 0 else Ev(0.0)
+    return nrm, pen, fac
+
+
+def grid_chain(nblocks):
+    """roundings behind a loss accumulator once a workgroup has its thread sums: wave butterfly (6), four waves (3), grid_sum_commit's per-thread
+    loop over ceil(nblocks / 256) partials, butterfly (6), (a + b) + (c + d) (2), * coef (1), the add into the accumulator (1)"""
+    return 6 + 3 + (nblocks + 255) // 256 + 6 + 2 + 1 + 1
+
+
+def acc_sum(terms, coef, acc0, per_thread, nblocks):
+    """acc0 + coef * sum(terms) as a loss / score accumulator holds it: (value, bound).  The per-term bounds, summed, plus the grid-sum convention of
+    tests/test_gpu_elementwise.py::test_l1_diff: L u32 (coef sum |terms| + |acc0|), L = the thread's own `per_thread` terms and the grid chain."""
+    L = per_thread + grid_chain(nblocks)
+    want = acc0 + coef * float(terms.v.sum())
+    return want, U32 * abs(coef) * float(terms.e.sum()) + L * U32 * (abs(coef) * float(terms.v.abs().sum()) + abs(acc0)) + TINY32

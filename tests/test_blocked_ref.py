@@ -1,5 +1,6 @@
-"""CPU checks of oracle/blocked_ref.py, the references tests/test_gpu_elementwise.py and tests/test_gpu_filters.py trust, against stock torch: they
-run where no kernel can."""
+"""CPU checks of oracle/blocked_ref.py, the references tests/test_gpu_elementwise.py, tests/test_gpu_filters.py and tests/test_gpu_norm_gan.py trust,
+against stock torch: they run where no kernel can.  For the normalisation and GAN-loss references also: on the very inputs of the GPU tests
+(oracle/norm_gan_cases.py) stock fp32 arithmetic stays inside every bound and a list of deliberately wrong variants does not."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -356,3 +357,298 @@ def test_logloss_and_sigmoid_bwd_match_autograd(mode, eps):
     (y * go).sum().backward()
     v, mag = R.sigmoid_bwd(y.detach(), go)
     assert torch.allclose(v, z.grad, rtol=1e-14, atol=1e-18) and torch.equal(mag, v.abs())
+
+
+# ---- the normalisation, gradient-penalty and GAN-loss references ----------------------------------------------------------------------------
+from oracle import norm_gan_cases as K  # noqa: E402
+
+SLOPE, EPS = 0.2, 1e-5
+
+
+def close(got, want, rel=1e-12):
+    """agreement to `rel` of the largest magnitude of the tensor"""
+    got, want = (got.v if isinstance(got, R.Ev) else got), want.detach()
+    return got.shape == want.shape and float((got - want).abs().max()) <= rel * max(float(want.abs().max()), 1e-300)
+
+
+def _in(x):
+    return F.leaky_relu(F.instance_norm(x, eps=EPS), SLOPE)
+
+
+def _bn(x, group, gamma, beta):
+    return torch.cat([F.leaky_relu(F.batch_norm(x[n0:n1], None, None, gamma, beta, True, 0.1, EPS), SLOPE) for n0, n1 in R.groups(x.shape[0], group)])
+
+
+def _norm_plain(x, dims, gamma=None, beta=None):
+    """the normalisation + LeakyReLU in elementary torch operations: F.instance_norm / F.batch_norm hand their saved statistics to their double backward
+    as constants, so a derivative of THAT with respect to x (what *_second is) comes out wrong through them; through this form autograd has it all"""
+    mu = x.mean(dims, keepdim=True)
+    xh = (x - mu) / ((x - mu).pow(2).mean(dims, keepdim=True) + EPS).sqrt()
+    return F.leaky_relu(xh if gamma is None else xh * gamma.view(1, -1, 1, 1) + beta.view(1, -1, 1, 1), SLOPE)
+
+
+def _bn_plain(x, group, gamma, beta):
+    return torch.cat([_norm_plain(x[n0:n1], (0, 2, 3), gamma, beta) for n0, n1 in R.groups(x.shape[0], group)])
+
+
+def _first_and_second_order(f, x, t, ga, ga2, params=()):
+    """of y = f(x): (y, J^T ga, J t, d <J t, ga2> / dx, d <J t, ga2> / dparams), the tangent taken by the double-backward trick of
+    tests/test_gpu_wgan.py: J t = d <J^T v, t> / dv"""
+    x = x.clone().requires_grad_(True)
+    y = f(x)
+    gx, = torch.autograd.grad(y, x, ga, retain_graph=True)
+    v = torch.zeros_like(y, requires_grad=True)
+    jt_v, = torch.autograd.grad(y, x, v, create_graph=True)
+    jt, = torch.autograd.grad(jt_v, v, t, create_graph=True)
+    second = torch.autograd.grad((jt * ga2).sum(), (x,) + tuple(params), allow_unused=True)
+    return y.detach(), gx, jt.detach(), second[0], second[1:]
+
+
+@pytest.mark.parametrize('hw', [(1, 3), (7, 10)])
+def test_instance_norm_references_match_autograd(hw):
+    g = gen(40)
+    x = torch.randn(3, 5, *hw, generator=g, dtype=torch.float64) * 1.5 + 0.3
+    t, ga, ga2, out0 = (torch.randn(x.shape, generator=g, dtype=torch.float64) for _ in range(4))
+    y, gx, jt, _, _ = _first_and_second_order(_in, x, t, ga, ga2)
+    y2, gx2, jt2, sec, _ = _first_and_second_order(lambda v: _norm_plain(v, (2, 3)), x, t, ga, ga2)
+    assert close(y2, y) and close(gx2, gx) and close(jt2, jt)
+    yr, mean, rstd = R.inorm_lrelu_fwd(x, EPS, SLOPE)
+    assert close(yr, y) and close(mean, x.mean((2, 3), keepdim=True)) and close(rstd, 1.0 / (x.var((2, 3), unbiased=False, keepdim=True) + EPS).sqrt())
+    # the backward-type references read the saved output and rstd
+    assert close(R.inorm_lrelu_bwd(y, ga, rstd.v, SLOPE), gx)
+    assert close(R.inorm_lrelu_jvp(y, t, rstd.v, SLOPE), jt)
+    assert close(R.inorm_second(y, t, ga2, rstd.v, SLOPE), sec) and close(R.inorm_second(y, t, ga2, rstd.v, SLOPE, out0), sec + out0)
+    # the forward-mode tangent, directly
+    import torch.autograd.forward_ad as fwad
+    with fwad.dual_level():
+        assert close(R.inorm_lrelu_jvp(y, t, rstd.v, SLOPE), fwad.unpack_dual(_in(fwad.make_dual(x, t))).tangent)
+    # at a == +0 and -0: xhat = 0 and LeakyReLU' = slope, as autograd has it for leaky_relu at 0
+    a0 = y.clone()
+    a0[0, 0, 0, 0], a0[1, 1, 0, 1] = 0.0, -0.0
+    lone = torch.zeros_like(ga)
+    lone[0, 0, 0, 0], lone[1, 1, 0, 1] = 1.0, 1.0
+    jv = R.inorm_lrelu_jvp(a0, lone, rstd.v, SLOPE).v
+    cnt = hw[0] * hw[1]
+    for idx in ((0, 0, 0, 0), (1, 1, 0, 1)):
+        assert abs(float(jv[idx]) - SLOPE * float(rstd.v[idx[0], idx[1], 0, 0]) * (1.0 - 1.0 / cnt)) <= 1e-12 * float(rstd.v.max())
+
+
+@pytest.mark.parametrize('ng', [(4, 2), (3, 2), (3, 3), (2, 1)])
+def test_batch_norm_references_match_autograd(ng):
+    N, group = ng
+    g = gen(41)
+    C = 5
+    x = torch.randn(N, C, 7, 10, generator=g, dtype=torch.float64) * 1.5 + 0.3
+    gamma = (torch.rand(C, generator=g, dtype=torch.float64) + 0.5) * torch.tensor([1.0, -1.0, 1.0, 1.0, -1.0], dtype=torch.float64)
+    beta = torch.randn(C, generator=g, dtype=torch.float64) * 0.3
+    t, ga, ga2, out0 = (torch.randn(x.shape, generator=g, dtype=torch.float64) for _ in range(4))
+    gm, bt = gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True)
+    y, gx, jt, _, _ = _first_and_second_order(lambda v: _bn(v, group, gm, bt), x, t, ga, ga2, (gm, bt))
+    y2, gx2, jt2, sec, (sec_g, sec_b) = _first_and_second_order(lambda v: _bn_plain(v, group, gm, bt), x, t, ga, ga2, (gm, bt))
+    assert close(y2, y) and close(gx2, gx) and close(jt2, jt)
+    yr, z, mean, rstd, var = R.bnorm_lrelu_fwd(x, group, EPS, SLOPE, gamma, beta)
+    G = len(R.groups(N, group))
+    assert close(yr, y) and mean.v.shape == (G, C) and G == -(-N // group)
+    for gi, (n0, n1) in enumerate(R.groups(N, group)):
+        assert close(mean.v[gi], x[n0:n1].mean((0, 2, 3))) and close(var.v[gi], x[n0:n1].var((0, 2, 3), unbiased=False))
+        assert close(rstd.v[gi], 1.0 / (x[n0:n1].var((0, 2, 3), unbiased=False) + EPS).sqrt())
+    xr = x.clone().requires_grad_(True)
+    _bn(xr, group, gm, bt).backward(ga)
+    gxr, dg, db, _ = R.bnorm_lrelu_bwd(x, ga, group, SLOPE, gamma, beta, mean.v, rstd.v, 0.37)
+    assert close(gxr, gx) and close(dg, 0.37 * gm.grad) and close(db, 0.37 * bt.grad)
+    assert close(R.bnorm_lrelu_jvp(x, t, group, SLOPE, gamma, beta, mean.v, rstd.v)[0], jt)
+    out, dg2, _ = R.bnorm_second(x, t, ga2, group, SLOPE, gamma, beta, mean.v, rstd.v, None, None, 0.37)
+    assert close(out, sec) and close(dg2, 0.37 * sec_g) and (sec_b is None or float(sec_b.abs().max()) == 0.0)     # beta has no term
+    d0 = torch.randn(C, generator=g, dtype=torch.float64)
+    out, dg2, _ = R.bnorm_second(x, t, ga2, group, SLOPE, gamma, beta, mean.v, rstd.v, out0, d0, 0.37)
+    assert close(out, sec + out0) and close(dg2, d0 + 0.37 * sec_g)
+
+
+@pytest.mark.parametrize('n_hw', [(2, 5, 7), (1, 1, 1)])
+def test_running_statistics_are_batchnorm2d_state(n_hw):
+    N, H, W = n_hw
+    g = gen(42)
+    C = 5
+    bn = torch.nn.BatchNorm2d(C, eps=EPS, momentum=0.1).double()
+    bn.running_mean.copy_(torch.randn(C, generator=g, dtype=torch.float64))
+    bn.running_var.copy_(torch.rand(C, generator=g, dtype=torch.float64) + 0.5)
+    rm0, rv0 = bn.running_mean.clone(), bn.running_var.clone()
+    x = torch.randn(N, C, H, W, generator=g, dtype=torch.float64)
+    if N * H * W > 1:
+        bn.train()(x)
+        rm, rv = R.bnorm_running(x.mean((0, 2, 3)), x.var((0, 2, 3), unbiased=False), N * H * W, 0.1, rm0, rv0)
+        assert close(rm, bn.running_mean, 1e-12) and close(rv, bn.running_var, 1e-12) and int(bn.num_batches_tracked) == 1
+        assert not close(R.bnorm_running(x.mean((0, 2, 3)), x.var((0, 2, 3), unbiased=False), N * H * W, 0.1, rm0, rv0, 'biased')[1], bn.running_var, 1e-3)
+    else:       # one element per channel (torch refuses to train on it): the correction count / (count - 1) is left out, the variance 0 enters as it is
+        rm, rv = R.bnorm_running(x.mean((0, 2, 3)), torch.zeros(C), 1, 0.1, rm0, rv0)
+        assert close(rm, 0.9 * rm0 + 0.1 * x.view(C)) and close(rv, 0.9 * rv0)
+
+
+@pytest.mark.parametrize('target', [1.0, 0.0, 0.9])
+def test_gan_loss_types_match_torch(target):
+    x = (torch.randn(2, 3, 5, 7, generator=gen(43), dtype=torch.float64) * 3.0).requires_grad_(True)
+    tt = torch.full_like(x, target)
+    for gan_type, lossf in ((0, lambda: F.binary_cross_entropy_with_logits(x, tt, reduction='none')), (1, lambda: F.mse_loss(x, tt, reduction='none')),
+                            (2, lambda: -x if target > 0.5 else x)):
+        l = lossf()
+        gr, = torch.autograd.grad(l.sum() * 0.3, x)
+        lr, grr = R.gan_loss(x.detach(), gan_type, target, 0.3)
+        assert close(lr, l) and close(grr, gr)
+        # (torch's own mean-reduced criteria: the mean is coef = 1 / numel)
+        crit = (torch.nn.BCEWithLogitsLoss(), torch.nn.MSELoss(), None)[gan_type]
+        mean = crit(x, tt) if crit else (-x if target > 0.5 else x).mean()
+        assert abs(float(lr.v.sum()) / x.numel() - float(mean.detach())) <= 1e-12 * abs(float(mean.detach()))
+
+
+def _ragan_term_torch(z, t, eps, form):
+    if form == 0:
+        return F.binary_cross_entropy_with_logits(z, torch.full_like(z, t), reduction='none')
+    if form == 2:
+        return (z - t) ** 2
+    if form == 3:
+        return -z if t > 0.5 else z
+    if t < 0:
+        return z * 0.0
+    s = torch.sigmoid(z)
+    return -torch.log(s + eps) if t > 0.5 else -torch.log(1.0 - s + eps)
+
+
+@pytest.mark.parametrize('form,ta,tb', [(0, 1.0, 0.0), (0, 0.9, 0.0), (1, 1.0, 0.0), (1, 0.0, 1.0), (1, 0.0, -1.0), (2, 1.0, 0.0), (3, 1.0, 0.0), (3, 0.0, 1.0)])
+def test_ragan_forms_match_autograd_through_the_global_means(form, ta, tb):
+    """n_glob = 6 > N = 2: the remote samples enter the per-pixel means, and the LOCAL gradient of the GLOBAL loss holds their terms through the
+    means (part_* / n_glob) while their own direct terms stay on their rank"""
+    g = gen(44)
+    eps, gcoef, NG, NL = 1e-8, 0.3, 6, 2
+    a_all, b_all = (torch.randn(NG, 1, 5, 7, generator=g, dtype=torch.float64) * 3.0 for _ in range(2))
+    a, b = a_all[:NL].clone().requires_grad_(True), b_all[:NL].clone().requires_grad_(True)
+    aa, bb = torch.cat([a, a_all[NL:]]), torch.cat([b, b_all[NL:]])
+    za, zb = aa - bb.mean(0, keepdim=True), bb - aa.mean(0, keepdim=True)
+    la, lb = _ragan_term_torch(za, ta, eps, form), _ragan_term_torch(zb, tb, eps, form)
+    ga, gb = torch.autograd.grad((la.sum() + lb.sum()) * gcoef, (a, b))
+    sums_a, sums_b = aa.detach().sum(0, keepdim=True), bb.detach().sum(0, keepdim=True)
+    ad, bd = a.detach(), b.detach()
+    s0a, s0b = R.ragan_sums(ad, bd)
+    assert close(s0a, ad.sum(0, keepdim=True)) and close(s0b, bd.sum(0, keepdim=True))
+    (lar, da, sa), (lbr, db, sb) = R.ragan_terms(ad, bd, sums_a, sums_b, NG, form, ta, tb, eps)
+    assert close(lar, la[:NL]) and close(lbr, lb[:NL]) and close(sa, torch.sigmoid(za[:NL])) and close(sb, torch.sigmoid(zb[:NL]))
+    (_, rda, _), (_, rdb, _) = R.ragan_terms(a_all[NL:], b_all[NL:], sums_a, sums_b, NG, form, ta, tb, eps)
+    part_a, part_b = da.v.sum(0, keepdim=True) + rda.v.sum(0, keepdim=True), db.v.sum(0, keepdim=True) + rdb.v.sum(0, keepdim=True)
+    gar, gbr = R.ragan_grads(da, db, part_a, part_b, NG, gcoef)
+    assert close(gar, ga) and close(gbr, gb)
+    if not (form == 1 and tb < 0):        # without the remote samples' share of part_b the gradient is another one
+        assert not close(R.ragan_grads(da, db, da.v.sum(0, keepdim=True), db.v.sum(0, keepdim=True), NG, gcoef)[0], ga, 1e-6)
+
+
+@pytest.mark.parametrize('world', [1, 2])
+def test_grad_penalty_matches_autograd(world):
+    g = gen(45)
+    gr = [(torch.randn(2, 3, 5, 7, generator=g, dtype=torch.float64) * 0.05).requires_grad_(True) for _ in range(world)]
+    # the gradient of the GLOBAL mean output restricted to a rank's samples is g_r / world
+    nrm = torch.cat([t.reshape(-1) for t in gr]).div(world).norm()
+    pen = 10.0 * (nrm - 1.0) ** 2
+    dg, = torch.autograd.grad(pen, gr[0])
+    s = sum(float(R.grad_penalty_sumsq(t.detach()).v) for t in gr)
+    assert close(R.grad_penalty_sumsq(gr[0].detach()), (gr[0].detach() ** 2).sum())
+    nr, pr, fac = R.grad_penalty_finish(s, 10.0, world)
+    assert close(nr, nrm) and close(pr, pen)
+    # d pen / d g_0 = fac * g_0 / world: the factor in front of this rank's gradient, its other 1 / world carried by the weight-gradient reductions
+    assert close(float(fac.v) * gr[0].detach() / world, dg)
+    z = R.grad_penalty_finish(0.0, 10.0, world)
+    assert float(z[0].v) == 0.0 and float(z[1].v) == 10.0 and float(z[2].v) == 0.0 and float(z[2].e) == 0.0
+
+
+# ---- the bounds on the inputs of tests/test_gpu_norm_gan.py: sound (stock fp32 arithmetic meets them) and with teeth (wrong variants do not) --------
+EVALS = list(K.evals())
+WRONG = ['mean_count-1', 'unbiased', 'no_eps', 'other_row', 'ragged_drop', 'lrelu1_at0', 'factor2', 'dgamma_first', 'biased', 'means_N', 'swap_part',
+         'wgan_sign', 'no_world2']
+
+
+def _worst(got, ref):
+    """largest |got - ref| / bound over the outputs; nan counts as outside"""
+    worst = 0.0
+    for k, r in ref.items():
+        q = (got[k].v.double() - r.v).abs() / r.tol()
+        worst = max(worst, float('inf') if bool(torch.isnan(q).any()) else float(q.max()))
+    return worst
+
+
+@pytest.mark.parametrize('case', EVALS, ids=[e[0] for e in EVALS])
+def test_bounds_are_sound_and_have_teeth(case):
+    _, fn, args, wrong = case
+    inputs, ref = fn(*args)
+    for r in ref.values():
+        assert bool(torch.isfinite(r.v).all()) and bool(torch.isfinite(r.e).all()) and bool((r.e >= 0).all())
+    with R.fp32_arithmetic():
+        inputs32, got = fn(*args)
+    assert all(torch.equal(inputs[k], inputs32[k]) for k in inputs if torch.is_tensor(inputs[k]))      # the same inputs
+    assert all(g.v.dtype == torch.float32 for g in got.values())
+    assert _worst(got, ref) <= 1.0, _worst(got, ref)
+    if 'z_margin' in inputs:              # no recomputed z near its LeakyReLU branch (see norm_gan_cases.bn_saved)
+        assert inputs['z_margin'] > 1.0
+    for w in wrong:
+        assert w in WRONG
+        assert _worst(fn(*args, wrong=w)[1], ref) > 1.0, w
+
+
+def test_every_wrong_variant_is_exercised():
+    assert {w for e in EVALS for w in e[3]} == set(WRONG)
+
+
+@pytest.mark.parametrize('hw', K.NORM_HW)
+@pytest.mark.parametrize('C', K.NORM_C)
+def test_stock_forward_norms_meet_the_bounds(C, hw):
+    """F.instance_norm / F.batch_norm + F.leaky_relu in fp32 (torch's own order of summation) on the GPU tests' forward inputs"""
+    x = K.in_fwd(C, *hw)
+    y, mean, rstd = R.inorm_lrelu_fwd(x, K.EPS, K.SLOPE)
+    got = F.leaky_relu(F.instance_norm(x, eps=K.EPS), K.SLOPE)
+    assert bool(((got.double() - y.v).abs() <= y.tol()).all())
+    assert bool(torch.isfinite(y.v[:, K.CONST]).all()) and bool((y.v[:, K.CONST] == 0).all())          # the constant channel: exactly zero, finite bound
+    # ... whose bound is rstd * (the bound of the mean), up to the roundings of the difference and the product
+    assert bool((y.tol()[:, K.CONST] <= 1.01 * (rstd.v * mean.tol())[:, K.CONST] + R.TINY32).all())
+    for N, group in K.BN_NG:
+        i = K.bn_fwd(N, group, C, *hw)
+        yb = R.bnorm_lrelu_fwd(i['x'], group, K.EPS, K.SLOPE, i['gamma'], i['beta'])[0]
+        got = _bn(i['x'], group, i['gamma'], i['beta'])
+        assert bool(((got.double() - yb.v).abs() <= yb.tol()).all())
+
+
+@pytest.mark.parametrize('hw', K.PIX_HW)
+@pytest.mark.parametrize('gan_type', [0, 1])
+def test_accumulator_bound_holds_for_an_fp32_sum(gan_type, hw):
+    """coef * (fp32 sum of the fp32 terms) + acc0, all in stock fp32, inside the bound the GPU tests put on the loss accumulators"""
+    for C in K.PIX_C:
+        i, ref = K.ref_gan_loss(gan_type, 1.0, C, *hw)
+        coef = K.gan_coefs(C, *hw)[0]
+        with R.fp32_arithmetic():
+            l32 = K.ref_gan_loss(gan_type, 1.0, C, *hw)[1]['l'].v
+        got = torch.tensor(0.25) + torch.tensor(coef) * l32.sum()
+        want, bound = R.acc_sum(ref['l'], coef, 0.25, C, (K.PIX_N * hw[0] * hw[1] + 255) // 256)
+        assert abs(float(got) - want) <= bound and bound < 1e-5 * abs(want)
+
+
+def test_every_accumulator_bound_is_tight():
+    """every (value, bound) the GPU file applies to a loss / score accumulator: the bound stays below 2e-5 of coef sum |terms| + |acc0|, the scale the
+    grid-sum convention L u32 (coef sum |terms| + |acc0|) is relative to (L <= 24 here: 1.5e-6; the rest is the terms' own bounds, largest for the
+    -log terms of ragan form 1).  A bound of per cents -- what a saturated sigmoid under -log(1 - s + eps) would make of it -- fails here."""
+    def tight(accs, scales):
+        for k, (want, bound) in accs.items():
+            assert bound <= 2e-5 * scales[k], (k, want, bound, scales[k])
+    for C in K.PIX_C:
+        for H, W in K.PIX_HW:
+            coef, _, scoef = K.gan_coefs(C, H, W)
+            for gt in (0, 1, 2):
+                for t in K.TARGETS:
+                    i, ref = K.ref_gan_loss(gt, t, C, H, W)
+                    tight(K.gan_accs(gt, t, C, H, W), dict(loss=coef * float(ref['l'].v.abs().sum()) + abs(K.ACC0['loss']),
+                                                           score=scoef * float(i['x'].double().abs().sum()) + abs(K.ACC0['score'])))
+    for H, W in K.RAGAN_HW:
+        coef, _, scoef = K.gan_coefs(1, H, W)
+        for form, ts in K.RAGAN_T.items():
+            for ta, tb in ts:
+                i, ref = K.ref_ragan(form, ta, tb, H, W)
+                tight(K.ragan_accs(form, ta, tb, H, W), dict(loss=coef * float(ref['la'].v.abs().sum() + ref['lb'].v.abs().sum()) + abs(K.ACC0['loss']),
+                                                             score_a=scoef * float(ref['score_a'].v.abs().sum()) + abs(K.ACC0['score']),
+                                                             score_b=scoef * float(ref['score_b'].v.abs().sum()) + abs(K.ACC0['score_b'])))
+                # the gradients' bounds, too, stay first-order small against the largest gradient
+                for k in ('ga', 'gb'):
+                    assert float(ref[k].tol().max()) <= 1e-4 * float(ref[k].v.abs().max()) + R.TINY32, (form, ta, tb, k)

@@ -67,6 +67,22 @@ def _entries():
         'bilinear_up': (L.OP_BILINEAR, ['src', 'N', 'h', 'w', 'factor', 'dst']),
         'logloss': (L.OP_LOGLOSS, ['x', 'N', 'H', 'W', 'mode', 'eps', 'coef', 'gcoef', 'loss_acc', 'score_acc', 'score_coef', 'grad', 'accumulate']),
         'sigmoid_bwd': (L.OP_SIGMOID_BWD, ['y', 'g', 'N', 'C', 'H', 'W', 'gz']),
+        # tests/test_gpu_norm_gan.py
+        'inorm_lrelu_fwd': (L.OP_INORM_FWD, ['x', 'N', 'C', 'H', 'W', 'eps', 'slope', 'y', 'stats']),
+        'inorm_lrelu_bwd': (L.OP_INORM_BWD, ['a', 'ga', 'N', 'C', 'H', 'W', 'slope', 'stats', 'gx']),
+        'inorm_lrelu_jvp': (L.OP_INORM_JVP, ['a', 't', 'N', 'C', 'H', 'W', 'slope', 'stats', 'out']),
+        'inorm_second': (L.OP_INORM_SECOND, ['a', 't', 'ga', 'N', 'C', 'H', 'W', 'slope', 'stats', 'out', 'accumulate']),
+        'grad_penalty': (L.OP_GRAD_PENALTY, ['g', 'N', 'C', 'H', 'W', 'weight', 'part256', 'out3', 'loss_acc', 'stage', 'world']),
+        'fill_scaled': (L.OP_FILL_SCALED, ['x', 'N', 'C', 'H', 'W', 'scalar', 'factor']),
+        'bnorm_lrelu_fwd': (L.OP_BNORM_FWD, ['x', 'N', 'C', 'H', 'W', 'group', 'eps', 'slope', 'gamma', 'beta', 'y', 'stats']),
+        'bnorm_lrelu_bwd': (L.OP_BNORM_BWD, ['x', 'ga', 'N', 'C', 'H', 'W', 'group', 'slope', 'gamma', 'beta', 'stats', 'gx', 'dgamma', 'dbeta', 'pscale']),
+        'bnorm_lrelu_jvp': (L.OP_BNORM_JVP, ['x', 't', 'N', 'C', 'H', 'W', 'group', 'slope', 'gamma', 'beta', 'stats', 'out']),
+        'bnorm_second': (L.OP_BNORM_SECOND, ['x', 't', 'ga', 'N', 'C', 'H', 'W', 'group', 'slope', 'gamma', 'beta', 'stats', 'out', 'accumulate', 'dgamma',
+                                             'pscale']),
+        'bnorm_running': (L.OP_BNORM_RUNNING, ['stats', 'g', 'C', 'count', 'momentum', 'running_mean', 'running_var', 'num_batches_tracked']),
+        'gan_loss': (L.OP_BCE, ['x', 'N', 'C', 'H', 'W', 'gan_type', 'target', 'coef', 'gcoef', 'loss_acc', 'score_acc', 'score_coef', 'grad']),
+        'ragan': (L.OP_RAGAN, ['a', 'b', 'N', 'H', 'W', 'stage', 'n_glob', 'form', 'ta', 'tb', 'coef', 'gcoef', 'eps', 'sums', 'part', 'loss_acc', 'score_a',
+                               'score_b', 'score_coef', 'ga', 'gb']),
     }
 
 
