@@ -1547,7 +1547,7 @@ extern "C" int dasr_sigmoid_fwd(dasr_tensor x, int32_t N, int32_t C, int32_t H, 
 
 extern "C" int dasr_prelu_grad(dasr_tensor y, dasr_tensor gx, int32_t N, int32_t C, int32_t H, int32_t W, const float* slope, float* scratch256,
                                float* dst, float scale, void* stream) {
-    if ((long long)N * C * H * W <= 0) return DASR_EINVAL;
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || !y.p || !gx.p || !slope || !scratch256 || !dst) return DASR_EINVAL;
     // 1024 workgroups (4 per CU: the streaming read of two tensors needs the occupancy), one partial each; `scratch256` holds 1024 floats
     const long long vec = (long long)N * ((C + 15) / 16) * H * W * 4;
     const int nb = (int)(vec < 1024LL * 256 ? (vec + 255) / 256 : 1024);
@@ -1565,7 +1565,7 @@ extern "C" int dasr_prelu_final(const float* partial, int32_t nblocks, int64_t s
 
 extern "C" int dasr_prelu_grad_f16(dasr_tensor y, dasr_tensor gx, int32_t N, int32_t C, int32_t H, int32_t W, const float* slope, float* scratch256,
                                    float* dst, float scale, void* stream) {
-    if ((long long)N * C * H * W <= 0) return DASR_EINVAL;
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || !y.p || !gx.p || !slope || !scratch256 || !dst) return DASR_EINVAL;
     const long long vec = (long long)N * ((C + 15) / 16) * H * W * 4;
     const int nb = (int)(vec < 1024LL * 256 ? (vec + 255) / 256 : 1024);
     DASR_LAUNCH(prelu_grad_partial_kernel<f16_t>, dim3(nb), dim3(256), 0, as_stream(stream), y, gx, N, C, H, W, scratch256);

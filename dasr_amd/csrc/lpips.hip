@@ -227,6 +227,7 @@ extern "C" int dasr_lpips_s2d(dasr_tensor x, int32_t N, int32_t H, int32_t W, co
                               void* stream) {
     const int xf = (mode >> 4) & 7;   // bits 4-6: symmetry of the square applied in front of the network (transpose, flip rows, flip columns)
     mode &= 15;
+    if (!x.p || !y.p || !scale4 || !shift4) return DASR_EINVAL;   // scale4 / shift4 are read here, on the host
     if (N <= 0 || H <= 0 || W <= 0 || (H & 3) || (W & 3) || (mode != 0 && mode != 1) || ((xf & 1) && H != W)) return DASR_EINVAL;
     const int Hs = (H + 4) >> 2, Ws = (W + 4) >> 2;
     const long long total = mode == 0 ? (long long)N * 3 * Hs * Ws * 4 : (long long)N * H * W;
@@ -236,7 +237,7 @@ extern "C" int dasr_lpips_s2d(dasr_tensor x, int32_t N, int32_t H, int32_t W, co
 }
 
 extern "C" int dasr_maxpool3s2(dasr_tensor x, int32_t N, int32_t C, int32_t H, int32_t W, dasr_tensor y, void* stream) {
-    if (N <= 0 || C <= 0 || H < 3 || W < 3) return DASR_EINVAL;
+    if (N <= 0 || C <= 0 || H < 3 || W < 3 || !x.p || !y.p) return DASR_EINVAL;
     const long long total = (long long)N * ((C + 15) / 16) * ((H - 3) / 2 + 1) * ((W - 3) / 2 + 1) * 4;
     DASR_LAUNCH(maxpool3s2_fwd_kernel, dim3(nblk(total)), dim3(256), 0, as_stream(stream), x, N, C, H, W, y);
     return (int)hipGetLastError();
@@ -244,7 +245,7 @@ extern "C" int dasr_maxpool3s2(dasr_tensor x, int32_t N, int32_t C, int32_t H, i
 
 extern "C" int dasr_maxpool3s2_bwd(dasr_tensor x, dasr_tensor gy, int32_t N, int32_t C, int32_t H, int32_t W, dasr_tensor gx, int32_t relu_mask,
                                    int32_t accumulate, void* stream) {
-    if (N <= 0 || C <= 0 || H < 3 || W < 3) return DASR_EINVAL;
+    if (N <= 0 || C <= 0 || H < 3 || W < 3 || !x.p || !gy.p || !gx.p) return DASR_EINVAL;
     const long long total = (long long)N * ((C + 15) / 16) * H * W * 4;
     DASR_LAUNCH(maxpool3s2_bwd_kernel, dim3(nblk(total)), dim3(256), 0, as_stream(stream), x, gy, N, C, H, W, gx, relu_mask, accumulate);
     return (int)hipGetLastError();
@@ -252,7 +253,7 @@ extern "C" int dasr_maxpool3s2_bwd(dasr_tensor x, dasr_tensor gy, int32_t N, int
 
 extern "C" int dasr_lpips_head(dasr_tensor f, int64_t pair_off, int32_t N, int32_t C, int32_t H, int32_t W, const float* lin, float eps, float coef,
                                float gcoef, float* loss_acc, dasr_tensor g0, int32_t relu_mask, void* stream) {
-    if (N <= 0 || C <= 0 || (C & 15) || H <= 0 || W <= 0 || !lin) return DASR_EINVAL;
+    if (N <= 0 || C <= 0 || (C & 15) || H <= 0 || W <= 0 || !lin || !f.p) return DASR_EINVAL;
     const long long total = (long long)N * H * W;
     const dasr_red rs = dasr_red_scratch(loss_acc, as_stream(stream), nblk(total), 1);
     if (loss_acc && !rs.part) return dasr_red_error();

@@ -602,7 +602,7 @@ __global__ void gather_crops_kernel(const dasr_crop_desc* __restrict__ descs, in
 
 extern "C" int dasr_gather_crops(const dasr_crop_desc* descs_dev, int32_t n, int32_t C, int32_t size, float* dst, void* stream) {
     const long long total = (long long)n * C * size * size;
-    if (total <= 0 || !descs_dev || !dst) return DASR_EINVAL;
+    if (n <= 0 || C <= 0 || size <= 0 || !descs_dev || !dst) return DASR_EINVAL;
     DASR_LAUNCH(gather_crops_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, as_stream(stream), descs_dev, n, C, size, dst);
     return (int)hipGetLastError();
 }

@@ -442,16 +442,41 @@ int dasr_bilinear_up(const float* src, int32_t N, int32_t h, int32_t w, int32_t 
  * (H+4)/4 x (W+4)/4 -- the 11x11/s4/p2 conv becomes 3x3/s1/p0 on 48 channels.  mode 1: adjoint, ACCUMULATED into channels 0..2 of x.
  * mode bits 4-6 (DSN --lpips_rot_flip, PerceptualLoss.forward codes/DSN/loss.py:155-168: torch.rot90 / torch.flip of both images in front of
  * LPIPS): the network sees T(x), T(x)[i][j] = x[u][v], (u, v) = (i, j) swapped if bit 4, u -> H-1-u if bit 5, v -> W-1-v if bit 6; mode 1 routes
- * the gradient back through the same map.  Transposing forms need H == W. */
+ * the gradient back through the same map.  Transposing forms need H == W.
+ * Contracts (tests/test_gpu_lpips_prelu.py):
+ *  - mode 0 reads channels 0..2 of plane 0 of x (channels 3..15 and other planes are never read) and writes all 16 slots of exactly 3 planes of y; where the
+ *    padded grid lies outside the image y holds +0 bit for bit (the zero padding is applied to the SCALED image: a border pixel is 0, not shift4[c]).
+ *  - mode 1 adds scale4[c] * (the slot pixel (u, v) of x went to) into channels 0..2 of plane 0 of x; channels 3..15 and every other plane keep their bits; y is
+ *    read only.  With a symmetry the gradient of T(x)[i][j] returns to x[u][v]: the INVERSE of the index map mode 0 reads through (the two differ for the quarter turns).
+ *  - scale4 / shift4: HOST pointers to 4 floats (3 used), read by the launcher.
+ *  - DASR_EINVAL, nothing launched or dereferenced: N, H or W <= 0; H or W not a multiple of 4; (mode & 15) outside {0, 1}; a transposing code with H != W; x, y,
+ *    scale4 or shift4 null. */
 int dasr_lpips_s2d(dasr_tensor x, int32_t N, int32_t H, int32_t W, const float* scale4, const float* shift4, dasr_tensor y, int32_t mode,
                    void* stream);
 /* nn.MaxPool2d(3, 2) of torchvision alexnet.features[2] / [5] on H x W inputs (output (H-3)/2+1), and its backward: gather form, first
- * maximum in scan order wins (ATen); relu_mask: zero where x <= 0; accumulate: gx += (the head gradient of that layer is already there) */
+ * maximum in scan order wins (ATen); relu_mask: zero where x <= 0; accumulate: gx += (the head gradient of that layer is already there).
+ * Contracts (tests/test_gpu_lpips_prelu.py):
+ *  - whole 16-channel planes are processed, the padding channels of the last plane like real ones -- zero in, zero out.
+ *  - inputs are finite and above -3.4e38 (the running maximum starts there); the forward moves the maximum (equal to MaxPool2d by value).
+ *  - ties: the FIRST maximum of a window in scan order (rows, then columns) receives that window's gradient; a pixel receives the gradients of those of its (at most
+ *    2 x 2) windows whose first maximum it is, added in window order (rows, then columns).
+ *  - relu_mask != 0: a pixel with x <= 0 (+0 and -0 included) receives nothing -- gx is exact zero there, or keeps its value when accumulating; the windows that
+ *    are all zero hand nothing on.  relu_mask == 0: no mask.
+ *  - the backward writes EVERY pixel of the C planes of gx: a row / column no window covers (even H or W) gets exact +0, or keeps its value when accumulating.
+ *  - DASR_EINVAL, nothing launched: N or C <= 0; H or W < 3; x, y (forward), x, gy or gx (backward) null. */
 int dasr_maxpool3s2(dasr_tensor x, int32_t N, int32_t C, int32_t H, int32_t W, dasr_tensor y, void* stream);
 int dasr_maxpool3s2_bwd(dasr_tensor x, dasr_tensor gy, int32_t N, int32_t C, int32_t H, int32_t W, dasr_tensor gx, int32_t relu_mask,
                         int32_t accumulate, void* stream);
 /* one LPIPS layer: images n < N of f are compared with images n + pair_off; u = f0/(|f0|_2+eps), v likewise (normalize_tensor),
- * loss_acc += coef * sum_pixels sum_c lin[c] (u_c-v_c)^2;  g0 (optional) = gcoef * d(sum)/df0, zeroed where f0 <= 0 when relu_mask */
+ * loss_acc += coef * sum_pixels sum_c lin[c] (u_c-v_c)^2;  g0 (optional) = gcoef * d(sum)/df0, zeroed where f0 <= 0 when relu_mask.
+ * Contracts (tests/test_gpu_lpips_prelu.py):
+ *  - only images [0, N) and [pair_off, pair_off + N) of f are read (pair_off need not be N); features of either sign are accepted; lin: C floats on the device.
+ *  - g0 null: the loss alone; otherwise all C channels of N images of g0 are written.  relu_mask != 0: g0 is exact zero where f0 <= 0 (+0 and -0 included), whatever f1 holds.
+ *  - a pixel whose f0 is all zero: u = 0 and the derivative of the norm is taken as 0 at the origin (k2 = 0), so g0_c = gcoef 2 lin[c] (0 - v_c) / eps there: large
+ *    (eps = 1e-10) but finite, and zero when f1 is all zero too (such a pixel adds nothing to the loss).
+ *  - loss_acc is added to (whatever it holds) through a fixed-order sum over the grid: the same inputs give the same bits in loss_acc and g0 on every run.
+ *    loss_acc may be null (the gradient alone).
+ *  - DASR_EINVAL, nothing launched: N, C, H or W <= 0; C not a multiple of 16; f or lin null. */
 int dasr_lpips_head(dasr_tensor f, int64_t pair_off, int32_t N, int32_t C, int32_t H, int32_t W, const float* lin, float eps, float coef,
                     float gcoef, float* loss_acc, dasr_tensor g0, int32_t relu_mask, void* stream);
 
@@ -476,7 +501,14 @@ int dasr_sigmoid_bwd(dasr_tensor y, dasr_tensor g, int32_t N, int32_t C, int32_t
  * consumed by create_dataset_modified.py:14-24) */
 int dasr_sigmoid_fwd(dasr_tensor x, int32_t N, int32_t C, int32_t H, int32_t W, dasr_tensor y, void* stream);
 /* gradient of nn.PReLU()'s single slope (model.py:29,215) from the layer output y and dL/dx; deterministic two-stage sum;
- * scratch256: 1024 floats (one partial per workgroup of the first stage; the name is historical) */
+ * scratch256: 1024 floats (one partial per workgroup of the first stage; the name is historical).
+ * Contracts of the three slope-gradient entry points (tests/test_gpu_lpips_prelu.py):
+ *  - *dst = scale * sum_{y <= 0} gx * y / a^2, a = *slope, over whole 16-channel planes (padding channels: zero in y and gx).  At y == +0 and -0 the term is an exact
+ *    zero: the entry points are indifferent to `y <= 0` versus `y < 0` for finite gx, and no test tells the two apart.
+ *  - every term is rounded to fp32 once (exact for f16 inputs), both stages sum per thread in double in a fixed order and finish with a fixed tree: deterministic, and
+ *    accurate relative to sum |terms| (the total is a small difference of large sums).
+ *  - the first stage runs min(1024, ceil(vector loads / 256)) workgroups (a grid-stride loop beyond that) and writes that many words of scratch256; the rest is not touched.
+ *  - DASR_EINVAL, nothing launched: N, C, H or W <= 0; y, gx, slope, scratch256 or dst null. */
 int dasr_prelu_grad(dasr_tensor y, dasr_tensor gx, int32_t N, int32_t C, int32_t H, int32_t W, const float* slope, float* scratch256,
                     float* dst, float scale, void* stream);
 /* the same on f16 tensors (the DSN generator's 16-bit backward: y = f16 shadow of the layer output, gx = power-of-two pre-scaled f16 gradient;
@@ -485,7 +517,9 @@ int dasr_prelu_grad_f16(dasr_tensor y, dasr_tensor gx, int32_t N, int32_t C, int
                         float* dst, float scale, void* stream);
 /* (ABI 20) the second stage alone for `count` slopes in one launch: workgroup k sums partial[k * stride .. + nblocks) in a fixed order and writes
  * *dsts[k] = scale * sum / (*slopes[k])^2.  The partials are those the data-gradient conv epilogues leave in dasr_conv_params::prelu_part (slope * dL/dh * h per
- * workgroup): the DSN generator's residual blocks no longer read h and dL/dz a second time (dasr_prelu_grad_f16 did). slopes / dsts: DEVICE arrays of device pointers. */
+ * workgroup): the DSN generator's residual blocks no longer read h and dL/dz a second time (dasr_prelu_grad_f16 did). slopes / dsts: DEVICE arrays of device pointers.
+ * Only partial[k * stride + i], i < nblocks, is read: the gaps of a stride > nblocks layout are not.  DASR_EINVAL, nothing launched: nblocks <= 0, stride < nblocks,
+ * count <= 0, partial, slopes or dsts null. */
 int dasr_prelu_final(const float* partial, int32_t nblocks, int64_t stride, int32_t count, const float* const* slopes, float* const* dsts, float scale, void* stream);
 /* un-padded low-pass of the colour loss (FilterLow(padding=False), loss.py:52-56) on C (<= 4) channels of plane 0, w = [k][k] fp32 on the device
  * (any w: nothing relies on symmetry here).  H, W are the size of the IMAGE in both modes.  mode 0 forward: out[y][x] = sum w[ky][kx] * x[y+ky][x+kx],
@@ -499,7 +533,14 @@ int dasr_lowpass_valid(dasr_tensor x, const float* w, int32_t k, int32_t N, int3
  * Batch assembly of codes/SRN/data/LRHR_wavelet_unpairEq_fake_w_dataset.py:50-166 + data/util.py:116-128 on resident images:
  * sample k of the batch = size x size crop at (y0, x0) of image `src` (CHW fp32, RGB) -- first resized bilinearly to vH x vW when
  * that differs from H x W (cv2.resize(..., INTER_LINEAR) of the domain-distance map to the LR size) -- then horizontal flip,
- * vertical flip, transpose, in that order (util.augment).  dst is [n][C][size][size] fp32. */
+ * vertical flip, transpose, in that order (util.augment).  dst is [n][C][size][size] fp32.
+ * Contracts (tests/test_gpu_lpips_prelu.py):
+ *  - every element of dst is written.  A sample without a resize is a copy, bit for bit.  Channels c >= desc.C are zero (descriptors of different channel counts may
+ *    share a launch).  Where the window leaves the (resized) view -- y0 + i or x0 + j outside [0, vH) x [0, vW) -- dst is zero and nothing is read.
+ *  - the resize follows cv2.INTER_LINEAR: source coordinate (v + 0.5) * H / vH - 0.5 (half-pixel centres), both neighbours clamped to the image (edge clamp); it is
+ *    taken whenever vH != H or vW != W (an axis of equal size then has integer coordinates and weight 0).
+ *  - descriptors are device memory and are NOT validated: src must hold C * H * W floats.
+ *  - DASR_EINVAL, nothing launched: n, C or size <= 0; descs_dev or dst null. */
 typedef struct {
     const float* src;
     int32_t C, H, W;      /* source image */

@@ -1,7 +1,8 @@
-"""Plain torch-CPU references of the small kernels of csrc/misc.hip / csrc/gan.hip (elementwise, pooling, pixel losses, Adam; the frequency-split,
-domain-distance-map and DSN loss kernels; the normalisation, gradient-penalty and GAN-loss kernels), and the NC16HW16 layout plumbing the GPU tests
-need.  No device code: tests/test_blocked_ref.py holds every function here to stock torch on a machine without a GPU; tests/test_gpu_elementwise.py,
-tests/test_gpu_filters.py and tests/test_gpu_norm_gan.py then hold the kernels to these.
+"""Plain torch-CPU references of the small kernels of csrc/misc.hip / csrc/gan.hip / csrc/lpips.hip (elementwise, pooling, pixel losses, Adam; the
+frequency-split, domain-distance-map and DSN loss kernels; the normalisation, gradient-penalty and GAN-loss kernels; the LPIPS layers, the PReLU
+slope gradient and the fp32 crop gather), and the NC16HW16 layout plumbing the GPU tests need.  No device code: tests/test_blocked_ref.py holds every
+function here to stock torch on a machine without a GPU; tests/test_gpu_elementwise.py, tests/test_gpu_filters.py, tests/test_gpu_norm_gan.py and
+tests/test_gpu_lpips_prelu.py then hold the kernels to these.
 
 Every reference computes in fp64 on NCHW tensors and returns (value, magnitude): `magnitude` is the per-element sum of the absolute values of the
 terms the kernel adds up, the quantity a rounding-error bound k * u * magnitude is relative to.  Scalars (a, b, slope, coef, ...) are taken as given:
@@ -119,25 +120,30 @@ def pixel_unshuffle(g, mask=None, slope=0.0):
     return v, v.abs()
 
 
-def _first_max(x):
-    """x: NCHW fp64 (H, W may be odd: the last row / column takes no part).  (max, d) per 2x2 window, d = 2 dy + dx of the FIRST maximum in scan
-    order (a later candidate replaces the current one only if it is strictly greater)"""
-    Ho, Wo = x.shape[2] // 2, x.shape[3] // 2
-    xc = x[:, :, :2 * Ho, :2 * Wo]
-    cand = [xc[:, :, dy::2, dx::2] for dy in (0, 1) for dx in (0, 1)]
+def _windows(t, Ho, Wo, k, s):
+    """the k * k candidates of every window in scan order: element (dy, dx) of window (oy, ox) is t[s oy + dy][s ox + dx]"""
+    def sl(d, n):
+        return slice(d, d + s * (n - 1) + 1 if n > 0 else d, s)
+    return [t[:, :, sl(dy, Ho), sl(dx, Wo)] for dy in range(k) for dx in range(k)]
+
+
+def _first_max(x, k=2, s=2, last=False):
+    """x: NCHW fp64 (rows / columns past the last window take no part).  (max, d) per k x k window of stride s (no padding), d = k dy + dx of the
+    FIRST maximum in scan order (a later candidate replaces the current one only if it is strictly greater).  last: the LAST maximum instead (a
+    deliberately wrong variant)"""
+    Ho, Wo = (x.shape[2] - k) // s + 1, (x.shape[3] - k) // s + 1
+    cand = _windows(x, Ho, Wo, k, s)
     m, am = cand[0].clone(), torch.zeros(cand[0].shape, dtype=torch.long)
-    for d in (1, 2, 3):
-        up = cand[d] > m
+    for d in range(1, k * k):
+        up = cand[d] >= m if last else cand[d] > m
         m = torch.where(up, cand[d], m)
         am = torch.where(up, torch.full_like(am, d), am)
     return m, am
 
 
-def _take(t, am):
-    """element of the first maximum out of every 2x2 window of t (any dtype: moved, not computed)"""
-    Ho, Wo = am.shape[2], am.shape[3]
-    tc = t[:, :, :2 * Ho, :2 * Wo]
-    cand = torch.stack([tc[:, :, dy::2, dx::2] for dy in (0, 1) for dx in (0, 1)], dim=-1)
+def _take(t, am, k=2, s=2):
+    """element of the first maximum out of every window of t (any dtype: moved, not computed)"""
+    cand = torch.stack(_windows(t, am.shape[2], am.shape[3], k, s), dim=-1)
     return torch.gather(cand, -1, am.unsqueeze(-1)).squeeze(-1)
 
 
@@ -875,3 +881,229 @@ def acc_sum(terms, coef, acc0, per_thread, nblocks):
     L = per_thread + grid_chain(nblocks)
     want = acc0 + coef * float(terms.v.sum())
     return want, U32 * abs(coef) * float(terms.e.sum()) + L * U32 * (abs(coef) * float(terms.v.abs().sum()) + abs(acc0)) + TINY32
+
+
+# ---- LPIPS layers (csrc/lpips.hip), PReLU slope gradient (second half of csrc/gan.hip), fp32 crop gather (csrc/misc.hip) ----------------------
+# tests/test_gpu_lpips_prelu.py holds the kernels to these on the inputs of oracle/lpips_prelu_cases.py.
+def _ev_map(x, fn):
+    """a data movement applied to value and bound alike"""
+    return Ev(fn(x.v), fn(x.e))
+
+
+def dihedral_map(H, W, xf):
+    """index maps (U, V) [H][W] of dasr_lpips_s2d's symmetry code: T(x)[i][j] = x[U[i][j]][V[i][j]], (u, v) = (i, j), swapped if bit 0, then
+    u -> H-1-u if bit 1, v -> W-1-v if bit 2 (transposing codes need H == W)"""
+    assert not (xf & 1) or H == W
+    i, j = torch.meshgrid(torch.arange(H), torch.arange(W), indexing='ij')
+    u, v = (j, i) if xf & 1 else (i, j)
+    return (H - 1 - u if xf & 2 else u), (W - 1 - v if xf & 4 else v)
+
+
+def _chan3(p):
+    return torch.tensor([f32(s) for s in p[:3]], dtype=torch.float64).view(1, 3, 1, 1)
+
+
+def lpips_s2d(x, scale, shift, xf=0, wrong=None):
+    """mode 0: the symmetry T, then scale[c] * T(x) + shift[c] (2 roundings), zero padding by 2 applied to the SCALED image, 4x4 space-to-depth:
+    x [N][3][H][W] -> [N][48][(H+4)/4][(W+4)/4], channel 16 c + 4 by + bx = pixel (4Y + by - 2, 4X + bx - 2) of colour c; exact +0 in the padding"""
+    N, _, H, W = x.shape
+    U, V = dihedral_map(H, W, xf)
+    tx = x.double()[:, :, U, V]
+    pad = lambda t: torch.nn.functional.pad(t, (2, 2, 2, 2))
+    if wrong == 'border_shift':           # zero padding in front of the affine map: a border pixel holds shift[c]
+        s = Ev(pad(tx)) * _chan3(scale) + _chan3(shift)
+    else:
+        s = _ev_map(Ev(tx) * _chan3(scale) + _chan3(shift), pad)
+    Hs, Ws = (H + 4) // 4, (W + 4) // 4
+    order = (0, 1, 5, 3, 2, 4) if wrong == 'block_xy' else (0, 1, 3, 5, 2, 4)
+    return _ev_map(s, lambda t: t.reshape(N, 3, Hs, 4, Ws, 4).permute(*order).reshape(N, 48, Hs, Ws))
+
+
+def lpips_s2d_adj(gy, x0, scale, xf=0, wrong=None):
+    """mode 1: x0[c][u][v] + scale[c] * gy[the slot pixel (u, v) went to] (2 roundings): the gradient of T(x)[i][j] goes back to x[U[i][j]][V[i][j]]"""
+    N, _, H, W = x0.shape
+    Hs, Ws = (H + 4) // 4, (W + 4) // 4
+    g = gy.double().reshape(N, 3, 4, 4, Hs, Ws).permute(0, 1, 4, 2, 5, 3).reshape(N, 3, 4 * Hs, 4 * Ws)[:, :, 2:2 + H, 2:2 + W]
+    U, V = dihedral_map(H, W, xf)
+    if wrong == 'adj_forward_map':        # reads through the forward map where its inverse is due (the same thing unless T is a quarter turn)
+        back = g[:, :, U, V]
+    else:
+        back = torch.zeros_like(g)
+        back[:, :, U, V] = g
+    return Ev(x0) + Ev(back) * _chan3(scale)
+
+
+def maxpool3s2(x):
+    """nn.MaxPool2d(3, 2): (the maximum in x's dtype, d = 3 dy + dx of the first maximum in scan order)"""
+    _, am = _first_max(x.double(), 3, 2)
+    return _take(x, am, 3, 2), am
+
+
+def maxpool3s2_bwd(x, gy, relu_mask, gx0=None, wrong=None):
+    """gx[iy][ix] = sum of gy over the (at most 2 x 2) windows whose FIRST maximum the pixel is, added in the kernel's order (window rows, then
+    columns, ascending: the first add is to zero and exact, three more, one for `accumulate`); relu_mask: zero where x <= 0; gx0: what accumulate
+    adds to.  A row / column no window covers gets zero."""
+    N, C, H, W = x.shape
+    _, am = _first_max(x.double(), 3, 2, last=wrong == 'last_max')
+    Ho, Wo = am.shape[2], am.shape[3]
+    g = gy.double()
+    # slot (a, b): a = 0 the upper of the two window rows a pixel can belong to (dy = 2), a = 1 the lower (dy = 0 or 1); b likewise for columns
+    slots = [[torch.zeros(N, C, H, W, dtype=torch.float64) for _ in range(2)] for _ in range(2)]
+    for d in range(9):
+        dy, dx = d // 3, d % 3
+        slots[int(dy < 2)][int(dx < 2)][:, :, dy:dy + 2 * (Ho - 1) + 1:2, dx:dx + 2 * (Wo - 1) + 1:2] += torch.where(am == d, g, torch.zeros_like(g))
+    acc = ((Ev(slots[0][0]) + Ev(slots[0][1])) + Ev(slots[1][0])) + Ev(slots[1][1])
+    if relu_mask:
+        keep = x.double() >= 0 if wrong == 'relu_ge' else x.double() > 0
+        acc = acc.where(keep, 0.0)
+    return acc if gx0 is None else acc + Ev(gx0)
+
+
+def _sqrt0(q):
+    """sqrt of a sum of squares that may be EXACTLY zero (every term zero, bound zero): 0 with bound 0"""
+    r = q.sqrt()
+    zero = q.v == 0
+    assert bool((q.e[zero] == 0).all())
+    return Ev(torch.where(zero, torch.zeros_like(r.v), r.v), torch.where(zero, torch.zeros_like(r.e), r.e))
+
+
+def lpips_head(f0, f1, lin, eps, gcoef, relu_mask, wrong=None):
+    """one LPIPS layer per pixel, as the kernel evaluates it (sums over the C channels: chains of C adds):
+        q_k = sum f_k^2; r0 = sqrt(q0); s_k = sqrt(q_k) + eps; i_k = 1 / s_k; d = f0 i0 - f1 i1; val = sum (w d) d; dot = sum ((2 w) d) f0
+        k2 = dot / ((r0 s0) s0), 0 where r0 == 0 (the derivative of the norm taken as 0 at the origin); g0 = gcoef (((2 w) d) i0 - f0 k2),
+        zero where f0 <= 0 when relu_mask.
+    Returns (val [N][1][H][W], g0 [N][C][H][W]) as Ev."""
+    C = f0.shape[1]
+    X0, X1, Wt = Ev(f0), Ev(f1), lin.double().view(1, C, 1, 1)
+    q0, q1 = (X0 * X0).sum((1,), C), (X1 * X1).sum((1,), C)
+    r0 = _sqrt0(q0)
+    if wrong == 'eps_in_sqrt':
+        s0, s1 = (q0 + eps).sqrt(), (q1 + eps).sqrt()
+    else:
+        s0, s1 = r0 + eps, _sqrt0(q1) + eps
+    i0, i1 = 1.0 / s0, 1.0 / s1
+    d = X0 * i0 - X1 * i1
+    val = ((d * Wt) * d).sum((1,), C)
+    dot = ((d * (2.0 * Wt)) * X0).sum((1,), C)
+    den = (s0 * s0) * s0 if wrong == 'k2_s0cubed' else (r0 * s0) * s0
+    k2 = (dot / den).where(r0.v > 0, 0.0)
+    g0 = (d * (2.0 * Wt)) * i0
+    if wrong != 'no_x0k2':
+        g0 = g0 - X0 * k2
+    g0 = g0 * gcoef
+    if relu_mask:
+        g0 = g0.where((f1 if wrong == 'relu_f1' else f0).double() > 0, 0.0)
+    return val, g0
+
+
+# roundings behind a workgroup's total once its 256 threads hold their sums in double (whose own error, a few 2^-53, rounds into the first): the
+# cast to fp32 (1), the wave butterfly (6), the four waves (3)
+BLOCK_CHAIN = 1 + 6 + 3
+
+
+def prelu_grad(y, gx, a, scale, wrong=None):
+    """dL/da of a shared PReLU slope from the layer output y and gx = dL/dx: scale * sum_{y <= 0} gx y / a^2.  Every term is rounded to fp32 once
+    (exact for f16 inputs), both stages sum per thread in double and finish with BLOCK_CHAIN roundings, then scale * tot (1), a * a (1), the
+    division (1): all of it relative to sum |terms|.  At y == +0 and -0 the term is an exact zero: `y <= 0` and `y < 0` give the same value for
+    finite gx (wrong 'y_lt' shows it)."""
+    take = y.double() < 0 if wrong == 'y_lt' else y.double() <= 0
+    if wrong == 'skip_plane':
+        take = take.clone()
+        take[-1, -16:] = False
+    tot = (Ev(gx) * Ev(y)).where(take, 0.0).sum((0, 1, 2, 3), 2 * BLOCK_CHAIN)[0, 0, 0, 0]
+    A = Ev(a)
+    return (tot * scale) / (A if wrong == 'div_a' else A * A)
+
+
+def prelu_final(partial, slopes, scale, wrong=None):
+    """the second stage alone: partial [count][nblocks] -> scale * sum / a_k^2 per row"""
+    tot = Ev(partial).sum((1,), BLOCK_CHAIN)[:, 0]
+    A = Ev(torch.tensor([f32(s) for s in slopes], dtype=torch.float64))
+    return (tot * scale) / (A if wrong == 'div_a' else A * A)
+
+
+def _crop_axis(v, n_src, n_view, wrong=None):
+    """cv2.INTER_LINEAR source coordinate f = (v + 0.5) n_src / n_view - 0.5 of view index v, from exact integer arithmetic: (floor(f), f - floor(f),
+    delta): delta bounds |fp32 f - f| (the division, the product and the difference of the kernel's expression) plus one rounding of the weight"""
+    v = v.long()
+    num = 2 * v * n_src if wrong == 'no_half_pixel' else (2 * v + 1) * n_src - n_view
+    den = 2 * n_view
+    i0 = torch.div(num, den, rounding_mode='floor')
+    f = (_Ev64(v.double() + 0.5) * (_Ev64(float(n_src)) / _Ev64(float(n_view)))) - 0.5
+    return i0, (num - i0 * den).double() / den, U32 * f.e + U32
+
+
+def _crop_fp32(img, vy, vx, vH, vW, below):
+    """the kernel's own bilinear expression in stock fp32; below: where the exact coordinate is an integer, floorf is taken to have landed on the
+    other side of it (index one lower, weight the largest fp32 below 1)"""
+    _, H, W = img.shape
+    one = torch.tensor(1.0)
+
+    def axis(v, n_src, n_view):
+        f = (v.float() + 0.5) * (torch.tensor(float(n_src)) / torch.tensor(float(n_view))) - 0.5
+        i0 = torch.floor(f)
+        w = f - i0
+        if below:
+            hit = ((2 * v.long() + 1) * n_src - n_view) % (2 * n_view) == 0
+            i0, w = torch.where(hit, i0 - 1.0, i0), torch.where(hit, torch.tensor(1.0 - 2.0 ** -24), w)
+        i0 = i0.long()
+        return i0.clamp(0, n_src - 1), (i0 + 1).clamp(0, n_src - 1), w
+    ya, yb, wy = axis(vy, H, vH)
+    xa, xb, wx = axis(vx, W, vW)
+    s = img.float()
+    return (one - wy) * ((one - wx) * s[:, ya, xa] + wx * s[:, ya, xb]) + wy * ((one - wx) * s[:, yb, xa] + wx * s[:, yb, xb])
+
+
+def gather_crops(descs, C, size, wrong=None):
+    """dasr_gather_crops: sample k = the size x size window at (y0, x0) of image `img` [c][H][W] -- resized bilinearly to vH x vW first when that
+    differs from H x W (cv2.INTER_LINEAR: half-pixel centres, edge clamp) -- then hflip (flags bit 0), vflip (bit 1), transpose (bit 2), in that
+    order; zero for channels >= c and wherever the window leaves the view.  descs: dicts(img, vH, vW, y0, x0, flags).
+    Returns (dst [n][C][size][size] as Ev, exact [n][C][size][size] bool: pure data movement or zero fill).  The bound of a resized sample: the six
+    roundings of the blend, relative to the sum of weight * |corner|, plus the fp32 error of each source coordinate times the steepest slope of the
+    (continuous, piecewise linear) interpolant over the cells on both sides of the coordinate -- which also covers a floorf that lands across an integer.
+    wrong 'floor_below' (fp32 arithmetic only) plays exactly that."""
+    fp32 = Ev is F32
+    n = len(descs)
+    val, err = torch.zeros(n, C, size, size, dtype=torch.float64), torch.zeros(n, C, size, size, dtype=torch.float64)
+    exact = torch.ones(n, C, size, size, dtype=torch.bool)
+    ys, xs = torch.meshgrid(torch.arange(size), torch.arange(size), indexing='ij')
+    for k, D in enumerate(descs):
+        img, fl = D['img'], D['flags']
+        c, H, W = img.shape
+        ci, cj = ys, xs
+        if wrong == 'flip_order':         # flips undone in front of the transpose
+            ci, cj = (size - 1 - ci if fl & 2 else ci), (size - 1 - cj if fl & 1 else cj)
+            ci, cj = (cj, ci) if fl & 4 else (ci, cj)
+        else:
+            ci, cj = (cj, ci) if fl & 4 else (ci, cj)
+            ci, cj = (size - 1 - ci if fl & 2 else ci), (size - 1 - cj if fl & 1 else cj)
+        vy, vx = D['y0'] + ci, D['x0'] + cj
+        inside = (vy >= 0) & (vy < D['vH']) & (vx >= 0) & (vx < D['vW'])
+        vy, vx = vy.clamp(0, D['vH'] - 1), vx.clamp(0, D['vW'] - 1)
+        s = img.double()
+        cc = min(c, C)
+        if (D['vH'], D['vW']) == (H, W):
+            val[k, :cc] = torch.where(inside, s[:cc, vy, vx], torch.zeros(()).double())
+            continue
+        exact[k, :cc] = ~inside
+        if fp32:
+            val[k, :cc] = torch.where(inside, _crop_fp32(img, vy, vx, D['vH'], D['vW'], wrong == 'floor_below')[:cc].double(), torch.zeros(()).double())
+            continue
+        ya, wy, dy = _crop_axis(vy, H, D['vH'], wrong)
+        xa, wx, dx = _crop_axis(vx, W, D['vW'], wrong)
+
+        def px(yi, xi):
+            ok = ((yi >= 0) & (yi < H) & (xi >= 0) & (xi < W)) if wrong == 'no_clamp' else torch.ones_like(inside)
+            return torch.where(ok, s[:, yi.clamp(0, H - 1), xi.clamp(0, W - 1)], torch.zeros(()).double())
+        v, mag = 0.0, 0.0
+        for yi, a in ((ya, 1.0 - wy), (ya + 1, wy)):
+            for xi, b in ((xa, 1.0 - wx), (xa + 1, wx)):
+                t = (a * b) * px(yi, xi)
+                v, mag = v + t, mag + t.abs()
+        cl = lambda yi, xi: s[:, yi.clamp(0, H - 1), xi.clamp(0, W - 1)]
+        Ly = torch.stack([(cl(ya + r + 1, xa + q) - cl(ya + r, xa + q)).abs() for r in (-1, 0, 1) for q in (-1, 0, 1, 2)]).max(0).values
+        Lx = torch.stack([(cl(ya + r, xa + q + 1) - cl(ya + r, xa + q)).abs() for r in (-1, 0, 1, 2) for q in (-1, 0, 1)]).max(0).values
+        e = (6.0 * mag + (dy * Ly + dx * Lx) / U32)
+        val[k, :cc] = torch.where(inside, v[:cc], torch.zeros(()).double())
+        err[k, :cc] = torch.where(inside, e[:cc], torch.zeros(()).double())
+    return Ev(val, err), exact

@@ -1,6 +1,7 @@
-"""CPU checks of oracle/blocked_ref.py, the references tests/test_gpu_elementwise.py, tests/test_gpu_filters.py and tests/test_gpu_norm_gan.py trust,
-against stock torch: they run where no kernel can.  For the normalisation and GAN-loss references also: on the very inputs of the GPU tests
-(oracle/norm_gan_cases.py) stock fp32 arithmetic stays inside every bound and a list of deliberately wrong variants does not."""
+"""CPU checks of oracle/blocked_ref.py, the references tests/test_gpu_elementwise.py, tests/test_gpu_filters.py, tests/test_gpu_norm_gan.py and
+tests/test_gpu_lpips_prelu.py trust, against stock torch: they run where no kernel can.  For the normalisation and GAN-loss references and for the
+LPIPS / PReLU / crop-gather references also: on the very inputs of the GPU tests (oracle/norm_gan_cases.py, oracle/lpips_prelu_cases.py) stock fp32
+arithmetic stays inside every bound and a list of deliberately wrong variants does not."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -652,3 +653,289 @@ def test_every_accumulator_bound_is_tight():
                 # the gradients' bounds, too, stay first-order small against the largest gradient
                 for k in ('ga', 'gb'):
                     assert float(ref[k].tol().max()) <= 1e-4 * float(ref[k].v.abs().max()) + R.TINY32, (form, ta, tb, k)
+
+
+# ---- LPIPS layers, PReLU slope gradient, crop gather: the references of tests/test_gpu_lpips_prelu.py against stock torch in fp64 -------------------
+from oracle import lpips_prelu_cases as K2  # noqa: E402
+
+
+def _s2d_torch(t, scale, shift):
+    """ScalingLayer, zero padding by 2, 4x4 space-to-depth, on an NCHW fp64 image"""
+    N, _, H, W = t.shape
+    s = t * torch.tensor(scale[:3], dtype=torch.float64).view(1, 3, 1, 1) + torch.tensor(shift[:3], dtype=torch.float64).view(1, 3, 1, 1)
+    Hs, Ws = (H + 4) // 4, (W + 4) // 4
+    return F.pad(s, (2, 2, 2, 2)).view(N, 3, Hs, 4, Ws, 4).permute(0, 1, 3, 5, 2, 4).reshape(N, 48, Hs, Ws)
+
+
+DRAWS = [(k, r, c) for k in range(4) for r, c in ((0, 0), (1, 0), (0, 1))]      # the draws of PerceptualLoss.forward: a rotation, then at most one flip
+
+
+@pytest.mark.parametrize('k_rot,rows,cols', DRAWS + [(1, 1, 1), (2, 1, 1)])
+def test_lpips_s2d_symmetry_codes_are_rot90_and_flip(k_rot, rows, cols):
+    from dasr_amd.dsn_model import symmetry_code
+    code = symmetry_code(k_rot, rows, cols)
+    for H, W in ((12, 12), (8, 12)):
+        if code & 1 and H != W:
+            continue
+        i = K2.s2d_inputs(H, W)
+        x = i['x'].double().requires_grad_(True)
+        t = torch.rot90(x, k_rot, [2, 3])
+        t = torch.flip(t, (2,)) if rows else t
+        t = torch.flip(t, (3,)) if cols else t
+        y = _s2d_torch(t, K2.SCALE4, K2.SHIFT4)
+        ref = R.lpips_s2d(i['x'], K2.SCALE4, K2.SHIFT4, code)
+        assert close(ref, y, 1e-15)
+        border = torch.ones(H + 4, W + 4, dtype=torch.bool)
+        border[2:-2, 2:-2] = False
+        unblocked = ref.v.view(2, 3, 4, 4, (H + 4) // 4, (W + 4) // 4).permute(0, 1, 4, 2, 5, 3).reshape(2, 3, H + 4, W + 4)
+        ebound = ref.e.view(2, 3, 4, 4, (H + 4) // 4, (W + 4) // 4).permute(0, 1, 4, 2, 5, 3).reshape(2, 3, H + 4, W + 4)
+        # the padding: exact zero with a zero bound; inside the image the bound is the two roundings' worth, never zero (shift is not)
+        assert bool((unblocked[:, :, border] == 0).all()) and bool((ebound[:, :, border] == 0).all()) and bool((ebound[:, :, ~border] > 0).all())
+        # the adjoint is the transpose of the linear part: autograd's gradient of <y, gy>, added to what x0 holds
+        gx, = torch.autograd.grad((y * i['gy'].double()).sum(), x)
+        assert close(R.lpips_s2d_adj(i['gy'], i['x0'], K2.SCALE4, code), i['x0'].double() + gx, 1e-15)
+        # <s2d_T(x) - shift part, gy> == <x, adj_T(gy)>
+        lin = R.lpips_s2d(i['x'], K2.SCALE4, [0.0] * 4, code).v
+        adj = R.lpips_s2d_adj(i['gy'], torch.zeros_like(i['x0']), K2.SCALE4, code).v
+        lhs, rhs = float((lin * i['gy'].double()).sum()), float((i['x'].double() * adj).sum())
+        assert abs(lhs - rhs) <= 1e-12 * abs(lhs)
+
+
+def test_dihedral_codes_cover_the_square_and_only_quarter_turns_are_not_involutions():
+    x = torch.arange(144.0).view(1, 1, 12, 12)
+    seen = set()
+    for xf in range(8):
+        U, V = R.dihedral_map(12, 12, xf)
+        t = x[:, :, U, V]
+        seen.add(tuple(t.flatten().tolist()))
+        assert torch.equal(t[:, :, U, V], x) == (xf not in K2.QUARTER_TURNS)
+    assert len(seen) == 8
+
+
+@pytest.mark.parametrize('hw', K2.POOL_HW + [(15, 18)])
+def test_maxpool3s2_matches_torch(hw):
+    """F.max_pool2d(3, 2) and autograd on tied inputs (ATen, too, hands the gradient to the first maximum in scan order); relu_mask: the gradient
+    w.r.t. the pre-activation z of x = relu(z)"""
+    g = gen(60)
+    z = tied((2, 5, hw[0], hw[1]), g)
+    gy = torch.randn(2, 5, (hw[0] - 3) // 2 + 1, (hw[1] - 3) // 2 + 1, generator=g, dtype=torch.float64)
+    gx0 = torch.randn(2, 5, hw[0], hw[1], generator=g, dtype=torch.float64)
+    for relu in (0, 1):
+        zz = z.clone().requires_grad_(True)
+        x = torch.relu(zz) if relu else zz
+        y = F.max_pool2d(x, 3, 2)
+        assert torch.equal(R.maxpool3s2(x.detach())[0], y.detach())
+        want, = torch.autograd.grad((y * gy).sum(), zz)
+        assert close(R.maxpool3s2_bwd(x.detach(), gy, relu), want, 1e-15)
+        assert close(R.maxpool3s2_bwd(x.detach(), gy, relu, gx0), want + gx0, 1e-15)
+        if hw != (3, 3):
+            assert not close(R.maxpool3s2_bwd(x.detach(), gy, relu, wrong='last_max'), want, 1e-3)
+
+
+@pytest.mark.parametrize('C', K2.POOL_C)
+@pytest.mark.parametrize('hw', K2.POOL_HW)
+def test_pool_inputs_hold_the_cases_the_gpu_test_is_about(hw, C):
+    i = K2.pool_inputs(C, *hw)
+    x = i['x'].double()
+    m, am = R._first_max(x, 3, 2)
+    Ho, Wo = am.shape[2:]
+    cand = torch.stack(R._windows(x, Ho, Wo, 3, 2), -1)
+    tied_pos = ((cand == m.unsqueeze(-1)).sum(-1) > 1) & (m > 0)
+    assert bool(tied_pos[:, :C].any())                                   # tied maxima at non-zero values
+    assert bool((m[:, 0, 0, 0] == 0).all()) and bool((m[:, 1, 0, 0] < 0).all())      # a window all zero, a window all negative
+    assert float(x.min()) > -3.4e38 and bool(torch.isfinite(x).all())
+    if Ho * Wo > 1:
+        # a pixel that is the first maximum of one of its windows and not of another: its gradient is ONE of the window gradients, not their sum
+        first = torch.zeros(x.shape, dtype=torch.long)
+        member = torch.zeros(x.shape, dtype=torch.long)
+        for d in range(9):
+            dy, dx = d // 3, d % 3
+            first[:, :, dy:dy + 2 * (Ho - 1) + 1:2, dx:dx + 2 * (Wo - 1) + 1:2] += (am == d).long()
+            member[:, :, dy:dy + 2 * (Ho - 1) + 1:2, dx:dx + 2 * (Wo - 1) + 1:2] += 1
+        assert bool(((first >= 1) & (first < member))[:, :C].any()) and bool((first >= 2)[:, :C].any())
+    if hw in ((4, 4), (8, 6)):                                           # the last row and column lie in no window: exact zero, zero bound
+        gx = R.maxpool3s2_bwd(i['x'], i['gy'], 0)
+        assert bool((gx.v[:, :, -1] == 0).all()) and bool((gx.v[:, :, :, -1] == 0).all()) and bool((gx.e[:, :, -1] == 0).all())
+
+
+def _normalize(t, eps):
+    return t / (torch.sqrt((t ** 2).sum(1, keepdim=True)) + eps)
+
+
+@pytest.mark.parametrize('relu', [0, 1])
+@pytest.mark.parametrize('C', [16, 48])
+def test_lpips_head_matches_autograd_through_normalize_tensor(C, relu):
+    g = gen(61)
+    z = torch.randn(4, C, 5, 7, generator=g, dtype=torch.float64)
+    lin = torch.rand(C, generator=g, dtype=torch.float64)
+    zz = z.clone().requires_grad_(True)
+    f = torch.relu(zz) if relu else zz
+    d = _normalize(f[:2], 1e-10) - _normalize(f[2:], 1e-10)
+    val = ((d ** 2) * lin.view(1, C, 1, 1)).sum(1, keepdim=True)
+    want, = torch.autograd.grad(0.3 * val.sum(), zz)
+    rv, rg = R.lpips_head(f[:2].detach(), f[2:].detach(), lin, 1e-10, 0.3, relu)
+    assert close(rv, val, 1e-12) and close(rg, want[:2], 1e-9)
+    for w in ('no_x0k2', 'eps_in_sqrt'):
+        assert not close(R.lpips_head(f[:2].detach(), f[2:].detach(), lin, 1e-2, 0.3, relu, w)[1],
+                         R.lpips_head(f[:2].detach(), f[2:].detach(), lin, 1e-2, 0.3, relu)[1].v, 1e-3)
+
+
+@pytest.mark.parametrize('C', K2.HEAD_C)
+def test_lpips_head_contract_at_all_zero_pixels(C):
+    """f0 all zero: u = 0, the derivative of the norm is taken as 0 (k2 = 0), so g0 = gcoef 2 w (0 - v) / eps: large, finite, zero bound only where v
+    is zero too"""
+    i, ref = K2.ref_head(C, 0)
+    gc = K2.head_coefs()[1]
+    n, y, x = K2.PIX_F0_ZERO
+    v = _normalize(i['f'][K2.PAIR_OFF:K2.PAIR_OFF + 2].double(), K2.HEAD_EPS)[n, :, y, x]
+    want = gc * 2.0 * i['lin'].double() * (0.0 - v) / K2.HEAD_EPS
+    assert bool(torch.isfinite(ref['g0'].v).all()) and close(ref['g0'].v[n, :, y, x], want, 1e-12)
+    assert abs(float(ref['val'].v[n, 0, y, x]) - float((i['lin'].double() * v * v).sum())) <= 1e-12
+    n, y, x = K2.PIX_BOTH_ZERO
+    assert bool((ref['g0'].v[n, :, y, x] == 0).all()) and float(ref['val'].v[n, 0, y, x]) == 0.0 and float(ref['val'].e[n, 0, y, x]) == 0.0
+    n, y, x = K2.PIX_TINY            # eps is visible here and nowhere else: r0 is a few 1e-9
+    r0 = float(i['f'][n, :, y, x].double().norm())
+    assert K2.HEAD_EPS / r0 > 1e-3
+
+
+def test_lpips_head_accumulator_bound_is_sound_and_tight():
+    for C in K2.HEAD_C:
+        _, ref = K2.ref_head(C, 0)
+        with R.fp32_arithmetic():
+            v32 = K2.ref_head(C, 0)[1]['val'].v
+        coef = K2.head_coefs()[0]
+        got = torch.tensor(K2.HEAD_ACC0) + torch.tensor(coef) * v32.sum()
+        want, bound = K2.head_acc(C)
+        assert abs(float(got) - want) <= bound and bound <= 2e-5 * (coef * float(ref['val'].v.abs().sum()) + K2.HEAD_ACC0)
+
+
+def test_prelu_slope_gradient_matches_autograd():
+    g = gen(62)
+    x = torch.randn(2, 20, 5, 7, generator=g, dtype=torch.float64)
+    x[0, 0, 0, 0], x[1, 3, 2, 2] = 0.0, -0.0
+    w = torch.randn(2, 20, 5, 7, generator=g, dtype=torch.float64)
+    a = torch.tensor([0.2], dtype=torch.float64, requires_grad=True)
+    xx = x.clone().requires_grad_(True)
+    y = F.prelu(xx, a)
+    da, gx = torch.autograd.grad((y * w).sum(), (a, xx))
+    ref = R.prelu_grad(y.detach(), gx, 0.2, 0.5)
+    assert abs(float(ref.v) - 0.5 * float(da)) <= 1e-12 * float((w * x).abs().sum())
+    assert abs(float(ref.v) - 0.5 * float((gx * y.detach())[y.detach() <= 0].sum()) / 0.04) <= 1e-12 * float((w * x).abs().sum())
+    part = torch.randn(3, 300, generator=g)
+    fin = R.prelu_final(part, K2.FINAL_SLOPES, 0.5)
+    for k, s in enumerate(K2.FINAL_SLOPES):
+        assert abs(float(fin.v[k]) - 0.5 * float(part[k].double().sum()) / R.f32(s) ** 2) <= 1e-12 * float(part[k].abs().sum()) / s ** 2
+
+
+@pytest.mark.parametrize('case', K2.PRELU)
+@pytest.mark.parametrize('kind', ['f32', 'f16'])
+def test_prelu_slope_gradient_is_indifferent_to_the_branch_at_zero(kind, case):
+    """at y == +0 and -0 the term gx * y is an exact zero: `y < 0` in place of `y <= 0` is the same function of finite inputs, value and bound alike.
+    include/dasr_hip.h documents the entry points as indifferent to it; no test can tell the two apart."""
+    i, ref = K2.ref_prelu(*case, kind)
+    assert bool((i['y'].double() == 0).any()) and bool((i['gx'].double()[i['y'].double() == 0] != 0).any())
+    other = K2.ref_prelu(*case, kind, wrong='y_lt')[1]['d']
+    assert torch.equal(other.v, ref['d'].v) and torch.equal(other.e, ref['d'].e)
+    # the bound is relative to sum |terms|, and stays small against it
+    terms = (i['gx'].double() * i['y'].double())[i['y'].double() <= 0]
+    scale = K2.PRELU_SCALE / (K2.PRESCALE if kind == 'f16' else 1.0)
+    assert float(ref['d'].tol()) <= 30 * R.U32 * scale * float(terms.abs().sum()) / K2.PRELU_A ** 2
+
+
+def _crop_cv2(D, C, size):
+    """the forward statement: cv2.resize(INTER_LINEAR) of the whole image to vH x vW (half-pixel centres, edge clamp), the window (zero outside the
+    view), then hflip, vflip, transpose in that order, zero channels up to C"""
+    img = D['img'].double()
+    c, H, W = img.shape
+    vH, vW = D['vH'], D['vW']
+    if (vH, vW) == (H, W):
+        view = img
+    else:
+        view = torch.zeros(c, vH, vW, dtype=torch.float64)
+        for vy in range(vH):
+            fy = (vy + 0.5) * H / vH - 0.5
+            ya = int(torch.floor(torch.tensor(fy)))
+            wy = fy - ya
+            ya, yb = min(max(ya, 0), H - 1), min(max(ya + 1, 0), H - 1)
+            for vx in range(vW):
+                fx = (vx + 0.5) * W / vW - 0.5
+                xa = int(torch.floor(torch.tensor(fx)))
+                wx = fx - xa
+                xa, xb = min(max(xa, 0), W - 1), min(max(xa + 1, 0), W - 1)
+                view[:, vy, vx] = (1 - wy) * ((1 - wx) * img[:, ya, xa] + wx * img[:, ya, xb]) + wy * ((1 - wx) * img[:, yb, xa] + wx * img[:, yb, xb])
+    win = torch.zeros(C, size, size, dtype=torch.float64)
+    for y in range(size):
+        for x in range(size):
+            vy, vx = D['y0'] + y, D['x0'] + x
+            if 0 <= vy < vH and 0 <= vx < vW:
+                win[:min(c, C), y, x] = view[:min(c, C), vy, vx]
+    if D['flags'] & 1:
+        win = torch.flip(win, (2,))
+    if D['flags'] & 2:
+        win = torch.flip(win, (1,))
+    if D['flags'] & 4:
+        win = win.transpose(1, 2)
+    return win
+
+
+@pytest.mark.parametrize('launch', ['all', 'edge'])
+def test_gather_crops_matches_the_cv2_convention(launch):
+    i, ref = K2.ref_gather(launch)
+    want = torch.stack([_crop_cv2(D, K2.CROP_C, K2.CROP_SIZE) for D in i['descs']])
+    assert close(ref['dst'], want, 1e-14)
+    assert sorted(D['flags'] for D in K2.crop_descs('all')) == list(range(8))
+    # pure crops and the zero fill: exact, zero bound; the resized samples: six roundings of a blend of values in [0, 1] and, per axis, a coordinate
+    # below 33 known to three roundings and one of the weight, times a slope of at most 1
+    assert bool((ref['dst'].e[i['exact']] == 0).all()) and bool((ref['dst'].e[~i['exact']] > 0).all())
+    assert float(ref['dst'].tol().max()) <= (6 + 2 * (3 * 33 + 1)) * R.U32
+    if launch == 'all':
+        assert bool((ref['dst'].v[1, 1:] == 0).all()) and bool((ref['dst'].v[1, 0] != 0).all())       # channels >= D.C: zero
+    else:                                 # part of each window lies outside the view: zero there, the image elsewhere
+        for k, D in enumerate(i['descs']):
+            out = torch.zeros(K2.CROP_SIZE, K2.CROP_SIZE, dtype=torch.bool)      # the out-of-view mask, from the forward statement: window, flips, transpose
+            for y in range(K2.CROP_SIZE):
+                for x in range(K2.CROP_SIZE):
+                    out[y, x] = not (0 <= D['y0'] + y < D['vH'] and 0 <= D['x0'] + x < D['vW'])
+            out = torch.flip(out, (1,)) if D['flags'] & 1 else out
+            out = torch.flip(out, (0,)) if D['flags'] & 2 else out
+            out = out.t() if D['flags'] & 4 else out
+            assert 12 <= int(out.sum()) <= 40 and torch.equal(ref['dst'].v[k, 0] == 0, out)
+
+
+def test_gather_crops_floorf_across_an_integer_stays_inside_the_bound():
+    """22 -> 10 puts the source coordinate of every fifth row ON an integer: the case where fp32 may floor to either side.  Taking the lower cell with a
+    weight just below 1 there (what a coordinate rounded downwards gives) moves the fp32 result by less than the bound allows: the interpolant is
+    continuous across the cell boundary"""
+    hits = [vy for vy in range(10) if ((2 * vy + 1) * 22 - 10) % 20 == 0]
+    assert hits == [2, 7]
+    _, ref = K2.ref_gather('all')
+    with R.fp32_arithmetic():
+        plain = K2.ref_gather('all')[1]['dst'].v.double()
+        below = K2.ref_gather('all', wrong='floor_below')[1]['dst'].v.double()
+    assert not torch.equal(plain, below)
+    assert bool(((plain - ref['dst'].v).abs() <= ref['dst'].tol()).all()) and bool(((below - ref['dst'].v).abs() <= ref['dst'].tol()).all())
+
+
+EVALS2 = list(K2.evals())
+
+
+@pytest.mark.parametrize('case', EVALS2, ids=[e[0] for e in EVALS2])
+def test_lpips_prelu_gather_bounds_are_sound_and_have_teeth(case):
+    """on the inputs of tests/test_gpu_lpips_prelu.py: the kernel's expression in stock fp32 meets every bound the GPU file applies, every listed wrong
+    variant misses at least one"""
+    _, fn, args, wrong = case
+    inputs, ref = fn(*args)
+    for r in ref.values():
+        assert bool(torch.isfinite(r.v).all()) and bool(torch.isfinite(r.e).all()) and bool((r.e >= 0).all())
+    with R.fp32_arithmetic():
+        inputs32, got = fn(*args)
+    assert all(torch.equal(inputs[k], inputs32[k]) for k in inputs if torch.is_tensor(inputs[k]))
+    assert all(g.v.dtype == torch.float32 for g in got.values())
+    assert _worst(got, ref) <= 1.0, _worst(got, ref)
+    for w in wrong:
+        assert w in K2.WRONG
+        assert _worst(fn(*args, wrong=w)[1], ref) > 1.0, w
+
+
+def test_every_wrong_variant_of_the_lpips_prelu_gather_cases_is_exercised():
+    assert {w for e in EVALS2 for w in e[3]} == set(K2.WRONG)

@@ -83,6 +83,15 @@ def _entries():
         'gan_loss': (L.OP_BCE, ['x', 'N', 'C', 'H', 'W', 'gan_type', 'target', 'coef', 'gcoef', 'loss_acc', 'score_acc', 'score_coef', 'grad']),
         'ragan': (L.OP_RAGAN, ['a', 'b', 'N', 'H', 'W', 'stage', 'n_glob', 'form', 'ta', 'tb', 'coef', 'gcoef', 'eps', 'sums', 'part', 'loss_acc', 'score_a',
                                'score_b', 'score_coef', 'ga', 'gb']),
+        # tests/test_gpu_lpips_prelu.py
+        'lpips_s2d': (L.OP_LPIPS_S2D, ['x', 'N', 'H', 'W', 'scale4', 'shift4', 'y', 'mode']),
+        'maxpool3s2': (L.OP_MAXPOOL3, ['x', 'N', 'C', 'H', 'W', 'y']),
+        'maxpool3s2_bwd': (L.OP_MAXPOOL3_BWD, ['x', 'gy', 'N', 'C', 'H', 'W', 'gx', 'relu_mask', 'accumulate']),
+        'lpips_head': (L.OP_LPIPS_HEAD, ['f', 'pair_off', 'N', 'C', 'H', 'W', 'lin', 'eps', 'coef', 'gcoef', 'loss_acc', 'g0', 'relu_mask']),
+        'prelu_grad': (L.OP_PRELU_GRAD, ['y', 'gx', 'N', 'C', 'H', 'W', 'slope', 'scratch256', 'dst', 'scale']),
+        # the same op kind with f16 = 1; as an op it also takes inv_prescale (the executor multiplies it into scale)
+        'prelu_grad_f16': (L.OP_PRELU_GRAD, ['y', 'gx', 'N', 'C', 'H', 'W', 'slope', 'scratch256', 'dst', 'scale'], dict(f16=1)),
+        'prelu_final': (L.OP_PRELU_FINAL, ['partial', 'nblocks', 'stride', 'count', 'slopes', 'dsts', 'scale']),
     }
 
 
@@ -90,11 +99,11 @@ def call(via, name, **kw):
     """dasr_<name>(**kw) by argument name, through the ctypes entry point or as a recorded op; arguments left out are NULL / 0.  Returns the code."""
     from dasr_amd import _lib
     from dasr_amd.engine import NULL_T, OpList, _stream
-    kind, names = _entries()[name]
-    assert set(kw) <= set(names), set(kw) - set(names)
+    kind, names, fixed = (_entries()[name] + ({},))[:3]     # fixed: op slots that select this entry point behind a shared op kind
+    assert set(kw) <= set(names) | (set(_lib.OP_ARGS[kind]) - set(fixed) if via == 'op' else set()), set(kw) - set(names)
     if via == 'op':
         ol = OpList()
-        ol.add(_lib.make_op(kind, **kw))
+        ol.add(_lib.make_op(kind, **fixed, **kw))
         try:
             ol.run()
             rc = 0
@@ -157,6 +166,37 @@ def bounded(name, got, ref, bound, margins):
     worst = float((err / bound.clamp_min(1e-300)).max())
     margins('elementwise %s: worst |err| / bound %.3f' % (name, worst))
     assert bool((err <= bound).all()), '%s: %d elements beyond the bound, worst %.3f of it' % (name, int((err > bound).sum()), worst)
+
+
+G = 16                                    # guard words around every flat buffer
+
+
+class Buf:
+    """a flat fp32 device buffer between two runs of G sentinel words"""
+
+    def __init__(self, dev, data=None, n=None):
+        body = torch.full((n,), SENT) if data is None else data.detach().float().reshape(-1).clone()
+        self.n = body.numel()
+        self.t = torch.cat([torch.full((G,), SENT), body, torch.full((G,), SENT)]).to(dev)
+        self.before = self.t.cpu().clone()
+        self.ptr = self.t.data_ptr() + 4 * G
+
+    def get(self):
+        return self.t[G:G + self.n].cpu()
+
+    def put(self, data):
+        self.t[G:G + self.n] = data.detach().float().reshape(-1).to(self.t.device)
+
+    def guards_ok(self):
+        now = self.t.cpu()
+        return biteq(now[:G], self.before[:G]) and biteq(now[G + self.n:], self.before[G + self.n:])
+
+    def untouched(self):
+        return biteq(self.t.cpu(), self.before)
+
+
+def ev_ok(name, got, ref, margins):
+    bounded(name, got, ref.v, ref.tol(), margins)
 
 
 def sent_like(t):

@@ -19,34 +19,9 @@ import torch
 
 from oracle import blocked_ref as R
 from oracle import norm_gan_cases as K
-from test_gpu_elementwise import EINVAL, SENT, VIA, Slab, _gpu, _grid_chain, biteq, bounded, call, gpu
+from test_gpu_elementwise import EINVAL, G, SENT, VIA, Buf, Slab, _gpu, _grid_chain, biteq, bounded, call, ev_ok, gpu
 
-G = 16                                    # guard words around every flat buffer
 assert _grid_chain(3) == R.grid_chain(3)  # the accumulators are bounded with test_l1_diff's chain
-
-
-class Buf:
-    """a flat fp32 device buffer between two runs of G sentinel words"""
-
-    def __init__(self, dev, data=None, n=None):
-        body = torch.full((n,), SENT) if data is None else data.detach().float().reshape(-1).clone()
-        self.n = body.numel()
-        self.t = torch.cat([torch.full((G,), SENT), body, torch.full((G,), SENT)]).to(dev)
-        self.before = self.t.cpu().clone()
-        self.ptr = self.t.data_ptr() + 4 * G
-
-    def get(self):
-        return self.t[G:G + self.n].cpu()
-
-    def put(self, data):
-        self.t[G:G + self.n] = data.detach().float().reshape(-1).to(self.t.device)
-
-    def guards_ok(self):
-        now = self.t.cpu()
-        return biteq(now[:G], self.before[:G]) and biteq(now[G + self.n:], self.before[G + self.n:])
-
-    def untouched(self):
-        return biteq(self.t.cpu(), self.before)
 
 
 def slab(dev, x, pad=0.0, lead=1):
@@ -57,10 +32,6 @@ def slab(dev, x, pad=0.0, lead=1):
 
 def out_slab(dev, N, C, H, W, lead=2):
     return Slab(dev, 'f32', N, R.planes(C), H, W, None, lead=lead)
-
-
-def ev_ok(name, got, ref, margins):
-    bounded(name, got, ref.v, ref.tol(), margins)
 
 
 def zeros_from(t, C):
