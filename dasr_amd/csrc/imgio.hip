@@ -10,6 +10,8 @@
 //  * gather_srn_u8 / crops_down4_u8: batch assembly of the SRN trainers on resident 8-bit images (`"resident_u8": true`; reference: codes/SRN/data/LRHR_dataset.py:44-126,
 //    LRHR_wavelet_unpairEq_fake_w_dataset.py:50-166, data/util.py:116-128 augment; host side: dasr_amd/data.py).  The first writes every 3-channel tensor of a batch in one launch
 //    (per-descriptor window size and destination), the second the augmented LR crops of an HR-only set: samples of the x1/4 image of the WHOLE image, made where a crop needs them.
+//  * dihedral8 / dihedral8_mean: the geometry of the x8 self-ensemble (`"self_ensemble": true`; reference: codes/SRN/models/SR_model.py:102-140 test_x8): the eight flips /
+//    transposes of the LR image in one launch, and the mean of the eight inverse-transformed SR images in one launch with a fixed order of the adds.
 // The first two are memory-bound (about 36 multiply-adds per output sample at s = 4 against 2 x 18 gathered reads), so the kernels are plain: one thread per output
 // sample, the x index on the lanes so that loads and stores of a wave are contiguous (pass 2 reads with a stride of s samples inside one row of the
 // intermediate, which the 18-tap overlap of neighbouring outputs keeps in cache), no LDS, no atomics.
@@ -233,6 +235,156 @@ __global__ __launch_bounds__(256) void crops_down4_u8_kernel(const dasr_srn_u8_d
     }
 }
 
+// ---- x8 geometric self-ensemble (reference: codes/SRN/models/SR_model.py:102-140 test_x8; host restatement: dasr_amd/util.py dihedral8_reference) ----------------------
+// Member i of the ensemble: b0 = i & 1 flips along W, b1 = (i >> 1) & 1 flips along H, b2 = i >> 2 transposes (applied last).  Both kernels work on D8_T x D8_T tiles of
+// the untransposed image, one workgroup per tile and channel, grid (ceil(W / D8_T), ceil(H / D8_T), C).  The four untransposed members never touch the LDS: a thread
+// moves the samples it holds (a flip along W reverses them inside the 16-byte vector and mirrors the vector's position).  The four transposed members go through an LDS
+// tile with a row stride of D8_T + 1 words, written along one axis and read along the other, so that BOTH global sides are contiguous over the lanes (256-byte runs).
+// VW / VH: 16-byte global accesses along W (x, dst_a / sr_a, dst) and along H (dst_b / sr_b): the launcher sets them when the length is a multiple of 4 and the pointers are
+// 16-byte aligned -- every row then starts aligned, a mirrored vector (W - 4 - q) is aligned too, and a vector is never cut by the image's edge.  Otherwise one sample per lane.
+// Memory-bound (1 read + 8 writes of the image / 8 reads + 1 write), no arithmetic but the seven adds and the exact scaling by 1 / 8.
+constexpr int D8_T = 64, D8_S = D8_T + 1;
+
+__device__ __forceinline__ float4 d8_rev(float4 v) { return make_float4(v.w, v.z, v.y, v.x); }
+
+template <bool VW, bool VH>
+__global__ __launch_bounds__(256) void dihedral8_kernel(const float* __restrict__ x, int H, int W, float* __restrict__ dst_a, float* __restrict__ dst_b) {
+    __shared__ float tile[D8_T * D8_S];   // tile[r][q] of the source
+    const int q0 = blockIdx.x * D8_T, r0 = blockIdx.y * D8_T;
+    const size_t HW = (size_t)H * W, CHW = HW * gridDim.z;
+    const float* xp = x + blockIdx.z * HW;
+    float* a = dst_a + blockIdx.z * HW;
+    float* b = dst_b + blockIdx.z * HW;
+    if (VW) {
+        for (int e = threadIdx.x; e < D8_T * D8_T / 4; e += 256) {
+            const int rl = e >> 4, ql = (e & 15) * 4, r = r0 + rl, q = q0 + ql;
+            if (r >= H || q >= W) continue;
+            const size_t up = (size_t)r * W, dn = (size_t)(H - 1 - r) * W;
+            const int qf = W - 4 - q;
+            const float4 v = *(const float4*)(xp + up + q);
+            float* t = tile + rl * D8_S + ql;
+            t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w;
+            *(float4*)(a + up + q) = v;
+            *(float4*)(a + CHW + up + qf) = d8_rev(v);
+            *(float4*)(a + 2 * CHW + dn + q) = v;
+            *(float4*)(a + 3 * CHW + dn + qf) = d8_rev(v);
+        }
+    } else {
+        for (int e = threadIdx.x; e < D8_T * D8_T; e += 256) {
+            const int rl = e >> 6, ql = e & 63, r = r0 + rl, q = q0 + ql;
+            if (r >= H || q >= W) continue;
+            const size_t up = (size_t)r * W, dn = (size_t)(H - 1 - r) * W;
+            const int qf = W - 1 - q;
+            const float v = xp[up + q];
+            tile[rl * D8_S + ql] = v;
+            a[up + q] = v;
+            a[CHW + up + qf] = v;
+            a[2 * CHW + dn + q] = v;
+            a[3 * CHW + dn + qf] = v;
+        }
+    }
+    __syncthreads();
+    // transposed members: planes [W][H]; source (r, q) -> row q or W - 1 - q, column r or H - 1 - r.  The lanes run along r.
+    if (VH) {
+        for (int e = threadIdx.x; e < D8_T * D8_T / 4; e += 256) {
+            const int rl = (e & 15) * 4, ql = e >> 4, r = r0 + rl, q = q0 + ql;
+            if (r >= H || q >= W) continue;
+            const size_t up = (size_t)q * H, dn = (size_t)(W - 1 - q) * H;
+            const int rf = H - 4 - r;
+            const float* t = tile + rl * D8_S + ql;
+            const float4 v = make_float4(t[0], t[D8_S], t[2 * D8_S], t[3 * D8_S]);
+            *(float4*)(b + up + r) = v;
+            *(float4*)(b + CHW + dn + r) = v;
+            *(float4*)(b + 2 * CHW + up + rf) = d8_rev(v);
+            *(float4*)(b + 3 * CHW + dn + rf) = d8_rev(v);
+        }
+    } else {
+        for (int e = threadIdx.x; e < D8_T * D8_T; e += 256) {
+            const int rl = e & 63, ql = e >> 6, r = r0 + rl, q = q0 + ql;
+            if (r >= H || q >= W) continue;
+            const size_t up = (size_t)q * H, dn = (size_t)(W - 1 - q) * H;
+            const int rf = H - 1 - r;
+            const float v = tile[rl * D8_S + ql];
+            b[up + r] = v;
+            b[CHW + dn + r] = v;
+            b[2 * CHW + up + rf] = v;
+            b[3 * CHW + dn + rf] = v;
+        }
+    }
+}
+
+// dst[c][R][Q] = 0.125f * (((((((s0 + s1) + s2) + s3) + s4) + s5) + s6) + s7), s_i the sample of member i's SR image that lands on (R, Q) once its transform is undone.
+// The transposed members (sr_b, planes [W][H]) are staged first: lds[m][Q - Q0][R - R0], read from memory with the lanes along R and from the LDS with the lanes along Q.
+// LDS: 4 x D8_T x D8_S words = 66560 bytes (dynamic: above the 64 KB of a static array), two workgroups on a CU.
+template <bool VW, bool VH>
+__global__ __launch_bounds__(256) void dihedral8_mean_kernel(const float* __restrict__ sr_a, const float* __restrict__ sr_b, int H, int W, float* __restrict__ dst) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* lds = (float*)smem;
+    constexpr int M = D8_T * D8_S;
+    const int Q0 = blockIdx.x * D8_T, R0 = blockIdx.y * D8_T;
+    const size_t HW = (size_t)H * W, CHW = HW * gridDim.z;
+    const float* ap = sr_a + blockIdx.z * HW;
+    const float* bp = sr_b + blockIdx.z * HW;
+    if (VH) {
+        for (int e = threadIdx.x; e < D8_T * D8_T / 4; e += 256) {
+            const int rl = (e & 15) * 4, ql = e >> 4, R = R0 + rl, Q = Q0 + ql;
+            if (R >= H || Q >= W) continue;
+            const size_t up = (size_t)Q * H, dn = (size_t)(W - 1 - Q) * H;
+            const int rf = H - 4 - R;
+            const float4 v4 = *(const float4*)(bp + up + R), v5 = *(const float4*)(bp + CHW + dn + R);
+            const float4 v6 = d8_rev(*(const float4*)(bp + 2 * CHW + up + rf)), v7 = d8_rev(*(const float4*)(bp + 3 * CHW + dn + rf));
+            float* t = lds + ql * D8_S + rl;
+            t[0] = v4.x; t[1] = v4.y; t[2] = v4.z; t[3] = v4.w;
+            t[M] = v5.x; t[M + 1] = v5.y; t[M + 2] = v5.z; t[M + 3] = v5.w;
+            t[2 * M] = v6.x; t[2 * M + 1] = v6.y; t[2 * M + 2] = v6.z; t[2 * M + 3] = v6.w;
+            t[3 * M] = v7.x; t[3 * M + 1] = v7.y; t[3 * M + 2] = v7.z; t[3 * M + 3] = v7.w;
+        }
+    } else {
+        for (int e = threadIdx.x; e < D8_T * D8_T; e += 256) {
+            const int rl = e & 63, ql = e >> 6, R = R0 + rl, Q = Q0 + ql;
+            if (R >= H || Q >= W) continue;
+            const size_t up = (size_t)Q * H, dn = (size_t)(W - 1 - Q) * H;
+            const int rf = H - 1 - R;
+            float* t = lds + ql * D8_S + rl;
+            t[0] = bp[up + R];
+            t[M] = bp[CHW + dn + R];
+            t[2 * M] = bp[2 * CHW + up + rf];
+            t[3 * M] = bp[3 * CHW + dn + rf];
+        }
+    }
+    __syncthreads();
+    float* o = dst + blockIdx.z * HW;
+    if (VW) {
+        for (int e = threadIdx.x; e < D8_T * D8_T / 4; e += 256) {
+            const int rl = e >> 4, ql = (e & 15) * 4, R = R0 + rl, Q = Q0 + ql;
+            if (R >= H || Q >= W) continue;
+            const size_t up = (size_t)R * W, dn = (size_t)(H - 1 - R) * W;
+            const int qf = W - 4 - Q;
+            const float4 s0 = *(const float4*)(ap + up + Q), s1 = d8_rev(*(const float4*)(ap + CHW + up + qf));
+            const float4 s2 = *(const float4*)(ap + 2 * CHW + dn + Q), s3 = d8_rev(*(const float4*)(ap + 3 * CHW + dn + qf));
+            float acc[4] = {((s0.x + s1.x) + s2.x) + s3.x, ((s0.y + s1.y) + s2.y) + s3.y, ((s0.z + s1.z) + s2.z) + s3.z, ((s0.w + s1.w) + s2.w) + s3.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float* t = lds + (ql + k) * D8_S + rl;
+                acc[k] = 0.125f * ((((acc[k] + t[0]) + t[M]) + t[2 * M]) + t[3 * M]);
+            }
+            *(float4*)(o + up + Q) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+        }
+    } else {
+        for (int e = threadIdx.x; e < D8_T * D8_T; e += 256) {
+            const int rl = e >> 6, ql = e & 63, R = R0 + rl, Q = Q0 + ql;
+            if (R >= H || Q >= W) continue;
+            const size_t up = (size_t)R * W, dn = (size_t)(H - 1 - R) * W;
+            const int qf = W - 1 - Q;
+            const float* t = lds + ql * D8_S + rl;
+            const float acc = ((ap[up + Q] + ap[CHW + up + qf]) + ap[2 * CHW + dn + Q]) + ap[3 * CHW + dn + qf];
+            o[up + Q] = 0.125f * ((((acc + t[0]) + t[M]) + t[2 * M]) + t[3 * M]);
+        }
+    }
+}
+
+inline bool d8_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 }  // namespace
 
 extern "C" int dasr_u8_to_planar(const uint8_t* src, int32_t H, int32_t W, int32_t Hc, int32_t Wc, float* dst, void* stream) {
@@ -284,5 +436,28 @@ extern "C" int dasr_crops_down4_u8(const dasr_srn_u8_desc* descs_dev, const dasr
     for (int t = 0; t < D4_TAPS; ++t) wt.w[t] = w18[t];
     const int tiles = (size + D4_T - 1) / D4_T;
     DASR_LAUNCH(crops_down4_u8_kernel, dim3((unsigned)(tiles * tiles), (unsigned)n), dim3(256), 0, as_stream(stream), descs_dev, (int)size, tiles, wt);
+    return (int)hipGetLastError();
+}
+
+extern "C" int dasr_dihedral8(const float* x, int32_t C, int32_t H, int32_t W, float* dst_a, float* dst_b, void* stream) {
+    if (!x || !dst_a || !dst_b || C <= 0 || C > 65535 || H <= 0 || W <= 0 || dst_a == x || dst_b == x || dst_a == dst_b) return DASR_EINVAL;
+    const dim3 grid((unsigned)((W + D8_T - 1) / D8_T), (unsigned)((H + D8_T - 1) / D8_T), (unsigned)C);
+    if (grid.y > 65535) return DASR_EINVAL;
+    const bool vw = W % 4 == 0 && d8_al16(x) && d8_al16(dst_a), vh = H % 4 == 0 && d8_al16(dst_b);
+    auto k = vw ? (vh ? dihedral8_kernel<true, true> : dihedral8_kernel<true, false>) : (vh ? dihedral8_kernel<false, true> : dihedral8_kernel<false, false>);
+    DASR_LAUNCH_TAG("dihedral8_kernel", k, grid, dim3(256), 0, as_stream(stream), x, (int)H, (int)W, dst_a, dst_b);
+    return (int)hipGetLastError();
+}
+
+extern "C" int dasr_dihedral8_mean(const float* sr_a, const float* sr_b, int32_t C, int32_t H, int32_t W, float* dst, void* stream) {
+    if (!sr_a || !sr_b || !dst || C <= 0 || C > 65535 || H <= 0 || W <= 0 || dst == sr_a || dst == sr_b) return DASR_EINVAL;
+    const dim3 grid((unsigned)((W + D8_T - 1) / D8_T), (unsigned)((H + D8_T - 1) / D8_T), (unsigned)C);
+    if (grid.y > 65535) return DASR_EINVAL;
+    const bool vw = W % 4 == 0 && d8_al16(sr_a) && d8_al16(dst), vh = H % 4 == 0 && d8_al16(sr_b);
+    auto k = vw ? (vh ? dihedral8_mean_kernel<true, true> : dihedral8_mean_kernel<true, false>)
+                : (vh ? dihedral8_mean_kernel<false, true> : dihedral8_mean_kernel<false, false>);
+    const int lds = 4 * D8_T * D8_S * (int)sizeof(float);
+    HIP_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds));   // (per call: the attribute belongs to the current device)
+    DASR_LAUNCH_TAG("dihedral8_mean_kernel", k, grid, dim3(256), (size_t)lds, as_stream(stream), sr_a, sr_b, (int)H, (int)W, dst);
     return (int)hipGetLastError();
 }

@@ -311,13 +311,13 @@ class DASR_Model(BaseModel):
 
     def test(self, tsamples=False):
         """inference on var_L (DASR_model.py:333-345; `chop`: quadrant inference, utils/util.py:87-147)"""
-        if self.opt['chop']:
-            from .util import forward_chop
-            self.fake_H = forward_chop(self.var_L, self.opt['scale'], lambda x: self.netG.forward(x).clone(), min_size=320000)
-        else:
-            self.fake_H = self.netG.forward(self.var_L).clone()
+        self.fake_H = self._generate(self.var_L)
         if not tsamples and self.opt['val_lpips']:
-            self.LPIPS = lpips_metric(self.cri_fea_lpips, self.fake_H, self.var_H)   # DASR_model.py:340-344
+            self._eval_lpips()
+
+    def _eval_lpips(self):
+        """LPIPS of fake_H against the ground truth of the last feed_data (DASR_model.py:340-344)"""
+        self.LPIPS = lpips_metric(self.cri_fea_lpips, self.fake_H, self.var_H)
 
     def filter_high(self, x):
         """self.filter_high of the reference (DASR_model.py:58,61-66: FilterHigh(kernel_size=fs_kernel_size, gaussian = fs is not 'avgpool'),

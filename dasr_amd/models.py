@@ -1,6 +1,6 @@
 """Trainer objects with the reference's duck-typed interface (codes/SRN/models/base_model.py:6-85,
 SR_model.py:18-173, DASR_model.py:24-460): update_learning_rate / feed_data / optimize_parameters /
-get_current_log / get_current_learning_rate / test / get_current_visuals / save / save_training_state /
+get_current_log / get_current_learning_rate / test / test_x8 / get_current_visuals / save / save_training_state /
 resume_training, and the same checkpoint files ({iter}_G.pth, {iter}_D_target.pth, {iter}.state).
 
 All arithmetic of the step runs in libdasr_hip.so; this file only sequences recorded op lists, keeps the
@@ -187,6 +187,32 @@ class BaseModel:
         if hr.shape[1:] != sr.shape[1:]:
             raise RuntimeError('current_metrics: HR %s does not belong to SR %s (the last feed_data carried no HR?)' % (tuple(hr.shape), tuple(sr.shape)))
         return self._device_metrics().image_metrics(sr.detach()[:1], hr.detach()[:1], crop)
+
+    # ---- inference ----------------------------------------------------------------------------------------------------------------
+    def _generate(self, x):
+        """the generator as test() runs it on a batch x: netG.forward, inside the quadrant inference of util.forward_chop under `chop` (DASR_model.py:333-339,
+        util.py:87-147).  The result is the caller's own (netG.forward returns a plan's output buffer, which the next forward of that shape overwrites)."""
+        if self.opt['chop']:
+            from .util import forward_chop
+            return forward_chop(x, self.opt['scale'], lambda t: self.netG.forward(t).clone(), min_size=320000)
+        return self.netG.forward(x).clone()
+
+    def test_x8(self):
+        """geometric self-ensemble inference on var_L (SR_model.py:102-140), same contract as test(): sets fake_H [1, C, sH, sW] and, under `val_lpips`, LPIPS (the
+        reference's test_x8 never computes it; here the drivers need no second code path).  The generator runs on the eight flips / transposes of the LR image,
+        every transform is undone on its SR image, the eight are averaged.  The reference moves every transform through numpy on the host and runs eight batch-1
+        forwards; here dasr_dihedral8 writes the two batches of 4 (untransposed / transposed members), the generator runs twice at batch 4 -- the batch the quadrant
+        inference already uses -- and dasr_dihedral8_mean undoes and averages in one launch, with a fixed order of the adds."""
+        from .util import dihedral8, dihedral8_mean
+        if self.var_L.dim() != 4 or self.var_L.shape[0] != 1:
+            # the reference's mean(dim=0) over the concatenated list would average DIFFERENT images into one; its validation / test loaders are batch 1
+            raise ValueError('test_x8 takes a batch of 1 LR image, got a batch of shape %s: the self-ensemble averages over the batch axis, a larger batch would '
+                             'average different images into one' % (tuple(self.var_L.shape),))
+        lr_a, lr_b = dihedral8(self.var_L[0])
+        sr_a = self._generate(lr_a)   # (its own tensor: for a square image both batches run on the same plan)
+        self.fake_H = dihedral8_mean(sr_a, self._generate(lr_b))
+        if self.opt['val_lpips']:
+            self._eval_lpips()
 
     def get_network_description(self, network):
         n = network.params.total
@@ -483,16 +509,16 @@ class SRModel(BaseModel):
 
     def test(self):
         """inference on var_L (SR_model.py:87-93; `chop`: quadrant inference of DASR_model.py:333-339 / util.py:87-147)"""
-        if self.opt['chop']:
-            from .util import forward_chop
-            self.fake_H = forward_chop(self.var_L, self.opt['scale'], lambda x: self.netG.forward(x).clone(), min_size=320000)
-        else:
-            self.fake_H = self.netG.forward(self.var_L).clone()
-        if self.opt['val_lpips']:    # SR_model.py:95-99
-            from .lpips import load_lpips, lpips_metric
-            if getattr(self, 'cri_fea_lpips', None) is None:
-                self.cri_fea_lpips = load_lpips(self.opt, self.device)
-            self.LPIPS = lpips_metric(self.cri_fea_lpips, self.fake_H, self.real_H)
+        self.fake_H = self._generate(self.var_L)
+        if self.opt['val_lpips']:
+            self._eval_lpips()
+
+    def _eval_lpips(self):
+        """LPIPS of fake_H against the ground truth of the last feed_data (SR_model.py:95-99)"""
+        from .lpips import load_lpips, lpips_metric
+        if getattr(self, 'cri_fea_lpips', None) is None:
+            self.cri_fea_lpips = load_lpips(self.opt, self.device)
+        self.LPIPS = lpips_metric(self.cri_fea_lpips, self.fake_H, self.real_H)
 
     def get_current_visuals(self, need_HR=True):
         out = OrderedDict()

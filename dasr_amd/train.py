@@ -95,6 +95,9 @@ def create_dataset(ds_opt, opt):
                               'the boundary; feed their batch dicts to the trainer object).'.format(str(mode)))
 
 
+SELF_ENSEMBLE_NOTE = 'self_ensemble: x8 self-ensemble inference is on (test_x8: the generator on the eight flips / transposes of every LR image, their SR images averaged)'
+
+
 def validate(model, val_set, opt, current_step, logger):
     """validation pass of codes/SRN/train.py:174-235: test() per image, SR image saved, PSNR on the `scale`-pixel-cropped uint8 images"""
     from . import util
@@ -105,7 +108,10 @@ def validate(model, val_set, opt, current_step, logger):
         img_dir = os.path.join(opt['path']['val_images'], img_name)
         util.mkdir(img_dir)
         model.feed_data(val_data, False)
-        model.test()
+        if opt['self_ensemble']:   # x8 geometric self-ensemble (BaseModel.test_x8), same outputs as test()
+            model.test_x8()
+        else:
+            model.test()
         dev = bool(opt['device_metrics'])   # image quantised and PSNR formed on the GPU (dasr_amd/metrics.py); absent: the host path below
         if dev:
             sr_img, lpips = model.current_sr_u8(), (model.LPIPS if opt['val_lpips'] else None)
@@ -238,6 +244,8 @@ def main(argv=None):
     if resume_state:
         start_epoch, current_step = resume_state['epoch'], resume_state['iter']
         model.resume_training(resume_state, opt['train'])
+    if opt['self_ensemble'] and val_set is not None:
+        logger.info(SELF_ENSEMBLE_NOTE)
     logger.info('Start training from epoch: {:d}, iter: {:d}'.format(start_epoch, current_step))
     for epoch in range(start_epoch, total_epochs):
         for batch in train_set:

@@ -1,7 +1,7 @@
-"""Validation / inference helpers of the SRN trainer boundary: image conversion, PSNR / SSIM, quadrant inference.
+"""Validation / inference helpers of the SRN trainer boundary: image conversion, PSNR / SSIM, quadrant inference, the geometry of the x8 self-ensemble.
 
 Reference: codes/SRN/utils/util.py:87-147 (forward_chop), :180-204 (tensor2img), :236-291 (calculate_psnr / ssim / calculate_ssim),
-codes/SRN/data/util.py:169-190 (bgr2ycbcr).  The metrics are host-side numpy on uint8-range images (they are not on the hot path);
+codes/SRN/data/util.py:169-190 (bgr2ycbcr), codes/SRN/models/SR_model.py:102-140 (test_x8: dihedral8_*).  The metrics are host-side numpy on uint8-range images (they are not on the hot path);
 the network forward underneath test() / forward_chop runs on the HIP kernels.  cv2 is not required: the 11x11 Gaussian window
 (sigma 1.5) and the 'valid' filtering that the reference obtains from cv2.getGaussianKernel / cv2.filter2D(...)[5:-5, 5:-5] are
 written out with numpy (the cropped region never sees cv2's border handling, so the result is the same).
@@ -152,3 +152,61 @@ def forward_chop(img, scale, model, shave=20, min_size=160000):
     y[..., bt, l] = ys[2][..., bt_r, l]
     y[..., bt, r] = ys[3][..., bt_r, r_r]
     return y
+
+
+# ---- x8 geometric self-ensemble (codes/SRN/models/SR_model.py:102-140) ---------------------------------------------------------------
+# Member i = 0..7 in the order the reference's list construction produces (lr_list grows by 'v', then 'h', then 't'): b0 = i & 1 flips along W, b1 = (i >> 1) & 1
+# flips along H, b2 = i >> 2 transposes, applied last: y_i = T^b2 H^b1 V^b0 x.  The inverse undoes them in the opposite order.
+
+def dihedral8_reference(x):
+    """the eight members of [..., H, W] tensor x as a list, by index arithmetic alone (the statement dasr_dihedral8 is tested against)"""
+    out = []
+    for i in range(8):
+        y = x
+        if i & 1:
+            y = y.flip(-1)
+        if (i >> 1) & 1:
+            y = y.flip(-2)
+        if i >> 2:
+            y = y.transpose(-1, -2)
+        out.append(y.contiguous())
+    return out
+
+
+def dihedral8_mean_reference(srs):
+    """srs: the eight SR images, member i transformed as dihedral8_reference's -> every transform undone, then
+    0.125 * (((((((s0 + s1) + s2) + s3) + s4) + s5) + s6) + s7) in the dtype of the inputs: the order dasr_dihedral8_mean adds in"""
+    acc = None
+    for i, y in enumerate(srs):
+        if i >> 2:
+            y = y.transpose(-1, -2)
+        if (i >> 1) & 1:
+            y = y.flip(-2)
+        if i & 1:
+            y = y.flip(-1)
+        acc = y.clone() if acc is None else acc + y
+    return acc * 0.125
+
+
+def dihedral8(x):
+    """device: planar fp32 image [C, H, W] -> ([4, C, H, W] members 0..3, [4, C, W, H] members 4..7), one launch (dasr_dihedral8)"""
+    from . import _lib
+    x = x.contiguous().float()
+    C_, H, W = x.shape
+    a = torch.empty((4, C_, H, W), dtype=torch.float32, device=x.device)
+    b = torch.empty((4, C_, W, H), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().dasr_dihedral8(x.data_ptr(), C_, H, W, a.data_ptr(), b.data_ptr(), torch.cuda.current_stream().cuda_stream), 'dihedral8')
+    return a, b
+
+
+def dihedral8_mean(sr_a, sr_b):
+    """device: the SR batches of dihedral8's two outputs, [4, C, H, W] and [4, C, W, H] -> their inverse-transformed mean [1, C, H, W], one launch with a
+    fixed order of the adds (dasr_dihedral8_mean)"""
+    from . import _lib
+    n, C_, H, W = sr_a.shape
+    if n != 4 or tuple(sr_b.shape) != (4, C_, W, H):
+        raise ValueError('dihedral8_mean: expected [4, C, H, W] and [4, C, W, H], got %s and %s' % (tuple(sr_a.shape), tuple(sr_b.shape)))
+    sr_a, sr_b = sr_a.contiguous().float(), sr_b.contiguous().float()
+    out = torch.empty((1, C_, H, W), dtype=torch.float32, device=sr_a.device)
+    _lib.check(_lib.lib().dasr_dihedral8_mean(sr_a.data_ptr(), sr_b.data_ptr(), C_, H, W, out.data_ptr(), torch.cuda.current_stream().cuda_stream), 'dihedral8_mean')
+    return out

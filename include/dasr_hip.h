@@ -706,6 +706,24 @@ typedef struct {
 int dasr_gather_srn_u8(const dasr_srn_u8_desc* descs_dev, int32_t n, int32_t max_size, void* stream);
 int dasr_crops_down4_u8(const dasr_srn_u8_desc* descs_dev, const dasr_srn_u8_desc* descs_host, int32_t n, int32_t size, const double* w18, void* stream);
 
+/* ---- x8 geometric self-ensemble (csrc/imgio.hip) --------------------------------------------------------------------------------------
+ * The geometry of BaseModel.test_x8 (codes/SRN/models/SR_model.py:102-140): super-resolve the eight flips / transposes of the LR image, undo each transform on its SR
+ * image, average.  Member i = 0..7 as the reference's list construction numbers them: b0 = i & 1 flips along W, b1 = (i >> 1) & 1 flips along H, b2 = i >> 2 transposes
+ * (applied last).  Both calls are ONE launch, asynchronous on `stream`, planar fp32 images, any H, W >= 1 (16-byte accesses when the length along the contiguous axis is a
+ * multiple of 4 and the pointers are 16-byte aligned, one sample per lane otherwise; the transposed half goes through LDS tiles, never a strided global access).
+ *
+ * dasr_dihedral8: x [C][H][W] -> dst_a [4][C][H][W] (members 0..3): dst_a[i][c][r][q] = x[c][b1 ? H-1-r : r][b0 ? W-1-q : q], and dst_b [4][C][W][H] (members 4..7):
+ * dst_b[i-4][c][a][b] = x[c][b1 ? H-1-b : b][b0 ? W-1-a : a].  Exact copies.
+ *
+ * dasr_dihedral8_mean: H, W are the size of the OUTPUT; sr_a [4][C][H][W] and sr_b [4][C][W][H] are the generator's outputs for dst_a and dst_b.
+ * dst[c][R][Q] = 0.125f * (((((((s0 + s1) + s2) + s3) + s4) + s5) + s6) + s7) in fp32, in exactly that order (no contraction, no fast-math: the same inputs give the same
+ * bits), with Rh = b1 ? H-1-R : R, Qv = b0 ? W-1-Q : Q, s_i = sr_a[i][c][Rh][Qv] for i < 4 and s_i = sr_b[i-4][c][Qv][Rh] for i >= 4.
+ *
+ * A null pointer, C, H or W <= 0, C > 65535, H > 65535 * 64, or a destination equal to a source (or dst_a == dst_b): DASR_EINVAL, nothing is launched.  The buffers must
+ * not overlap in any other way either (not checked). */
+int dasr_dihedral8(const float* x, int32_t C, int32_t H, int32_t W, float* dst_a, float* dst_b, void* stream);
+int dasr_dihedral8_mean(const float* sr_a, const float* sr_b, int32_t C, int32_t H, int32_t W, float* dst, void* stream);
+
 /* ---- profiling session (bench.py `roofline`) -----------------------------------------------------------
  * Between dasr_prof_begin and dasr_prof_end every kernel launch of the library (up to `capacity`) carries its own start/stop
  * events on its launch stream (hipExtLaunchKernel: the dispatch's begin/end timestamps, what rocprofv3 --kernel-trace prints).
