@@ -8,11 +8,12 @@ launches that write the five batch tensors of the reference's dict directly in H
 reference's order (np.random for the unpaired indices, `random` for the crop origins and the three augmentation coins), so with
 equal seeds and num_workers=0 the batches coincide.  Image decoding (PIL) stays on the host and happens once per file.
 
-`"resident_u8": true` in `datasets.train` (both training datasets): the files are decoded once on `n_workers` threads (dsn_data.load_resident) and stay in device
+`"resident_u8": true` in `datasets.train` (both training datasets): the files are decoded once on `n_workers` threads (imgio.load_resident) and stay in device
 memory as the BYTES PIL decodes (uint8 [H][W][3], a quarter of the fp32 store); the domain-distance maps stay fp32.  A batch is one descriptor block in pinned memory,
-one asynchronous upload and at most three launches: dasr_gather_srn_u8 (every 3-channel tensor of the batch), dasr_gather_crops (fake_w) and, for `mode: "LRHR"` without
+one asynchronous upload (imgio.upload: the fp32 store takes the same road) and at most three launches: dasr_gather_srn_u8 (every 3-channel tensor of the batch), dasr_gather_crops (fake_w) and, for `mode: "LRHR"` without
 LR files, dasr_crops_down4_u8 (the LR crops, straight from the HR bytes).  The random draws are the same calls in the same order, so equal seeds give equal batches with
 and without the key: bit for bit, except the LR images made on the device (one rounding to fp32 of the fp64 evaluation: within 2^-23 of imresize_matlab).
+The host side of csrc/imgio.hip that the DSN datasets use as well (decode, resident store, tap tables, descriptor upload) is imgio.py.
 """
 import ctypes as C
 import logging
@@ -24,7 +25,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import _stream, ensure_runtime_ready
+from .engine import _stream
+from .imgio import bicubic_taps, decode_u8, device_of, down4_weights, fill_crop_desc, image_header, load_resident, tap_table, u8_to_chw, upload
 
 IMG_EXTENSIONS = ('.jpg', '.JPG', '.jpeg', '.JPEG', '.png', '.PNG', '.ppm', '.PPM', '.bmp', '.BMP')
 
@@ -44,9 +46,7 @@ def load_image(path):
     if path.endswith('.npy'):
         a = np.load(path)
         return torch.from_numpy(np.ascontiguousarray(a[0] if a.ndim == 4 else a)).float()
-    from PIL import Image
-    a = np.asarray(Image.open(path).convert('RGB'), dtype=np.float32) / 255.0
-    return torch.from_numpy(a).permute(2, 0, 1).contiguous()
+    return u8_to_chw(decode_u8(path)).contiguous()
 
 
 def _hw(t):
@@ -58,19 +58,16 @@ def _u8_header(path):
     """(H, W) of an image file that can be stored as the bytes PIL decodes, from its header; ValueError naming the file otherwise"""
     if path.endswith('.npy'):
         raise ValueError('%s: a .npy file in an image folder cannot be kept as 8-bit samples; drop "resident_u8" or convert the file' % path)
-    from PIL import Image
-    with Image.open(path) as im:
-        if im.mode != 'RGB':
-            raise ValueError("%s: mode '%s' (grey, palette or alpha), which convert('RGB') would have to change; \"resident_u8\" takes 8-bit RGB files only" % (path, im.mode))
-        w, h = im.size
+    h, w, mode = image_header(path)
+    if mode != 'RGB':
+        raise ValueError("%s: mode '%s' (grey, palette or alpha), which convert('RGB') would have to change; \"resident_u8\" takes 8-bit RGB files only" % (path, mode))
     return h, w
 
 
 def load_resident_u8(lists, ds_opt, device=None, max_bytes=None, t0=None):
     """`resident_u8` store: lists {name: [paths]} -> (device, {name: [uint8 [H, W, 3] tensors]}), decoded once on `n_workers` threads (16 at most) by
-    dsn_data.load_resident.  Cap: max_bytes, else `resident_max_bytes` of the options, else half of the device memory free right now; over it: MemoryError.  Logs once
+    imgio.load_resident.  Cap: max_bytes, else `resident_max_bytes` of the options, else half of the device memory free right now; over it: MemoryError.  Logs once
     (logger 'base') the number of files, the bytes resident on this rank (every rank holds the whole set) and the construction time since t0."""
-    from .dsn_data import load_resident
     t0 = time.perf_counter() if t0 is None else t0
     cap = max_bytes if max_bytes is not None else ds_opt.get('resident_max_bytes')
     dev, out = load_resident(list(lists.values()), device, threads=ds_opt.get('n_workers') or 1, max_bytes=cap,
@@ -83,24 +80,10 @@ def load_resident_u8(lists, ds_opt, device=None, max_bytes=None, t0=None):
     return dev, dict(zip(lists, out)), nbytes
 
 
-_W18 = None
-
-
-def down4_weights():
-    """the 18 weights of MATLAB's antialiased bicubic at scale 1 / 4 as a ctypes array: ONE row of bicubic_taps(n, 0.25)[1] -- the sample positions u = 4 k - 1.5 have the
-    same fractional part for every k, so every output sample has bit-equal weights (tests/test_srn_device_data_host.py)"""
-    global _W18
-    if _W18 is None:
-        _W18 = (C.c_double * 18)(*bicubic_taps(32, 0.25)[1][0].tolist())
-    return _W18
-
-
 def assemble_u8(device, gather, ddm=None, down=None):
     """the launches of one `resident_u8` batch.  gather / down: lists of (uint8 image [H, W, 3], y0, x0, size, flags, destination [3, size, size] fp32 view) for
     dasr_gather_srn_u8 / dasr_crops_down4_u8 (for `down` the window is given in the x1/4 image); ddm: (CropDesc array, channels, size, destination) for dasr_gather_crops.
-    ALL descriptors go into one block of pinned memory and cross in one asynchronous copy; no host synchronisation.  Returns the device block (kept by the caller)."""
-    if device.type != 'cuda':
-        raise _lib.DasrHipError('batches are assembled by HIP kernels on images resident in device memory; this dataset was built on %s' % device)
+    ALL descriptors cross in one imgio.upload; no host synchronisation.  Returns the device block (kept by the caller)."""
     n_g, n_d = len(gather), len(down or ())
     descs = (_lib.SrnU8Desc * (n_g + n_d))()
     for k, (img, y0, x0, size, flags, dst) in enumerate(list(gather) + list(down or ())):
@@ -111,73 +94,107 @@ def assemble_u8(device, gather, ddm=None, down=None):
             raise ValueError('crop descriptor outside its image: window %r of %d x %d' % ((y0, x0, size), Hv, Wv))
         d = descs[k]
         d.src, d.H, d.W, d.y0, d.x0, d.size, d.flags, d.dst = img.data_ptr(), H, W, y0, x0, size, flags, dst.data_ptr()
-    sz = C.sizeof(_lib.SrnU8Desc)
-    off_w = C.sizeof(descs)
-    total = off_w + (C.sizeof(ddm[0]) if ddm else 0)
-    staging = torch.empty(total, dtype=torch.uint8, pin_memory=True)   # (torch's pinned-memory cache hands a block out again only after the copy below is done)
-    C.memmove(staging.data_ptr(), descs, off_w)
-    if ddm:
-        C.memmove(staging.data_ptr() + off_w, ddm[0], C.sizeof(ddm[0]))
-    dd = staging.to(device, non_blocking=True)
-    L = _lib.lib()
+    dd, offsets = upload(device, descs, *([ddm[0]] if ddm else []))
+    L, off_d = _lib.lib(), n_g * C.sizeof(_lib.SrnU8Desc)
     if n_g:
         _lib.check(L.dasr_gather_srn_u8(dd.data_ptr(), n_g, max(g[3] for g in gather), _stream()), 'dasr_gather_srn_u8')
     if ddm:
-        _lib.check(L.dasr_gather_crops(dd.data_ptr() + off_w, len(ddm[0]), ddm[1], ddm[2], ddm[3].data_ptr(), _stream()), 'gather_crops')
-    if n_d:
-        _lib.check(L.dasr_crops_down4_u8(dd.data_ptr() + n_g * sz, staging.data_ptr() + n_g * sz, n_d, down[0][3], C.addressof(down4_weights()), _stream()),
-                   'dasr_crops_down4_u8')
+        _lib.check(L.dasr_gather_crops(dd.data_ptr() + offsets[1], len(ddm[0]), ddm[1], ddm[2], ddm[3].data_ptr(), _stream()), 'gather_crops')
+    if n_d:   # (the entry point checks the host copy of its descriptors before it launches)
+        _lib.check(L.dasr_crops_down4_u8(dd.data_ptr() + off_d, C.addressof(descs) + off_d, n_d, down[0][3], C.addressof(down4_weights()), _stream()), 'dasr_crops_down4_u8')
     return dd
 
 
-class DeviceUnpairedDataset:
+class _DeviceBatches:
+    """What the two training datasets share: the option parsing, the size checks of the `resident_u8` store, util.augment's three coins, the fp32-store batch and the
+    iteration in batches over the `count_key` list of the subclass.  A subclass reads its folders, draws a sample and lays out its batch."""
+    count_key = None
+
+    def __init__(self, ds_opt, scale, images, shuffle, drop_last):
+        self.opt, self.scale, self.drop_last = ds_opt, scale, drop_last
+        self.n, self.hr_size = int(ds_opt['batch_size']), int(ds_opt['HR_size'])
+        self.use_flip, self.use_rot = bool(ds_opt.get('use_flip')), bool(ds_opt.get('use_rot'))
+        self.shuffle = bool(ds_opt.get('use_shuffle')) if shuffle is None else shuffle
+        self.resident = bool(ds_opt.get('resident_u8'))
+        if self.resident and images is not None:
+            raise ValueError('images=: "resident_u8" reads the dataroot_* folders itself (decoded bytes); pass images without the key')
+
+    def _store_f32(self, images):
+        self.img = {k: [t.to(self.device, torch.float32).contiguous() for t in v] for k, v in images.items()}
+
+    def _checked_sizes(self, lists, least, lr_key):
+        """{name: [(H, W)]} of the files of lists {name: [paths]}, from their headers (_u8_header refuses what cannot be kept as bytes).  The u8 kernels clamp a window
+        that leaves its image where the fp32 one writes zeros, so a file smaller than its window (least[name]) is refused here, and so is an HR file smaller than
+        scale x its `lr_key` file."""
+        s = self.scale
+        sizes = {k: [_u8_header(p) for p in v] for k, v in lists.items()}
+        for k in lists:
+            for p, (h, w) in zip(lists[k], sizes[k]):
+                if h < least.get(k, 0) or w < least.get(k, 0):
+                    raise ValueError('%s: image %dx%d is smaller than the crop size %d' % (p, h, w, least[k]))
+        for p, (h, w), (hl, wl) in zip(lists['HR'], sizes['HR'], sizes.get(lr_key, ())):
+            if h < s * hl or w < s * wl:
+                raise ValueError('%s: %dx%d is smaller than %d x its LR image (%dx%d)' % (p, h, w, s, hl, wl))
+        return sizes
+
+    def _coins(self):
+        """util.augment's coins as the flag bits of the kernels: hflip 1, vflip 2, transpose 4.  random.random() is drawn only for a switch that is on"""
+        hflip = self.use_flip and random.random() < 0.5
+        vflip = self.use_rot and random.random() < 0.5
+        rot90 = self.use_rot and random.random() < 0.5
+        return int(hflip) | (int(vflip) << 1) | (int(rot90) << 2)
+
+    def _batch_f32(self, tensors):
+        """the fp32-store batch.  tensors: [(key, channels, size, [(image, virt, y0, x0, flags) per sample])] (the arguments of fill_crop_desc): every CropDesc array
+        crosses in ONE imgio.upload, then one dasr_gather_crops launch per tensor; no host synchronisation"""
+        arrays = []
+        for _, _, _, crops in tensors:
+            arrays.append((_lib.CropDesc * len(crops))())
+            for d, crop in zip(arrays[-1], crops):
+                fill_crop_desc(d, *crop)
+        dd, offsets = upload(self.device, *arrays)
+        L, out = _lib.lib(), {'_keep': [dd]}
+        for (key, Cc, size, crops), off in zip(tensors, offsets):
+            out[key] = torch.empty((len(crops), Cc, size, size), dtype=torch.float32, device=self.device)
+            _lib.check(L.dasr_gather_crops(dd.data_ptr() + off, len(crops), Cc, size, out[key].data_ptr(), _stream()), 'gather_crops')
+        return out
+
+    def __len__(self):
+        m = len(self.img[self.count_key])
+        return m // self.n if self.drop_last else (m + self.n - 1) // self.n
+
+    def __iter__(self):
+        m = len(self.img[self.count_key])
+        order = torch.randperm(m).tolist() if self.shuffle else list(range(m))   # DataLoader(shuffle=True): RandomSampler draws from torch's global generator
+        for b in range(len(self)):
+            idx = order[b * self.n:(b + 1) * self.n]
+            if idx:
+                yield self.batch(idx)
+
+
+class DeviceUnpairedDataset(_DeviceBatches):
     """Iterable of batch dicts {'LR_fake','LR_real','HR','HR_unpair','fake_w'} (CUDA tensors) built on the device.
 
     images: dict with lists of CHW fp32 tensors 'fake_LR', 'real_LR', 'HR' and 'fake_w' ([1,h',w'] domain-distance maps, any size)
     -- or None to read `dataroot_*` folders of `ds_opt` (PNG / .npy files)."""
+    count_key = 'fake_LR'
 
     def __init__(self, ds_opt, scale=4, images=None, device=None, shuffle=None, drop_last=True, max_bytes=None):
-        self.opt, self.scale = ds_opt, scale
-        self.n = int(ds_opt['batch_size'])
-        self.hr_size = int(ds_opt['HR_size'])
-        self.use_flip, self.use_rot = bool(ds_opt.get('use_flip')), bool(ds_opt.get('use_rot'))
-        self.shuffle = bool(ds_opt.get('use_shuffle')) if shuffle is None else shuffle
-        self.resident = bool(ds_opt.get('resident_u8'))
+        super().__init__(ds_opt, scale, images, shuffle, drop_last)
         folders = (('fake_LR', 'dataroot_fake_LR'), ('real_LR', 'dataroot_real_LR'), ('HR', 'dataroot_HR'), ('fake_w', 'dataroot_fake_weights'))
-        if self.resident:
-            self._load_u8(folders, images, device, max_bytes)
+        LRs = self.hr_size // scale
+        self.shapes = (('LR_fake', 3, LRs), ('LR_real', 3, LRs), ('HR', 3, self.hr_size), ('HR_unpair', 3, self.hr_size), ('fake_w', 1, LRs))
+        if self.resident:   # the three image folders as bytes, the domain-distance maps as fp32 (dasr_gather_crops resizes them bilinearly)
+            t0 = time.perf_counter()
+            lists = {k: image_paths(ds_opt[r]) for k, r in folders[:3]}
+            self._checked_sizes(lists, {'fake_LR': LRs, 'real_LR': LRs, 'HR': self.hr_size}, 'fake_LR')
+            self.device, self.img, self.resident_bytes = load_resident_u8(lists, ds_opt, device, max_bytes, t0)
+            self.img['fake_w'] = [load_image(p).to(self.device, torch.float32).contiguous() for p in image_paths(ds_opt[folders[3][1]])]
         else:
-            ensure_runtime_ready()
-            self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-            if images is None:
-                images = {k: [load_image(p) for p in image_paths(ds_opt[r])] for k, r in folders}
-            self.img = {k: [t.to(self.device, torch.float32).contiguous() for t in v] for k, v in images.items()}
+            self.device = device_of(device)
+            self._store_f32(images if images is not None else {k: [load_image(p) for p in image_paths(ds_opt[r])] for k, r in folders})
         assert self.img['HR'], 'Error: HR path is empty.'
         assert len(self.img['fake_LR']) == len(self.img['HR']) == len(self.img['fake_w'])
-        self.drop_last = drop_last
-
-    def _load_u8(self, folders, images, device, max_bytes):
-        """the `resident_u8` store: the three image folders as bytes, the domain-distance maps as fp32 (dasr_gather_crops resizes them bilinearly).  The u8 kernel clamps
-        a window that leaves its image where the fp32 one writes zeros, so files smaller than their window are refused here."""
-        t0 = time.perf_counter()
-        if images is not None:
-            raise ValueError('images=: "resident_u8" reads the dataroot_* folders itself (decoded bytes); pass images without the key')
-        s, HRs = self.scale, self.hr_size
-        lists = {k: image_paths(self.opt[r]) for k, r in folders[:3]}
-        sizes = {k: [_u8_header(p) for p in v] for k, v in lists.items()}
-        for k, least in (('fake_LR', HRs // s), ('real_LR', HRs // s), ('HR', HRs)):
-            for p, (h, w) in zip(lists[k], sizes[k]):
-                if h < least or w < least:
-                    raise ValueError('%s: image %dx%d is smaller than the crop size %d' % (p, h, w, least))
-        for p, (h, w), (hl, wl) in zip(lists['HR'], sizes['HR'], sizes['fake_LR']):
-            if h < s * hl or w < s * wl:
-                raise ValueError('%s: %dx%d is smaller than %d x its LR image (%dx%d)' % (p, h, w, s, hl, wl))
-        self.device, self.img, self.resident_bytes = load_resident_u8(lists, self.opt, device, max_bytes, t0)
-        self.img['fake_w'] = [load_image(p).to(self.device, torch.float32).contiguous() for p in image_paths(self.opt[folders[3][1]])]
-
-    def __len__(self):
-        m = len(self.img['fake_LR'])
-        return m // self.n if self.drop_last else (m + self.n - 1) // self.n
 
     def sample(self, index):
         """descriptor of one sample; consumes the RNGs exactly like the reference's __getitem__ (train phase)"""
@@ -193,83 +210,20 @@ class DeviceUnpairedDataset:
         y_r, x_r = random.randint(0, max(0, Hr - LRs)), random.randint(0, max(0, Wr - LRs))
         Hu, Wu = _hw(hu)
         y_u, x_u = random.randint(0, max(0, Hu - HRs)), random.randint(0, max(0, Wu - HRs))
-        hflip = self.use_flip and random.random() < 0.5
-        vflip = self.use_rot and random.random() < 0.5
-        rot90 = self.use_rot and random.random() < 0.5
-        flags = int(hflip) | (int(vflip) << 1) | (int(rot90) << 2)
         return {'LR_fake': (lf, None, y_f, x_f), 'LR_real': (lr_, None, y_r, x_r), 'HR': (hr, None, y_f * s, x_f * s), 'HR_unpair': (hu, None, y_u, x_u),
-                'fake_w': (fw, (H, W), y_f, x_f), 'flags': flags}
-
-    def _batch_u8(self, samples):
-        n, LRs, HRs = len(samples), self.hr_size // self.scale, self.hr_size
-        out = {key: torch.empty((n, 1 if key == 'fake_w' else 3, size, size), dtype=torch.float32, device=self.device)
-               for key, size in (('LR_fake', LRs), ('LR_real', LRs), ('HR', HRs), ('HR_unpair', HRs), ('fake_w', LRs))}
-        gather = [(smp[key][0], smp[key][2], smp[key][3], out[key].shape[2], smp['flags'], out[key][k])
-                  for key in ('LR_fake', 'LR_real', 'HR', 'HR_unpair') for k, smp in enumerate(samples)]
-        descs = (_lib.CropDesc * n)()
-        for d, smp in zip(descs, samples):
-            t, virt, y0, x0 = smp['fake_w']
-            d.src, d.C, d.H, d.W = t.data_ptr(), t.shape[0], t.shape[1], t.shape[2]
-            d.vH, d.vW, d.y0, d.x0, d.flags = virt[0], virt[1], y0, x0, smp['flags']
-        out['_keep'] = [assemble_u8(self.device, gather, ddm=(descs, 1, LRs, out['fake_w']))]
-        return out
+                'fake_w': (fw, (H, W), y_f, x_f), 'flags': self._coins()}
 
     def batch(self, indices):
         samples = [self.sample(i) for i in indices]
-        if self.resident:
-            return self._batch_u8(samples)
-        out = {}
-        L = _lib.lib()
-        for key, size in (('LR_fake', self.hr_size // self.scale), ('LR_real', self.hr_size // self.scale), ('HR', self.hr_size), ('HR_unpair', self.hr_size),
-                          ('fake_w', self.hr_size // self.scale)):
-            Cc = 1 if key == 'fake_w' else 3
-            descs = (_lib.CropDesc * len(samples))()
-            for d, smp in zip(descs, samples):
-                t, virt, y0, x0 = smp[key]
-                d.src, d.C, d.H, d.W = t.data_ptr(), t.shape[0], t.shape[1], t.shape[2]
-                d.vH, d.vW = virt if virt is not None else (t.shape[1], t.shape[2])
-                d.y0, d.x0, d.flags = y0, x0, smp['flags']
-            dd = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(self.device)
-            dst = torch.empty((len(samples), Cc, size, size), dtype=torch.float32, device=self.device)
-            _lib.check(L.dasr_gather_crops(dd.data_ptr(), len(samples), Cc, size, dst.data_ptr(), _stream()), 'gather_crops')
-            out[key] = dst
-            out.setdefault('_keep', []).append(dd)
+        if not self.resident:
+            return self._batch_f32([(key, Cc, size, [smp[key] + (smp['flags'],) for smp in samples]) for key, Cc, size in self.shapes])
+        out = {key: torch.empty((len(samples), Cc, size, size), dtype=torch.float32, device=self.device) for key, Cc, size in self.shapes}
+        gather = [(smp[key][0], smp[key][2], smp[key][3], size, smp['flags'], out[key][k]) for key, _, size in self.shapes[:4] for k, smp in enumerate(samples)]
+        descs = (_lib.CropDesc * len(samples))()
+        for d, smp in zip(descs, samples):
+            fill_crop_desc(d, *smp['fake_w'], smp['flags'])
+        out['_keep'] = [assemble_u8(self.device, gather, ddm=(descs, 1, self.shapes[4][2], out['fake_w']))]
         return out
-
-    def __iter__(self):
-        m = len(self.img['fake_LR'])
-        order = list(range(m))
-        if self.shuffle:
-            order = torch.randperm(m).tolist()   # DataLoader(shuffle=True): RandomSampler draws from torch's global generator
-        for b in range(len(self)):
-            idx = order[b * self.n:(b + 1) * self.n]
-            if idx:
-                yield self.batch(idx)
-
-
-def bicubic_taps(n_in, scale):
-    """per-output-sample taps of MATLAB's imresize along one axis, in float64: (j, w), both [n_out, taps] with taps = ceil(kernel width) + 2.  Bicubic kernel (a = -0.5),
-    widened by 1 / scale and scaled by `scale` when shrinking (antialiasing), weights normalised to sum 1 per output sample, samples beyond the ends mirrored about the edge
-    (the edge sample itself repeated): j is the 0-based source index after mirroring.  Output sample k (1-based) sits at u = k / scale + (1 - 1 / scale) / 2 in input
-    coordinates.  What codes/SRN/data/util.py:243-297 computes.  The dense matrix of imresize_matlab and the device tables of dasr_imresize_down both come from here."""
-    import math
-    n_out = int(math.ceil(n_in * scale))
-    width = 4.0 / scale if scale < 1 else 4.0
-    taps = int(math.ceil(width)) + 2
-    k = torch.arange(1, n_out + 1, dtype=torch.float64)
-    u = k / scale + 0.5 * (1.0 - 1.0 / scale)
-    left = torch.floor(u - width / 2.0)
-    idx = left[:, None] + torch.arange(taps, dtype=torch.float64)[None, :]        # 1-based input positions
-    d = (u[:, None] - idx) * (scale if scale < 1 else 1.0)
-    a = d.abs()
-    w = torch.where(a <= 1, 1.5 * a ** 3 - 2.5 * a ** 2 + 1, torch.where(a <= 2, -0.5 * a ** 3 + 2.5 * a ** 2 - 4 * a + 2, torch.zeros_like(a)))
-    if scale < 1:
-        w = w * scale
-    w = w / w.sum(1, keepdim=True)
-    j = idx.long() - 1                                                              # 0-based; mirror: -1 -> 0, -2 -> 1, n -> n - 1, n + 1 -> n - 2
-    j = torch.where(j < 0, -j - 1, j)
-    j = torch.where(j >= n_in, 2 * n_in - 1 - j, j).clamp_(0, n_in - 1)
-    return j, w
 
 
 def _bicubic_resample_matrix(n_in, scale):
@@ -290,25 +244,34 @@ def imresize_matlab(img, scale):
     return torch.einsum('oh,chw,pw->cop', Mh, x, Mw).to(img.dtype)
 
 
-class DevicePairedDataset:
+class DevicePairedDataset(_DeviceBatches):
     """`mode: "LRHR"` with LR files given (codes/SRN/data/LRHR_dataset.py:44-126, train phase): {'LR','HR'} batches assembled on the
     device.  Per sample the reference draws random.randint twice (crop origin in the LR image) and then util.augment's coins.
     Without `dataroot_LR` the LR images are made from the HR images by MATLAB-style bicubic down-sampling (imresize_matlab), once, at construction: the reference's train
     phase does the same per sample with random_scale_list = [1] (LRHR_dataset.py:63-88) whenever the HR size is a multiple of `scale` -- the case taken here; other sizes
-    go through cv2.resize(INTER_LINEAR) there first, and an HR image smaller than HR_size is resized: both stay on the reference's side (NotImplementedError)."""
+    go through cv2.resize(INTER_LINEAR) there first, and an HR image smaller than HR_size is resized: both stay on the reference's side (NotImplementedError).
+    Under `resident_u8` without LR files nothing is made at construction: dasr_crops_down4_u8 makes the LR crops per batch from the HR bytes (img['LR'] is None)."""
+    count_key = 'HR'
 
     def __init__(self, ds_opt, scale=4, images=None, device=None, shuffle=None, drop_last=True, max_bytes=None):
-        self.opt, self.scale = ds_opt, scale
-        self.n, self.hr_size = int(ds_opt['batch_size']), int(ds_opt['HR_size'])
-        self.use_flip, self.use_rot = bool(ds_opt.get('use_flip')), bool(ds_opt.get('use_rot'))
-        self.shuffle = bool(ds_opt.get('use_shuffle')) if shuffle is None else shuffle
-        self.resident = bool(ds_opt.get('resident_u8'))
+        super().__init__(ds_opt, scale, images, shuffle, drop_last)
         if self.resident:
-            self._load_u8(images, device, max_bytes)
+            t0 = time.perf_counter()
+            lists = {'HR': self.hr_paths(ds_opt)}
+            if ds_opt.get('dataroot_LR'):
+                lists['LR'] = image_paths(ds_opt['dataroot_LR'])
+            elif scale != 4 or self.hr_size // scale > 128:
+                raise NotImplementedError('"resident_u8" without dataroot_LR: the LR crops are made on the device for scale 4 and LR crops up to 128 x 128 (got scale %d, '
+                                          'HR_size %d); provide LR files or drop "resident_u8"' % (scale, self.hr_size))
+            sizes = self._checked_sizes(lists, {'LR': self.hr_size // scale}, 'LR')
+            if 'LR' not in lists:
+                for h, w in sizes['HR']:
+                    self._check_multiple(h, w)
+            self.device, self.img, self.resident_bytes = load_resident_u8(lists, ds_opt, device, max_bytes, t0)
+            self.img.setdefault('LR', None)
         else:
             paths_HR = self.hr_paths(ds_opt) if images is None else None
-            ensure_runtime_ready()
-            self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+            self.device = device_of(device)
             if images is None:
                 hr = [load_image(p) for p in paths_HR]
                 images = {'HR': hr, 'LR': [load_image(p) for p in image_paths(ds_opt['dataroot_LR'])] if ds_opt.get('dataroot_LR') else None}
@@ -316,12 +279,11 @@ class DevicePairedDataset:
                 for t in images['HR']:
                     self._check_multiple(t.shape[1], t.shape[2])
                 images = dict(images, LR=[imresize_matlab(t.float().cpu(), 1.0 / scale) for t in images['HR']])
-            self.img = {k: [t.to(self.device, torch.float32).contiguous() for t in v] for k, v in images.items()}
+            self._store_f32(images)
         assert self.img['HR'], 'Error: HR path is empty.'
         if self.img['LR'] is not None:
             assert len(self.img['LR']) == len(self.img['HR']), 'HR and LR datasets have different number of images - {}, {}.'.format(
                 len(self.img['LR']), len(self.img['HR']))
-        self.drop_last = drop_last
 
     @staticmethod
     def hr_paths(ds_opt):
@@ -339,36 +301,6 @@ class DevicePairedDataset:
             raise NotImplementedError('LRHR without dataroot_LR: HR image of %d x %d is not a multiple of scale %d (the reference resizes it with cv2 first); '
                                       'crop the HR images or provide LR files' % (H, W, self.scale))
 
-    def _load_u8(self, images, device, max_bytes):
-        """the `resident_u8` store: HR (and LR, when there is a folder of them) as bytes.  Without LR files nothing is made at construction: dasr_crops_down4_u8 makes
-        the LR crops per batch from the HR bytes (img['LR'] is None)."""
-        t0 = time.perf_counter()
-        if images is not None:
-            raise ValueError('images=: "resident_u8" reads the dataroot_* folders itself (decoded bytes); pass images without the key')
-        s, HRs = self.scale, self.hr_size
-        lists = {'HR': self.hr_paths(self.opt)}
-        if self.opt.get('dataroot_LR'):
-            lists['LR'] = image_paths(self.opt['dataroot_LR'])
-        elif s != 4 or HRs // s > 128:
-            raise NotImplementedError('"resident_u8" without dataroot_LR: the LR crops are made on the device for scale 4 and LR crops up to 128 x 128 (got scale %d, '
-                                      'HR_size %d); provide LR files or drop "resident_u8"' % (s, HRs))
-        sizes = {k: [_u8_header(p) for p in v] for k, v in lists.items()}
-        if 'LR' in lists:
-            for (p, (h, w)), ph, (hh, wh) in zip(zip(lists['LR'], sizes['LR']), lists['HR'], sizes['HR']):
-                if h < HRs // s or w < HRs // s:
-                    raise ValueError('%s: image %dx%d is smaller than the crop size %d' % (p, h, w, HRs // s))
-                if hh < s * h or wh < s * w:
-                    raise ValueError('%s: %dx%d is smaller than %d x its LR image (%dx%d)' % (ph, hh, wh, s, h, w))
-        else:
-            for h, w in sizes['HR']:
-                self._check_multiple(h, w)
-        self.device, self.img, self.resident_bytes = load_resident_u8(lists, self.opt, device, max_bytes, t0)
-        self.img.setdefault('LR', None)
-
-    def __len__(self):
-        m = len(self.img['HR'])
-        return m // self.n if self.drop_last else (m + self.n - 1) // self.n
-
     def _draw(self, idx):
         """(y0, x0, flags) of sample idx: the crop origin in the LR image, then util.augment's three coins"""
         s, HRs = self.scale, self.hr_size
@@ -378,57 +310,22 @@ class DevicePairedDataset:
             raise NotImplementedError('HR image smaller than HR_size (the reference resizes it and re-derives LR by imresize on the host)')
         Hl, Wl = _hw(self.img['LR'][idx]) if self.img['LR'] is not None else (Hh // s, Wh // s)
         y0, x0 = random.randint(0, max(0, Hl - LRs)), random.randint(0, max(0, Wl - LRs))
-        hflip = self.use_flip and random.random() < 0.5
-        vflip = self.use_rot and random.random() < 0.5
-        rot90 = self.use_rot and random.random() < 0.5
-        return y0, x0, int(hflip) | (int(vflip) << 1) | (int(rot90) << 2)
-
-    def _batch_u8(self, indices):
-        s, HRs = self.scale, self.hr_size
-        LRs, n = HRs // s, len(indices)
-        out = {'LR': torch.empty((n, 3, LRs, LRs), dtype=torch.float32, device=self.device),
-               'HR': torch.empty((n, 3, HRs, HRs), dtype=torch.float32, device=self.device)}
-        gather, lr_plans = [], []
-        for k, idx in enumerate(indices):
-            y0, x0, flags = self._draw(idx)
-            gather.append((self.img['HR'][idx], y0 * s, x0 * s, HRs, flags, out['HR'][k]))
-            lr_plans.append((self.img['LR'][idx] if self.img['LR'] is not None else self.img['HR'][idx], y0, x0, LRs, flags, out['LR'][k]))
-        if self.img['LR'] is not None:
-            out['_keep'] = [assemble_u8(self.device, lr_plans + gather)]
-        else:
-            out['_keep'] = [assemble_u8(self.device, gather, down=lr_plans)]
-        return out
+        return y0, x0, self._coins()
 
     def batch(self, indices):
-        if self.resident:
-            return self._batch_u8(indices)
         s, HRs = self.scale, self.hr_size
-        LRs = HRs // s
-        L = _lib.lib()
-        descs = {'LR': (_lib.CropDesc * len(indices))(), 'HR': (_lib.CropDesc * len(indices))()}
-        for k, idx in enumerate(indices):
-            lr, hr = self.img['LR'][idx], self.img['HR'][idx]
-            y0, x0, flags = self._draw(idx)
-            for key, t, yy, xx in (('LR', lr, y0, x0), ('HR', hr, y0 * s, x0 * s)):
-                d = descs[key][k]
-                d.src, d.C, d.H, d.W, d.vH, d.vW = t.data_ptr(), t.shape[0], t.shape[1], t.shape[2], t.shape[1], t.shape[2]
-                d.y0, d.x0, d.flags = yy, xx, flags
-        out = {'_keep': []}
-        for key, size in (('LR', LRs), ('HR', HRs)):
-            dd = torch.frombuffer(bytearray(bytes(descs[key])), dtype=torch.uint8).to(self.device)
-            dst = torch.empty((len(indices), 3, size, size), dtype=torch.float32, device=self.device)
-            _lib.check(L.dasr_gather_crops(dd.data_ptr(), len(indices), 3, size, dst.data_ptr(), _stream()), 'gather_crops')
-            out[key] = dst
-            out['_keep'].append(dd)
+        LRs, n = HRs // s, len(indices)
+        draws = [(idx,) + self._draw(idx) for idx in indices]
+        if not self.resident:
+            return self._batch_f32([('LR', 3, LRs, [(self.img['LR'][i], None, y0, x0, flags) for i, y0, x0, flags in draws]),
+                                    ('HR', 3, HRs, [(self.img['HR'][i], None, y0 * s, x0 * s, flags) for i, y0, x0, flags in draws])])
+        out = {'LR': torch.empty((n, 3, LRs, LRs), dtype=torch.float32, device=self.device),
+               'HR': torch.empty((n, 3, HRs, HRs), dtype=torch.float32, device=self.device)}
+        made = self.img['LR'] is None   # the LR crops come from the HR bytes: dasr_crops_down4_u8
+        gather = [(self.img['HR'][i], y0 * s, x0 * s, HRs, flags, out['HR'][k]) for k, (i, y0, x0, flags) in enumerate(draws)]
+        lr_plans = [(self.img['HR' if made else 'LR'][i], y0, x0, LRs, flags, out['LR'][k]) for k, (i, y0, x0, flags) in enumerate(draws)]
+        out['_keep'] = [assemble_u8(self.device, gather, down=lr_plans) if made else assemble_u8(self.device, lr_plans + gather)]
         return out
-
-    def __iter__(self):
-        m = len(self.img['HR'])
-        order = torch.randperm(m).tolist() if self.shuffle else list(range(m))
-        for b in range(len(self)):
-            idx = order[b * self.n:(b + 1) * self.n]
-            if idx:
-                yield self.batch(idx)
 
 
 # ---- evaluation / validation folders (`mode: "LRHR"` in the val / test phase, `mode: "LR"`) -----------------------------------------
@@ -479,14 +376,14 @@ class EvalFolderDataset:
     Per item the file is decoded by PIL on the host (RGB, uint8), its BYTES are uploaded, and csrc/imgio.hip does the rest: dasr_u8_to_planar gives the planar fp32
     image in [0, 1] (bit for bit load_image), cropped to a multiple of `scale` for HR (modcrop); without LR files the LR image is dasr_imresize_down of the cropped HR
     (MATLAB bicubic with antialiasing, the fp64 taps of bicubic_taps, one rounding to fp32: within one fp32 unit of imresize_matlab).  .npy files (CHW or 1CHW float
-    arrays, as load_image reads them) are uploaded as they are.  Nothing is kept across items but the tap tables per (length, scale) and the fp64 intermediate per shape."""
+    arrays, as load_image reads them) are uploaded as they are.  Nothing is kept across items but the fp64 intermediate per shape (the tap tables per length and scale are imgio.tap_table's)."""
 
     def __init__(self, ds_opt, scale=4, device=None):
         self.opt, self.scale = ds_opt, int(scale)
         self.mode = ds_opt.get('mode')
         self.paths_HR, self.paths_LR = eval_folder_pairs(ds_opt)
         self._device = device
-        self._taps, self._tmp = {}, {}
+        self._tmp = {}
 
     def __len__(self):
         return len(self.paths_HR if self.paths_HR is not None else self.paths_LR)
@@ -494,18 +391,13 @@ class EvalFolderDataset:
     @property
     def device(self):
         if not isinstance(self._device, torch.device):   # resolved on first use: listing and pairing (the constructor) need no GPU
-            ensure_runtime_ready()
-            self._device = torch.device('cuda', torch.cuda.current_device()) if self._device is None else torch.device(self._device)
+            self._device = device_of(self._device)
         return self._device
 
     @staticmethod
     def decode(path):
         """host part of reading one file: the uint8 [H, W, 3] RGB array PIL decodes (a .npy file: the CHW fp32 tensor load_image gives)"""
-        if path.endswith('.npy'):
-            return load_image(path)
-        from PIL import Image
-        with Image.open(path) as im:
-            return np.array(im.convert('RGB'), dtype=np.uint8)
+        return load_image(path) if path.endswith('.npy') else decode_u8(path)
 
     def to_device(self, a, crop_to=None, path='image'):
         """decoded image -> [1, 3, Hc, Wc] fp32 on the device; crop_to: the scale whose multiple the size is cut down to (modcrop), None: the whole image"""
@@ -523,15 +415,6 @@ class EvalFolderDataset:
     def _read(self, path, crop_to=None):
         return self.to_device(self.decode(path), crop_to, path)
 
-    def _tables(self, n_in):
-        """device tap tables (int32 index, fp64 weight) of one axis, uploaded once per (n_in, scale)"""
-        t = self._taps.get(n_in)
-        if t is None:
-            j, w = bicubic_taps(n_in, 1.0 / self.scale)
-            t = (j.to(torch.int32).contiguous().to(self.device), w.contiguous().to(self.device))
-            self._taps[n_in] = t
-        return t
-
     def downsample(self, img):
         """[1, C, H, W] (or [C, H, W]) fp32 device image with H and W multiples of scale -> [1, C, H / scale, W / scale]: dasr_imresize_down"""
         x = (img if img.dim() == 4 else img[None]).to(self.device, torch.float32).contiguous()
@@ -541,7 +424,7 @@ class EvalFolderDataset:
             raise ValueError('downsample takes one image, got a batch of %d' % n)
         if s not in (2, 3, 4) or H % s or W % s:
             raise NotImplementedError('LR images are made on the fly for scale 2, 3 or 4 and sizes that are multiples of it (got scale %d, %d x %d); provide LR files' % (s, H, W))
-        (jh, wh), (jw, ww) = self._tables(H), self._tables(W)
+        (jh, wh), (jw, ww) = tap_table(H, s, self.device), tap_table(W, s, self.device)
         tmp = self._tmp.get((c, H, W))
         if tmp is None:
             self._tmp = {(c, H, W): torch.empty((c, H // s, W), dtype=torch.float64, device=self.device)}   # one shape at a time: a folder of mixed sizes does not pile them up

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from .dsn_model import DSNModel
+from .imgio import decode_u8, u8_to_chw
 
 IMG_EXT = ('.png', '.jpg', '.jpeg', '.JPG', '.JPEG', '.PNG')
 
@@ -46,9 +47,7 @@ def build_parser():
 
 
 def _load(path):
-    from PIL import Image
-    a = np.asarray(Image.open(path).convert('RGB'), dtype=np.float32) / 255.0
-    return torch.from_numpy(a).permute(2, 0, 1).unsqueeze(0).contiguous()
+    return u8_to_chw(decode_u8(path)).unsqueeze(0).contiguous()
 
 
 def _save_png(t, path):

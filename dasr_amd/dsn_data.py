@@ -16,16 +16,19 @@ per-row loops: same weights, same result up to fp32 summation order (tests/test_
 bytes stay resident in device memory; per item the host only draws the random numbers (`plan_item`, the calls of the host datasets in their order, so equal
 seeds give equal batches) and a batch is one descriptor upload and three launches of csrc/imgio.hip (clean crops, source crops, the bicubic image), with no
 host synchronisation.  hr and real are bit-equal to the host path, bicubic is the fp64 evaluation rounded once (within one fp32 unit of it, and of the host's image within that
-plus the host's own fp32 error).
+plus the host's own fp32 error).  The decode, the resident store, the tap tables and the descriptor upload are imgio.py's, shared with data.py.
 """
 import collections
-import ctypes
 import math
 import os
 import random
 
 import numpy as np
 import torch
+
+from . import _lib
+from .engine import _stream
+from .imgio import decode_u8, image_size, load_resident, tap_table, u8_to_chw, upload
 
 IMG_EXTENSIONS = ('.png', '.jpg', '.jpeg', '.PNG', '.JPG', '.JPEG')
 DERESNET_DATASETS = ('aim2019', 'ntire2020', 'realsr', 'camerasr')   # codes/DSN/train.py:84-115: the branches whose loaders return (hr, bicubic, real) triples
@@ -45,6 +48,8 @@ def _cubic(x):
     return (1.5 * a3 - 2.5 * a2 + 1) * (a <= 1).to(x.dtype) + (-0.5 * a3 + 2.5 * a2 - 4 * a + 2) * ((a > 1) & (a <= 2)).to(x.dtype)
 
 
+# resize_matrix / imresize evaluate the weights in fp32, as the reference's function does: tests/test_dsn_data.py pins the host loader's bicubic image to the reference's
+# own vectors.  imgio.bicubic_taps is the same kernel in fp64 (the device tables); building this matrix from it would change bits of every host batch.  Keep the two apart.
 def resize_matrix(in_length, scale, antialiasing=True, dtype=torch.float32):
     """[out_length, in_length] matrix of the 1-D bicubic resampling of utils.py:46-98: output pixel k takes the kernel (stretched by 1 / scale when
     shrinking with antialiasing) centred on u = k / scale + 0.5 (1 - 1 / scale), weights normalised per output pixel, taps outside the image
@@ -82,10 +87,7 @@ def imresize(img, scale, antialiasing=True):
 
 def open_image(path):
     """file -> CHW fp32 RGB in [0, 1] (Image.open + to_tensor; grey / palette / alpha files are converted to RGB)"""
-    from PIL import Image
-    with Image.open(path) as im:
-        a = np.array(im.convert('RGB'), dtype=np.uint8)
-    return torch.from_numpy(a).permute(2, 0, 1).float().div_(255.0)
+    return u8_to_chw(decode_u8(path))
 
 
 def _list_images(dirs):
@@ -106,13 +108,27 @@ def random_crop(img, size):
     return img[:, y:y + size, x:x + size]
 
 
-def center_crop(img, size):
-    """T.CenterCrop(size) on a CHW tensor (torchvision rounds the offsets)"""
-    _, h, w = img.shape
+def _centre(h, w, size):
+    """(y, x) of the window T.CenterCrop(size) keeps of an h x w image (torchvision rounds the offsets): center_crop and DeviceValDeresnet"""
     if h < size or w < size:
         raise ValueError('image %dx%d is smaller than the crop size %d' % (h, w, size))
-    y, x = int(round((h - size) / 2.0)), int(round((w - size) / 2.0))
+    return int(round((h - size) / 2.0)), int(round((w - size) / 2.0))
+
+
+def center_crop(img, size):
+    """T.CenterCrop(size) on a CHW tensor"""
+    y, x = _centre(img.shape[1], img.shape[2], size)
     return img[:, y:y + size, x:x + size]
+
+
+def _plan_window(h, w, crop, flips, rotations):
+    """(y0, x0, flags) of one augmented crop: THE order of its draws, for the host loader (load_augmented_crop) and the device one (plan_item) -- randint y, randint x,
+    the vflip coin (flags bit 0), the hflip coin (bit 1), the choice of quarter-turns (bits 2-3); the coins only with `flips`, the choice only with `rotations`"""
+    y, x = random.randint(0, h - crop), random.randint(0, w - crop)
+    vflip = flips and random.random() < 0.5
+    hflip = flips and random.random() < 0.5
+    k = random.choice([0, 1, 2, 3]) if rotations else 0
+    return y, x, int(vflip) | (int(hflip) << 1) | (k << 2)
 
 
 def load_augmented_crop(path, crop_size, flips, rotations):
@@ -120,20 +136,17 @@ def load_augmented_crop(path, crop_size, flips, rotations):
     when `rotations` (TF.rotate of the square crop, counter-clockwise): data_loader.py:27-31,43-47 -- without converting the whole image to floats:
     the crop window is cut from the decoded 8-bit image first and the flips are applied to the crop (a uniformly random window of the flipped
     image = the flip of a uniformly random window)"""
-    from PIL import Image
-    with Image.open(path) as im:
-        w, h = im.size
-        if h < crop_size or w < crop_size:
-            raise ValueError('%s: image %dx%d is smaller than the crop size %d' % (path, h, w, crop_size))
-        y, x = random.randint(0, h - crop_size), random.randint(0, w - crop_size)
-        a = np.array(im.convert('RGB').crop((x, y, x + crop_size, y + crop_size)), dtype=np.uint8)
-    img = torch.from_numpy(a).permute(2, 0, 1).float().div_(255.0)
-    if flips and random.random() < 0.5:
+    h, w = image_size(path)
+    if h < crop_size or w < crop_size:
+        raise ValueError('%s: image %dx%d is smaller than the crop size %d' % (path, h, w, crop_size))
+    y, x, flags = _plan_window(h, w, crop_size, flips, rotations)
+    img = u8_to_chw(decode_u8(path, (x, y, x + crop_size, y + crop_size)))
+    if flags & 1:
         img = img.flip(1)
-    if flips and random.random() < 0.5:
+    if flags & 2:
         img = img.flip(2)
-    if rotations:
-        img = torch.rot90(img, random.choice([0, 1, 2, 3]), (1, 2))
+    if flags >> 2:
+        img = torch.rot90(img, flags >> 2, (1, 2))
     return img.contiguous()
 
 
@@ -242,111 +255,29 @@ def make_datasets(o, paths):
 
 
 # ---- --device_data: the same datasets on images resident in device memory -------------------------------------------------------------
-MAX_DECODE_THREADS = 16
-
 # one window of a resident image as dasr_gather_crops_u8 cuts it: `image` uint8 [H, W, 3]; the crop x crop window at (y0, x0), flipped vertically (flags bit 0),
 # then horizontally (bit 1), then turned by k = bits 2-3 quarter-turns (torch.rot90(., k, (1, 2))); of that the size x size window at (sub_y, sub_x)
 CropPlan = collections.namedtuple('CropPlan', 'image y0 x0 crop flags sub_y sub_x size')
 
 
-def _plan_window(h, w, crop, flips, rotations):
-    """(y0, x0, flags) of one augmented crop, drawn like load_augmented_crop draws them"""
-    y, x = random.randint(0, h - crop), random.randint(0, w - crop)
-    vflip = flips and random.random() < 0.5
-    hflip = flips and random.random() < 0.5
-    k = random.choice([0, 1, 2, 3]) if rotations else 0
-    return y, x, int(vflip) | (int(hflip) << 1) | (k << 2)
-
-
-def _image_size(path):
-    """(H, W) from the file header, without decoding"""
-    from PIL import Image
-    with Image.open(path) as im:
-        w, h = im.size
-    return h, w
-
-
-def _decode_u8(path):
-    from PIL import Image
-    with Image.open(path) as im:
-        return np.array(im.convert('RGB'), dtype=np.uint8)
-
-
-def _device_of(device):
-    """the device the images live on (None: the current GPU); 'cpu' touches no GPU"""
-    if device is not None and torch.device(device).type == 'cpu':
-        return torch.device('cpu')
-    from .engine import ensure_runtime_ready
-    ensure_runtime_ready()
-    dev = torch.device('cuda') if device is None else torch.device(device)
-    return dev if dev.index is not None else torch.device('cuda', torch.cuda.current_device())
-
-
-def load_resident(file_lists, device=None, threads=6, max_bytes=None, min_size=0, remedy='train with the host loader (without --device_data)'):
-    """the files of every list decoded once (PIL, RGB, uint8 [H, W, 3]) on a pool of at most 16 threads and uploaded to `device`: (the device, lists of uint8 tensors).
-    The sizes are read from the file headers and summed BEFORE anything is decoded or the device is touched: an image with a side under `min_size` is a
-    ValueError naming the file, a total of H W 3 bytes above `max_bytes` (default: half of the device memory free right now) a MemoryError.  Nothing spills
-    to the host.  (The default cap is taken per call: a validation set loaded after its train set is held to half of what the train set left free.)
-    device 'cpu' keeps the bytes in host memory: enough for plan_item, not for assembling batches.  `remedy`: what the MemoryError tells the caller to do instead."""
-    from concurrent.futures import ThreadPoolExecutor
-    total = 0
-    for files in file_lists:
-        for path in files:
-            h, w = _image_size(path)
-            if h < min_size or w < min_size:
-                raise ValueError('%s: image %dx%d is smaller than the crop size %d' % (path, h, w, min_size))
-            total += h * w * 3
-
-    def refuse(cap):
-        raise MemoryError('the decoded images take %d bytes, above the cap of %d bytes for images resident in device memory: %s or raise max_bytes' % (total, cap, remedy))
-    if max_bytes is not None and total > max_bytes:
-        refuse(max_bytes)
-    dev = _device_of(device)
-    if max_bytes is None and dev.type == 'cuda' and total > torch.cuda.mem_get_info(dev)[0] // 2:
-        refuse(torch.cuda.mem_get_info(dev)[0] // 2)
-    threads = max(1, min(MAX_DECODE_THREADS, int(threads)))
-    out = []
-    with ThreadPoolExecutor(max_workers=threads) as pool:
-        for files in file_lists:
-            imgs = []
-            for k in range(0, len(files), 4 * threads):   # (decoded arrays wait in host memory one chunk at a time)
-                imgs += [torch.from_numpy(a).to(dev) for a in pool.map(_decode_u8, files[k:k + 4 * threads])]
-            out.append(imgs)
-    return dev, out
-
-
-def _tap_table(c, s, device):
-    """device tap table of dasr_crops_bicubic_down for crops of side c: (int32 index, fp64 weight), both [c / s, 4 s + 2]"""
-    from .data import bicubic_taps
-    j, w = bicubic_taps(c, 1.0 / s)
-    return j.to(torch.int32).contiguous().to(device), w.contiguous().to(device)
-
-
 def _gather_u8(plan_groups, device):
-    """one output tensor [n, 3, size, size] per group of CropPlans (equal `size` inside a group): ALL descriptors in one host-to-device copy from pinned
-    memory, one dasr_gather_crops_u8 launch per group, no host synchronisation"""
-    from . import _lib
-    from .engine import _stream
-    if device.type != 'cuda':
-        raise _lib.DasrHipError('batches are assembled by HIP kernels on images resident in device memory; this dataset was built on %s' % device)
-    plans = [p for g in plan_groups for p in g]
-    descs = (_lib.CropU8Desc * len(plans))()
-    for d, p in zip(descs, plans):
-        H, W = p.image.shape[:2]
-        if not (0 <= p.y0 and p.y0 + p.crop <= H and 0 <= p.x0 and p.x0 + p.crop <= W and 0 <= p.sub_y and p.sub_y + p.size <= p.crop
-                and 0 <= p.sub_x and p.sub_x + p.size <= p.crop and p.image.device == device and p.image.dtype == torch.uint8 and p.image.is_contiguous()):
-            raise ValueError('crop descriptor outside its image: %r of %d x %d' % (p[1:], H, W))
-        d.src, d.H, d.W, d.y0, d.x0, d.crop, d.flags, d.sub_y, d.sub_x = p.image.data_ptr(), H, W, p.y0, p.x0, p.crop, p.flags, p.sub_y, p.sub_x
-    staging = torch.empty(ctypes.sizeof(descs), dtype=torch.uint8, pin_memory=True)   # (torch's pinned-memory cache hands a block out again only after the copy below is done)
-    ctypes.memmove(staging.data_ptr(), descs, ctypes.sizeof(descs))
-    dd = staging.to(device, non_blocking=True)
-    L, out, k = _lib.lib(), [], 0
+    """one output tensor [n, 3, size, size] per group of CropPlans (equal `size` inside a group): ALL descriptors in one imgio.upload, one dasr_gather_crops_u8
+    launch per group, no host synchronisation"""
+    arrays = []
     for g in plan_groups:
+        arrays.append((_lib.CropU8Desc * len(g))())
+        for d, p in zip(arrays[-1], g):
+            H, W = p.image.shape[:2]
+            if not (0 <= p.y0 and p.y0 + p.crop <= H and 0 <= p.x0 and p.x0 + p.crop <= W and 0 <= p.sub_y and p.sub_y + p.size <= p.crop
+                    and 0 <= p.sub_x and p.sub_x + p.size <= p.crop and p.image.device == device and p.image.dtype == torch.uint8 and p.image.is_contiguous()):
+                raise ValueError('crop descriptor outside its image: %r of %d x %d' % (p[1:], H, W))
+            d.src, d.H, d.W, d.y0, d.x0, d.crop, d.flags, d.sub_y, d.sub_x = p.image.data_ptr(), H, W, p.y0, p.x0, p.crop, p.flags, p.sub_y, p.sub_x
+    dd, offsets = upload(device, *arrays)
+    L, out = _lib.lib(), []
+    for g, off in zip(plan_groups, offsets):
         size = g[0].size
-        dst = torch.empty((len(g), 3, size, size), dtype=torch.float32, device=device)
-        _lib.check(L.dasr_gather_crops_u8(dd.data_ptr() + k * ctypes.sizeof(_lib.CropU8Desc), len(g), size, dst.data_ptr(), _stream()), 'dasr_gather_crops_u8')
-        out.append(dst)
-        k += len(g)
+        out.append(torch.empty((len(g), 3, size, size), dtype=torch.float32, device=device))
+        _lib.check(L.dasr_gather_crops_u8(dd.data_ptr() + off, len(g), size, out[-1].data_ptr(), _stream()), 'dasr_gather_crops_u8')
     return out
 
 
@@ -358,19 +289,15 @@ def _check_bicubic_side(c, upscale_factor, what):
 
 
 class _BicubicDown:
-    """dasr_crops_bicubic_down with its tap tables, one per crop side, built and uploaded on first use"""
+    """dasr_crops_bicubic_down with the tap tables (imgio.tap_table) of the crop sides it has seen"""
 
     def __init__(self, upscale_factor, device):
         self.s, self.device, self._tables = int(upscale_factor), device, {}
 
     def __call__(self, hr):
-        from . import _lib
-        from .engine import _stream
         n, _, c, _ = hr.shape
         _check_bicubic_side(c, self.s, 'crops of side %d' % c)
-        if c not in self._tables:
-            self._tables[c] = _tap_table(c, self.s, self.device)
-        j, w = self._tables[c]
+        j, w = self._tables[c] = tap_table(c, self.s, self.device)
         out = torch.empty((n, 3, c // self.s, c // self.s), dtype=torch.float32, device=self.device)
         _lib.check(_lib.lib().dasr_crops_bicubic_down(hr.data_ptr(), n, c, self.s, j.data_ptr(), w.data_ptr(), out.data_ptr(), _stream()), 'dasr_crops_bicubic_down')
         return out
@@ -421,9 +348,9 @@ class DeviceValDeresnet:
         self.lr_files = sorted(_list_images(lr_dir))
         self.upscale_factor, self.crop_size = int(upscale_factor), crop_size_val
         for hr_path, lr_path in zip(self.hr_files, self.lr_files):   # every item's sizes, from the file headers: refused here, not at the first validation pass
-            cs = self._crop_side(*_image_size(hr_path))
+            cs = self._crop_side(*image_size(hr_path))
             _check_bicubic_side(cs, self.upscale_factor, hr_path)
-            h, w = _image_size(lr_path)
+            h, w = image_size(lr_path)
             if h < cs // self.upscale_factor or w < cs // self.upscale_factor:
                 raise ValueError('%s: image %dx%d is smaller than the crop size %d' % (lr_path, h, w, cs // self.upscale_factor))
         self.device, (self.hr, self.lr) = load_resident([self.hr_files, self.lr_files], device, threads, max_bytes)
@@ -438,10 +365,7 @@ class DeviceValDeresnet:
 
     def __getitem__(self, index):
         def centre(img, size):   # center_crop
-            h, w = img.shape[:2]
-            if h < size or w < size:
-                raise ValueError('image %dx%d is smaller than the crop size %d' % (h, w, size))
-            return CropPlan(img, int(round((h - size) / 2.0)), int(round((w - size) / 2.0)), size, 0, 0, 0, size)
+            return CropPlan(img, *_centre(img.shape[0], img.shape[1], size), size, 0, 0, 0, size)
         hr, lr = self.hr[index], self.lr[index]
         cs = self._crop_side(hr.shape[0], hr.shape[1])
         small = cs // self.upscale_factor
@@ -495,5 +419,4 @@ def display_transform(img, size=400):
     im = im.resize((nw, nh), Image.BILINEAR)
     x0, y0 = int(round((nw - size) / 2.0)), int(round((nh - size) / 2.0))
     im = im.crop((x0, y0, x0 + size, y0 + size))
-    a = np.array(im.convert('RGB'), dtype=np.uint8)
-    return torch.from_numpy(a).permute(2, 0, 1).float().div_(255.0)
+    return u8_to_chw(np.array(im.convert('RGB'), dtype=np.uint8))

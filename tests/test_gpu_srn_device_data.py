@@ -291,3 +291,35 @@ def test_training_driver_logs_the_same_losses_with_and_without_resident_u8(tmp_p
         logs.append([l.split('> ', 1)[1].strip() for l in text.splitlines() if '<epoch:' in l and 'iter:' in l])
     assert len(logs[0]) == 3 and 'l_pix' in logs[0][0], logs[0]
     assert logs[0] == logs[1]
+
+
+def test_fp32_store_batches_do_not_depend_on_when_the_host_waits():
+    """the fp32 store's descriptors cross in one asynchronous copy from a pinned staging block (imgio.upload): eight batches enqueued back to back, nothing kept but
+    the batch dicts and one synchronisation at the end, against the same eight with a synchronisation after each.  A staging block handed out again before its copy
+    has run would show as a mismatch (not as a fault: every kernel clamps its source coordinates).  Every descriptor kind: 3-channel crops, the HR window at 4 x the
+    LR origin, the domain-distance maps through the bilinear virtual resize (5 x 6 seen as 7 x 9), all flags."""
+    dev = _gpu()
+    from dasr_amd.data import DeviceUnpairedDataset
+    g = torch.Generator().manual_seed(41)
+    images = {'fake_LR': [torch.rand(3, 7, 9, generator=g) for _ in range(4)], 'real_LR': [torch.rand(3, 6, 8, generator=g) for _ in range(3)],
+              'HR': [torch.rand(3, 28, 36, generator=g) for _ in range(4)], 'fake_w': [torch.rand(1, 5, 6, generator=g) for _ in range(4)]}
+    ds = DeviceUnpairedDataset({'batch_size': 2, 'HR_size': 16, 'use_flip': True, 'use_rot': True, 'use_shuffle': True}, 4, images=images, device=dev)
+    keys = ('LR_fake', 'LR_real', 'HR', 'HR_unpair', 'fake_w')
+
+    def eight(wait):
+        _seed(23)
+        out = []
+        for _ in range(4):
+            for b in ds:
+                out.append(b)
+                if wait:
+                    torch.cuda.synchronize()
+        torch.cuda.synchronize()
+        return out
+    free, waited = eight(False), eight(True)
+    assert len(free) == len(waited) == 8 and len({int(b['_keep'][0].data_ptr()) for b in free}) == 8
+    assert [tuple(free[0][k].shape) for k in keys] == [(2, 3, 4, 4), (2, 3, 4, 4), (2, 3, 16, 16), (2, 3, 16, 16), (2, 1, 4, 4)]
+    for i, (a, b) in enumerate(zip(free, waited)):
+        for k in keys:
+            assert torch.equal(a[k], b[k]), (i, k)
+    assert not all(torch.equal(free[0][k], free[1][k]) for k in keys)           # (the batches differ from each other: a stale block would be seen)
