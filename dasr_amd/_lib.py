@@ -118,6 +118,7 @@ OP_RDB_CHAIN = 49
 OP_BNORM_JVP, OP_BNORM_SECOND = 50, 51   # --wgan with BatchNorm discriminators (round 6)
 OP_PRELU_FINAL = 52
 OP_RESBLOCK = 53   # fused residual block of SRResNet (ABI 21)
+OP_LPIPS_S2D_ANY = 54   # LPIPS input stage at any image size (the folder evaluator)
 
 # Argument slots of every op kind the plan builders record (all but OP_CONV), by the parameter name of the entry point that dasr_run_ops
 # (csrc/misc.hip) passes the slot to.  Slot codes: i0..i6 int32, f0..f3 float, l0..l3 int64, p0..p3 pointer, t0..t4 dasr_tensor;
@@ -189,6 +190,7 @@ OP_ARGS = {
     OP_MAXPOOL3_BWD: dict(x='t0', gy='t1', N='i0', C='i1', H='i2', W='i3', gx='t2', relu_mask='i4', accumulate='i5'),
     OP_LPIPS_HEAD: dict(f='t0', pair_off='l0', N='i0', C='i1', H='i2', W='i3', lin='p0', eps='f0', coef='f1', gcoef='f2', loss_acc='p1', g0='t1',
                         relu_mask='i4'),
+    OP_LPIPS_S2D_ANY: dict(x='t0', N='i0', H='i1', W='i2', scale4='f*', shift4='l*', y='t1'),
 }
 
 
@@ -282,6 +284,7 @@ _SIGS = {
     'dasr_bnorm_running': [c_vp, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp],
     'dasr_ragan': [Tensor, Tensor, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, Tensor, Tensor, c_vp],
     'dasr_lpips_s2d': [Tensor, c_i32, c_i32, c_i32, c_vp, c_vp, Tensor, c_i32, c_vp],
+    'dasr_lpips_s2d_any': [Tensor, c_i32, c_i32, c_i32, c_vp, c_vp, Tensor, c_vp],
     'dasr_maxpool3s2': [Tensor, c_i32, c_i32, c_i32, c_i32, Tensor, c_vp],
     'dasr_maxpool3s2_bwd': [Tensor, Tensor, c_i32, c_i32, c_i32, c_i32, Tensor, c_i32, c_i32, c_vp],
     'dasr_lpips_head': [Tensor, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, c_f32, c_f32, c_vp, Tensor, c_i32, c_vp],
@@ -289,6 +292,8 @@ _SIGS = {
     'dasr_tensor2img_u8': [c_vp, c_i32, c_i32, c_i32, c_i32, C.c_double, C.c_double, c_vp, c_vp, c_vp, c_vp],
     'dasr_img_sse': [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp],
     'dasr_img_ssim': [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp],
+    'dasr_img_ssim_box': [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp],
+    'dasr_img_channel_sums': [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp],
     'dasr_u8_to_planar': [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp],
     'dasr_imresize_down': [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     'dasr_gather_crops_u8': [c_vp, c_i32, c_i32, c_vp, c_vp],

@@ -1,7 +1,8 @@
 // HBM-bound kernels of the LPIPS(alex) perceptual loss (PerceptualLossLPIPS, codes/SRN/models/modules/loss.py:66-72 ->
 // PNetLin.forward, codes/PerceptualSimilarity/models/networks_basic.py:64-92, backbone pretrained_networks.py:57-95), gfx950:
 //  * input scaling + 4x4 space-to-depth: AlexNet's 11x11 / stride 4 / pad 2 first conv on 3 channels becomes a 3x3 / stride 1 / pad 0
-//    conv on 48 channels of the (H+4)/4 grid, which runs on the MFMA conv kernel like every other layer (and its adjoint)
+//    conv on 48 channels of the (H+4)/4 grid, which runs on the MFMA conv kernel like every other layer (and its adjoint); the forward stage also for
+//    sizes that are no multiple of 4 (dasr_lpips_s2d_any, the folder evaluator), on the grid of (H-7)/4 + 3 block rows
 //  * MaxPool2d(3, 2) forward / backward (first maximum in scan order wins, like ATen; the ReLU' of the layer feeding the pool is applied)
 //  * the per-layer head: channel-unit-normalise both feature stacks, squared difference, non-negative 1x1 "lin" weights, spatial mean;
 //    the loss and its gradient w.r.t. the first stack in one launch
@@ -39,8 +40,8 @@ __device__ __forceinline__ void dihedral_dst(int u, int v, int H, int W, int xf,
     j = (xf & 1) ? u : v;
 }
 
-__global__ void lpips_s2d_kernel(dasr_tensor x, int N, int H, int W, f32x4 sc, f32x4 sh, dasr_tensor y, int mode, int xf) {
-    const int Hs = (H + 4) >> 2, Ws = (W + 4) >> 2;
+// Hs x Ws: the block grid, (H+4)/4 x (W+4)/4 for dasr_lpips_s2d; dasr_lpips_s2d_any (mode 0, xf 0) passes the grid of lpips_s2d_grid for any size
+__global__ void lpips_s2d_kernel(dasr_tensor x, int N, int H, int W, int Hs, int Ws, f32x4 sc, f32x4 sh, dasr_tensor y, int mode, int xf) {
     if (mode == 0) {
         const long long total = (long long)N * 3 * Hs * Ws * 4;   // one thread: one colour, one s2d pixel, one row `by` of its 4x4 block
         const long long gi = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -232,7 +233,22 @@ extern "C" int dasr_lpips_s2d(dasr_tensor x, int32_t N, int32_t H, int32_t W, co
     const int Hs = (H + 4) >> 2, Ws = (W + 4) >> 2;
     const long long total = mode == 0 ? (long long)N * 3 * Hs * Ws * 4 : (long long)N * H * W;
     const f32x4 sc = {scale4[0], scale4[1], scale4[2], 0.f}, sh = {shift4[0], shift4[1], shift4[2], 0.f};
-    DASR_LAUNCH(lpips_s2d_kernel, dim3(nblk(total)), dim3(256), 0, as_stream(stream), x, N, H, W, sc, sh, y, mode, xf);
+    DASR_LAUNCH(lpips_s2d_kernel, dim3(nblk(total)), dim3(256), 0, as_stream(stream), x, N, H, W, Hs, Ws, sc, sh, y, mode, xf);
+    return (int)hipGetLastError();
+}
+
+// block rows (columns) of the space-to-depth grid of an axis of n pixels: the 11 / stride 4 / pad 2 conv has (n - 7) / 4 + 1 outputs, each the 3 x 3 conv
+// of 3 consecutive blocks; n / 4 + 1 at multiples of 4
+static inline int lpips_s2d_grid(int n) { return (n - 7) / 4 + 3; }
+
+extern "C" int dasr_lpips_s2d_any(dasr_tensor x, int32_t N, int32_t H, int32_t W, const float* scale4, const float* shift4, dasr_tensor y, void* stream) {
+    if (!x.p || !y.p || !scale4 || !shift4) return DASR_EINVAL;   // scale4 / shift4 are read here, on the host
+    if (N <= 0 || H < 31 || W < 31) return DASR_EINVAL;
+    const int Hs = lpips_s2d_grid(H), Ws = lpips_s2d_grid(W);
+    const long long total = (long long)N * 3 * Hs * Ws * 4;
+    if ((total + 255) / 256 > 0x7fffffffLL) return DASR_EINVAL;
+    const f32x4 sc = {scale4[0], scale4[1], scale4[2], 0.f}, sh = {shift4[0], shift4[1], shift4[2], 0.f};
+    DASR_LAUNCH(lpips_s2d_kernel, dim3(nblk(total)), dim3(256), 0, as_stream(stream), x, N, H, W, Hs, Ws, sc, sh, y, 0, 0);
     return (int)hipGetLastError();
 }
 

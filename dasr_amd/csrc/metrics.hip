@@ -3,6 +3,9 @@
 //  * tensor2img: fp32 NCHW image -> uint8, HWC BGR (what save_img takes) and / or planar CHW (what the metric kernels read); NaN -> 0, counted
 //  * squared error over the cropped region: the integer sum over all channels (RGB PSNR) and the fp64 sum on the Y channel (PSNR_Y)
 //  * SSIM (11 x 11 Gaussian window, sigma 1.5, 'valid' region of the cropped images), fp64, on the uint8 planes or on the Y channel
+// and of the folder evaluator (reference: codes/DSN/evaluate.py:44-46; host side: dasr_amd/metrics.py pair_metrics_u8):
+//  * SSIM in scikit-image's form (7 x 7 uniform window, sample covariance) from exact integer window sums, one fp64 evaluation per window
+//  * the exact integer sum of the bytes of every channel (the mean colour of PSNR_col)
 // Every sum over the grid is two launches: one partial per workgroup (plain stores into the caller's workspace), then one workgroup per image that adds
 // the partials in index order.  The kernel boundary orders the two, so there is no in-launch hand-off and no floating-point atomic: the same inputs give
 // the same bits run to run.  The work is small (two 8 MB images, under 3 GFLOP of fp64 at 1356 x 2040), so the kernels are plain: one LDS-staged tile
@@ -218,6 +221,116 @@ __global__ __launch_bounds__(256) void img_ssim_kernel(const uint8_t* __restrict
     if (threadIdx.x == 0) part[((size_t)n * gridDim.y + ch) * gridDim.x + tile] = t;
 }
 
+constexpr int BOX_K = 7;            // window of the box SSIM
+constexpr int BOX_TH = 32;          // output tile: 32 rows x 64 columns, eight outputs (one column, eight rows) per thread
+constexpr int BOX_TW = 64;
+constexpr int BOX_IH = BOX_TH + BOX_K - 1;   // 38 input rows: the tile and its 6-pixel apron
+constexpr int BOX_IW = BOX_TW + BOX_K - 1;   // 70 input columns
+constexpr int BOX_PITCH = 72;                // bytes per staged row
+
+// SSIM of one 7 x 7 window from its five integer sums (skimage.measure.compare_ssim: uniform filter, use_sample_covariance, data_range 255).
+// The integers are exact and fit 32 bits: Sx <= 49 * 255 = 12 495, Sxx <= 49 * 255^2 = 3 186 225, and the largest intermediate, 49 * Sxx or Sx^2, is
+// 156 125 025 < 2^31.  The formula is evaluated once, in fp64, from them: the value does not depend on how the image was cut into tiles.
+// With u = S / n and v = (n Sxx - Sx^2) / (n (n - 1)), S = (2 ux uy + C1)(2 vxy + C2) / ((ux^2 + uy^2 + C1)(vx + vy + C2)) is evaluated with the first factor of
+// numerator and denominator multiplied by n^2 and the second by n (n - 1): the integer parts enter exactly and ONE division is left (six otherwise).
+__device__ __forceinline__ double box_ssim_of(int sx, int sy, int sxx, int syy, int sxy) {
+    const double K1 = ((0.01 * 255) * (0.01 * 255)) * (49.0 * 49.0), K2 = ((0.03 * 255) * (0.03 * 255)) * (49.0 * 48.0);
+    const double dx = (double)(49 * sxx - sx * sx), dy = (double)(49 * syy - sy * sy), dxy = (double)(49 * sxy - sx * sy);
+    const double pxx = (double)(sx * sx), pyy = (double)(sy * sy), pxy = (double)(sx * sy);
+    return ((2.0 * pxy + K1) * (2.0 * dxy + K2)) / ((pxx + pyy + K1) * (dx + dy + K2));
+}
+
+// Box SSIM map of one 32 x 64 tile of the window positions of one channel, summed.  grid (tiles_x * tiles_y, C, N).  The 38 x 70 bytes under the tile (with the
+// 6-pixel apron) of both images are staged in LDS; row sums over 7 columns of a, b, a^2, b^2, a b are formed there as integers (a and b share a word: both are
+// under 2^16, also after the column sum), then every thread walks 8 rows of one column with a running column sum (integers: adding a row and dropping one is exact).
+// part[(n * C + ch) * tiles + tile] = sum of the map over the tile's window positions inside the cropped image.
+__global__ __launch_bounds__(256) void img_ssim_box_kernel(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, int C, int H, int W, int crop, int tiles_x,
+                                                           double* __restrict__ part) {
+    __shared__ uint8_t sa[BOX_IH][BOX_PITCH];
+    __shared__ uint8_t sb[BOX_IH][BOX_PITCH];
+    __shared__ int hs[4][BOX_IH][BOX_TW];   // row sums: a | b << 16, a^2, b^2, a b
+    __shared__ double red_d[4];
+    const int tile = blockIdx.x, ch = blockIdx.y, n = blockIdx.z;
+    const int h = H - 2 * crop, w = W - 2 * crop;          // cropped image
+    const int hv = h - (BOX_K - 1), wv = w - (BOX_K - 1);   // window positions
+    const int oy = (tile / tiles_x) * BOX_TH, ox = (tile % tiles_x) * BOX_TW;
+    const size_t HW = (size_t)H * W;
+    const uint8_t* pa = a + ((size_t)n * C + ch) * HW;
+    const uint8_t* pb = b + ((size_t)n * C + ch) * HW;
+    for (int i = threadIdx.x; i < BOX_IH * BOX_IW; i += 256) {
+        const int r = i / BOX_IW, c = i - r * BOX_IW;
+        const int iy = oy + r, ix = ox + c;
+        uint8_t va = 0, vb = 0;   // outside the cropped image: feeds only window positions outside it, which are not summed
+        if (iy < h && ix < w) {
+            const size_t p = (size_t)(iy + crop) * W + (ix + crop);
+            va = pa[p];
+            vb = pb[p];
+        }
+        sa[r][c] = va;
+        sb[r][c] = vb;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < BOX_IH * BOX_TW; i += 256) {
+        const int r = i / BOX_TW, c = i - r * BOX_TW;
+        int m0 = 0, m1 = 0, m2 = 0, m3 = 0;
+#pragma unroll
+        for (int k = 0; k < BOX_K; ++k) {
+            const int va = sa[r][c + k], vb = sb[r][c + k];
+            m0 += va | (vb << 16);
+            m1 += va * va;
+            m2 += vb * vb;
+            m3 += va * vb;
+        }
+        hs[0][r][c] = m0;
+        hs[1][r][c] = m1;
+        hs[2][r][c] = m2;
+        hs[3][r][c] = m3;
+    }
+    __syncthreads();
+    const int c = threadIdx.x & (BOX_TW - 1), r0 = (threadIdx.x >> 6) * 8;   // a wave: 64 columns of the same 8 rows
+    int m0 = 0, m1 = 0, m2 = 0, m3 = 0;
+#pragma unroll
+    for (int k = 0; k < BOX_K - 1; ++k) {
+        m0 += hs[0][r0 + k][c];
+        m1 += hs[1][r0 + k][c];
+        m2 += hs[2][r0 + k][c];
+        m3 += hs[3][r0 + k][c];
+    }
+    double s = 0.0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {   // window rows r0 + j .. r0 + j + 6 (at most row 37)
+        m0 += hs[0][r0 + j + 6][c];
+        m1 += hs[1][r0 + j + 6][c];
+        m2 += hs[2][r0 + j + 6][c];
+        m3 += hs[3][r0 + j + 6][c];
+        if (oy + r0 + j < hv && ox + c < wv) s += box_ssim_of(m0 & 0xffff, m0 >> 16, m1, m2, m3);
+        m0 -= hs[0][r0 + j][c];
+        m1 -= hs[1][r0 + j][c];
+        m2 -= hs[2][r0 + j][c];
+        m3 -= hs[3][r0 + j][c];
+    }
+    const double t = block_sum_f64(s, red_d);
+    if (threadIdx.x == 0) part[((size_t)n * gridDim.y + ch) * gridDim.x + tile] = t;
+}
+
+// Sum of the bytes of one plane (image n, channel c: blockIdx.x = n * C + c) over rows [crop, H - crop) x columns [crop, W - crop): workgroup g = blockIdx.y of
+// the plane takes the cropped rows g, g + G, ...;  part[plane * G + g]
+__global__ void img_channel_sums_kernel(const uint8_t* __restrict__ a, int H, int W, int crop, long long* __restrict__ part) {
+    __shared__ long long red_i[4];
+    const int G = gridDim.y;
+    const int h = H - 2 * crop, w = W - 2 * crop;
+    const uint8_t* p = a + (size_t)blockIdx.x * H * W;
+    long long s = 0;
+    for (int r = blockIdx.y; r < h; r += G) {
+        const size_t row = (size_t)(r + crop) * W + crop;
+        int rs = 0;   // a thread's share of a row: at most 128 bytes
+        for (int xx = threadIdx.x; xx < w; xx += 256) rs += p[row + xx];
+        s += rs;
+    }
+    const long long t = block_sum_i64(s, red_i);
+    if (threadIdx.x == 0) part[(size_t)blockIdx.x * G + blockIdx.y] = t;
+}
+
 inline bool geometry_ok(int N, int C, int H, int W, int crop) {
     // (N rides in a grid's y / z dimension: <= 65535)
     return N > 0 && N <= 65535 && (C == 1 || C == 3) && crop >= 0 && H > 0 && W > 0 && H <= 32768 && W <= 32768 && 2 * (long long)crop < H && 2 * (long long)crop < W;
@@ -232,12 +345,22 @@ inline long long ssim_tiles(int H, int W, int crop, int* tiles_x) {
     return (long long)*tiles_x * ((hv + SSIM_TH - 1) / SSIM_TH);
 }
 
-// bytes of workspace dasr_img_sse / dasr_img_ssim write their per-workgroup partials into (the larger of the two)
+inline long long box_tiles(int H, int W, int crop, int* tiles_x) {
+    const int hv = H - 2 * crop - (BOX_K - 1), wv = W - 2 * crop - (BOX_K - 1);
+    if (hv < 1 || wv < 1) return 0;
+    *tiles_x = (wv + BOX_TW - 1) / BOX_TW;
+    return (long long)*tiles_x * ((hv + BOX_TH - 1) / BOX_TH);
+}
+
+// bytes of workspace dasr_img_sse / dasr_img_ssim / dasr_img_ssim_box / dasr_img_channel_sums write their per-workgroup partials into (the largest of the four)
 inline long long ws_bytes(int N, int C, int H, int W, int crop) {
     int tx = 0;
     const long long sse = (long long)N * sse_blocks(H, crop) * 16;
     const long long ssim = (long long)N * C * ssim_tiles(H, W, crop, &tx) * 8;
-    return sse > ssim ? sse : ssim;
+    const long long box = (long long)N * C * box_tiles(H, W, crop, &tx) * 8;
+    const long long chan = (long long)N * C * sse_blocks(H, crop) * 8;
+    const long long m1 = sse > ssim ? sse : ssim, m2 = box > chan ? box : chan;
+    return m1 > m2 ? m1 : m2;
 }
 
 }  // namespace
@@ -298,5 +421,28 @@ extern "C" int dasr_img_ssim(const uint8_t* a, const uint8_t* b, int32_t N, int3
     }
     DASR_LAUNCH(img_reduce_kernel, dim3(N), dim3(256), 0, as_stream(stream), (const long long*)nullptr, (const double*)ws, (int)(tiles * ch), (long long*)nullptr, ssim,
                 count);
+    return (int)hipGetLastError();
+}
+
+extern "C" int dasr_img_ssim_box(const uint8_t* a, const uint8_t* b, int32_t N, int32_t C, int32_t H, int32_t W, int32_t crop, double* ssim, void* ws, int64_t ws_size,
+                                 void* stream) {
+    if (!a || !b || !ssim || !ws || !geometry_ok(N, C, H, W, crop)) return DASR_EINVAL;
+    int tiles_x = 0;
+    const long long tiles = box_tiles(H, W, crop, &tiles_x);
+    if (tiles < 1) return DASR_EINVAL;   // a cropped side under 7 pixels: no window fits
+    if (tiles * C > 0x7fffffffLL || ws_size < (long long)N * C * tiles * 8) return DASR_EINVAL;
+    const double count = (double)C * (double)(H - 2 * crop - (BOX_K - 1)) * (double)(W - 2 * crop - (BOX_K - 1));
+    DASR_LAUNCH(img_ssim_box_kernel, dim3((unsigned)tiles, C, N), dim3(256), 0, as_stream(stream), a, b, C, H, W, crop, tiles_x, (double*)ws);
+    DASR_LAUNCH(img_reduce_kernel, dim3(N), dim3(256), 0, as_stream(stream), (const long long*)nullptr, (const double*)ws, (int)(tiles * C), (long long*)nullptr, ssim,
+                count);
+    return (int)hipGetLastError();
+}
+
+extern "C" int dasr_img_channel_sums(const uint8_t* a, int32_t N, int32_t C, int32_t H, int32_t W, int32_t crop, int64_t* sums, void* ws, int64_t ws_size, void* stream) {
+    if (!a || !sums || !ws || !geometry_ok(N, C, H, W, crop)) return DASR_EINVAL;
+    const int G = sse_blocks(H, crop);
+    if (ws_size < (long long)N * C * G * 8) return DASR_EINVAL;
+    DASR_LAUNCH(img_channel_sums_kernel, dim3(N * C, G), dim3(256), 0, as_stream(stream), a, H, W, crop, (long long*)ws);
+    DASR_LAUNCH(img_reduce_kernel, dim3(N * C), dim3(256), 0, as_stream(stream), (const long long*)ws, (const double*)nullptr, G, (long long*)sums, (double*)nullptr, 1.0);
     return (int)hipGetLastError();
 }

@@ -875,6 +875,7 @@ extern "C" int dasr_run_ops(const dasr_op* ops, int32_t n, void* stream0) {
                 rc = dasr_lpips_head(o.t[0], o.l[0], o.i[0], o.i[1], o.i[2], o.i[3], (const float*)o.p[0], o.f[0], o.f[1], o.f[2], (float*)o.p[1], o.t[1],
                                      o.i[4], stream);
                 break;
+            case DASR_OP_LPIPS_S2D_ANY: rc = dasr_lpips_s2d_any(o.t[0], o.i[0], o.i[1], o.i[2], &o.f[0], (const float*)o.l, o.t[1], stream); break;
             default: rc = DASR_EINVAL;
         }
         if (rc != 0) {

@@ -67,6 +67,14 @@ def conv1_to_s2d(w):
     return wp.view(cout, 3, 3, 4, 3, 4).permute(0, 1, 3, 5, 2, 4).reshape(cout, 48, 3, 3).contiguous()
 
 
+def s2d_grid(n):
+    """block rows (columns) of the space-to-depth grid of an axis of n pixels: the 11 / stride 4 / pad 2 conv has (n - 7) // 4 + 1 outputs, each the 3 x 3
+    conv of three consecutive blocks; n // 4 + 1 at multiples of 4 (csrc/lpips.hip, dasr_lpips_s2d_any)"""
+    return (n - 7) // 4 + 3
+
+
+MIN_SIDE = 31   # below it the second MaxPool2d(3, 2) of the backbone has no output
+
 logger = logging.getLogger('base')
 
 
@@ -111,7 +119,7 @@ def lpips_metric(net, fake, real):
 
 
 class LPIPSAlexHIP:
-    """Frozen LPIPS network.  plan(N, n, H, W): N = 2n images [fake (n) ; real (n)] of H x W (multiples of 4)."""
+    """Frozen LPIPS network.  plan(N, n, H, W): N = 2n images [fake (n) ; real (n)] of H x W (multiples of 4; the forward pass alone: any size from 31 x 31)."""
 
     def __init__(self, device='cuda'):
         self.device = torch.device(device)
@@ -168,10 +176,13 @@ class LPIPSAlexHIP:
     def distance(self, a, b):
         """LPIPS distance of two image batches [n][3][H][W] in [0, 1] (device tensors), mean over the batch: the validation metric
         (DASR_model.py:340-344 / SR_model.py:95-99: `cri_fea_lpips(im2tensor(fake), im2tensor(real))`, whose im2tensor maps uint8 to
-        [-1, 1]: the caller passes the 8-bit-quantised images / 255).  Plans of the last two image sizes are kept."""
+        [-1, 1]: the caller passes the 8-bit-quantised images / 255).  Any H, W >= 31: sizes that are multiples of 4 run dasr_lpips_s2d as they always
+        did, the others dasr_lpips_s2d_any.  Plans of the last two image sizes are kept."""
         n, c, H, W = a.shape
-        if c != 3 or tuple(b.shape) != tuple(a.shape) or H % 4 or W % 4:
-            raise ValueError('LPIPS distance: two [n,3,H,W] batches with H, W multiples of 4, got %s / %s' % (tuple(a.shape), tuple(b.shape)))
+        if c != 3 or tuple(b.shape) != tuple(a.shape):
+            raise ValueError('LPIPS distance: two [n,3,H,W] batches of one shape, got %s / %s' % (tuple(a.shape), tuple(b.shape)))
+        if H < MIN_SIDE or W < MIN_SIDE:
+            raise ValueError('LPIPS distance: images of %d x %d are below the %d x %d the network needs' % (H, W, MIN_SIDE, MIN_SIDE))
         key = ('val', n, H, W)
         lru = self.__dict__.setdefault('_val_lru', OrderedDict())
         if key in lru:
@@ -204,10 +215,11 @@ class _LPIPSPlan:
     `adjoint_op(dst)` that accumulates it into a blocked image gradient."""
 
     def __init__(self, net, N, n, H, W):
-        assert H % 4 == 0 and W % 4 == 0 and N >= 2 * n, (N, n, H, W)
+        self.any_size = bool(H % 4 or W % 4)   # forward only, through dasr_lpips_s2d_any
+        assert N >= 2 * n and (not self.any_size or min(H, W) >= MIN_SIDE), (N, n, H, W)
         self.net, self.N, self.n, self.H, self.W = net, N, n, H, W
         dev, P, pack = net.device, net.params, net.pack
-        Hs, Ws = (H + 4) // 4, (W + 4) // 4
+        Hs, Ws = s2d_grid(H), s2d_grid(W)
         self.x = BTensor(N, 48, Hs, Ws, True, dev)
         self.relu, self.pool, self.dims = [], [], []
         fwd = OpList()
@@ -263,6 +275,10 @@ class _LPIPSPlan:
         self._sh = [-(1.0 + sh) / s for sh, s in zip(SHIFT, SCALE)] + [0.0]
 
     def _s2d(self, img_view, n_imgs, y_view, mode):
+        if self.any_size:
+            if mode != 0:
+                raise ValueError('LPIPS at %d x %d: the adjoint and the symmetries exist at multiples of 4 only' % (self.H, self.W))
+            return make_op(_lib.OP_LPIPS_S2D_ANY, x=img_view, N=n_imgs, H=self.H, W=self.W, y=y_view, scale4=self._sc, shift4=self._sh)
         return make_op(_lib.OP_LPIPS_S2D, x=img_view, N=n_imgs, H=self.H, W=self.W, y=y_view, mode=mode, scale4=self._sc, shift4=self._sh)
 
     def input_op(self, img_view, n0, n_imgs):

@@ -4,6 +4,9 @@ What `test.evaluate` / `train.validate` otherwise do on the host with numpy (uti
 reference codes/SRN/utils/util.py:180-204, :236-291, data/util.py:169-190) runs here on csrc/metrics.hip: the fp32 SR / HR images the trainer holds
 after test() are quantised to uint8 on the device, the squared-error sums (integer for RGB, fp64 for Y) and the fp64 SSIM means are formed there,
 and ONE small read-back per call brings them to the host, where PSNR is formed in double with util.calculate_psnr's formula.  Numerics: DESIGN.md.
+
+Also the numbers of the folder evaluator (dasr_amd/dsn_evaluate.py; reference codes/DSN/evaluate.py:44-46, scikit-image's compare_psnr / compare_ssim) on two
+uint8 device images: pair_metrics_u8, with its own kernels for the 7 x 7 box SSIM and the channel sums.
 """
 import ctypes as C
 import logging
@@ -132,6 +135,85 @@ def batch_metrics(sr, hr, crop, ssim=True, y=True, min_max=(0, 1)):
         out['psnr_y'] = [_psnr(v, ch * cw) for v in f64[n:2 * n].tolist()]
         if ssim:
             out['ssim_y'] = f64[3 * n:4 * n].tolist()
+    return out
+
+
+# ---- the folder evaluator's numbers (codes/DSN/evaluate.py:44-46; CLI: dasr_amd/dsn_evaluate.py) ------------------------------------------------------------
+BOX_WINDOW = 7
+
+
+def psnr_from_sse(sse, count):
+    """skimage's compare_psnr of two uint8 images from the integer sum of their squared differences over `count` samples: 10 log10(255^2 / mse)"""
+    if sse == 0:
+        return float('inf')
+    return 10.0 * math.log10(255.0 ** 2 / (float(sse) / count))
+
+
+def psnr_col_from_sums(sums_a, sums_b, pixels):
+    """compare_psnr(img.mean(1).mean(0) / 255., gt.mean(1).mean(0) / 255.) from the integer channel sums: float vectors in [0, 1] have data range 1, so
+    10 log10(1 / mse) with mse the mean over the channels of the squared difference of the mean colours"""
+    mse = sum((sa / pixels / 255.0 - sb / pixels / 255.0) ** 2 for sa, sb in zip(sums_a, sums_b)) / len(sums_a)
+    if mse == 0:
+        return float('inf')
+    return 10.0 * math.log10(1.0 / mse)
+
+
+def u8_planes(hwc):
+    """decoded bytes on the device, uint8 [H, W, 3] -> (fp32 planar [3, H, W] = byte / 255 correctly rounded, uint8 planar [3, H, W]), both by kernels:
+    dasr_u8_to_planar, then dasr_tensor2img_u8 on its output (rint(float32(u / 255) * 255) == u for all 256 bytes, tests/test_evaluate_host.py)"""
+    if hwc.dtype != torch.uint8 or hwc.dim() != 3 or hwc.shape[2] != 3 or not hwc.is_cuda:
+        raise TypeError('expected a uint8 [H, W, 3] device tensor, got %s %s on %s' % (hwc.dtype, tuple(hwc.shape), hwc.device))
+    hwc = hwc.contiguous()
+    h, w = hwc.shape[:2]
+    L, st = _lib.lib(), _stream()
+    with torch.cuda.device(hwc.device):
+        f = torch.empty((3, h, w), dtype=torch.float32, device=hwc.device)
+        u = torch.empty((3, h, w), dtype=torch.uint8, device=hwc.device)
+        _lib.check(L.dasr_u8_to_planar(hwc.data_ptr(), h, w, h, w, f.data_ptr(), st), 'dasr_u8_to_planar')
+        _lib.check(L.dasr_tensor2img_u8(f.data_ptr(), 1, 3, h, w, 0.0, 1.0, None, u.data_ptr(), None, st), 'dasr_tensor2img_u8')
+    return f, u
+
+
+def pair_metrics_u8(a, b, border=0, lpips=None):
+    """{'psnr', 'psnr_col', 'ssim'} (Python floats) of two planar uint8 device images [3|1, H, W] with `border` pixels removed from every side, as
+    codes/DSN/evaluate.py forms them with scikit-image: PSNR of the bytes, PSNR of the mean colours, SSIM with the 7 x 7 uniform window and the sample
+    covariance.  The squared-error sum, the channel sums and the SSIM mean are formed on the device (dasr_img_sse, dasr_img_channel_sums, dasr_img_ssim_box);
+    ONE read-back brings the result words to the host, where the two PSNRs are formed in double.  `lpips`: a device scalar (LPIPSAlexHIP.distance) that
+    rides in the same read-back and is returned as 'lpips'.  A region under 7 x 7: ValueError."""
+    if a.dim() == 4 and a.shape[0] == 1:
+        a = a[0]
+    if b.dim() == 4 and b.shape[0] == 1:
+        b = b[0]
+    if a.dtype != torch.uint8 or b.dtype != torch.uint8 or a.dim() != 3 or a.shape[0] not in (1, 3) or a.shape != b.shape:
+        raise TypeError('expected two uint8 [3|1, H, W] images of one shape, got %s %s / %s %s' % (a.dtype, tuple(a.shape), b.dtype, tuple(b.shape)))
+    c, h, w = a.shape
+    border = int(border)
+    ch, cw = h - 2 * border, w - 2 * border
+    if border < 0 or ch < BOX_WINDOW or cw < BOX_WINDOW:
+        raise ValueError('border %d leaves %d x %d of a %d x %d image: under the %d x %d window of the SSIM' % (border, ch, cw, h, w, BOX_WINDOW, BOX_WINDOW))
+    if not (a.is_cuda and b.is_cuda and a.device == b.device):
+        raise _lib.DasrHipError('pair_metrics_u8 needs both images on one GPU')
+    a, b = a.contiguous(), b.contiguous()
+    L, st = _lib.lib(), _stream()
+    with torch.cuda.device(a.device):
+        ws_bytes = L.dasr_img_ws_bytes(1, c, h, w, border)
+        if ws_bytes < 0:
+            raise _lib.DasrHipError('dasr_img_ws_bytes refuses C %d H %d W %d crop %d' % (c, h, w, border))
+        ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.int64, device=a.device)
+        res = torch.zeros(3 + 2 * c, dtype=torch.int64, device=a.device)   # words: sse, ssim (fp64), c sums of a, c sums of b, lpips (fp64)
+        r0, args = res.data_ptr(), (1, c, h, w, border)
+        _lib.check(L.dasr_img_sse(a.data_ptr(), b.data_ptr(), *args, r0, None, ws.data_ptr(), ws_bytes, st), 'dasr_img_sse')
+        _lib.check(L.dasr_img_ssim_box(a.data_ptr(), b.data_ptr(), *args, r0 + 8, ws.data_ptr(), ws_bytes, st), 'dasr_img_ssim_box')
+        _lib.check(L.dasr_img_channel_sums(a.data_ptr(), *args, r0 + 16, ws.data_ptr(), ws_bytes, st), 'dasr_img_channel_sums')
+        _lib.check(L.dasr_img_channel_sums(b.data_ptr(), *args, r0 + 16 + 8 * c, ws.data_ptr(), ws_bytes, st), 'dasr_img_channel_sums')
+        if lpips is not None:
+            res[2 + 2 * c:].view(torch.float64).copy_(lpips.detach().reshape(1))
+        host = res.cpu()   # the one synchronisation
+    words, f64 = host.tolist(), host.view(torch.float64)
+    out = {'psnr': psnr_from_sse(words[0], c * ch * cw), 'psnr_col': psnr_col_from_sums(words[2:2 + c], words[2 + c:2 + 2 * c], ch * cw),
+           'ssim': float(f64[1])}
+    if lpips is not None:
+        out['lpips'] = float(f64[2 + 2 * c])
     return out
 
 

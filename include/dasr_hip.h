@@ -453,6 +453,16 @@ int dasr_bilinear_up(const float* src, int32_t N, int32_t h, int32_t w, int32_t 
  *    scale4 or shift4 null. */
 int dasr_lpips_s2d(dasr_tensor x, int32_t N, int32_t H, int32_t W, const float* scale4, const float* shift4, dasr_tensor y, int32_t mode,
                    void* stream);
+/* The forward input stage of dasr_lpips_s2d mode 0 (no symmetry, no adjoint) for ANY image size H, W >= 31 (the folder evaluator, dasr_amd/dsn_evaluate.py: result
+ * images and border crops have arbitrary sizes).  Per axis the 11 / stride 4 / pad 2 conv has Ho = (H - 7) / 4 + 1 outputs (integer division) and the grid has
+ * Hs = Ho + 2 block rows; y[c][Y][X][4*by+bx] = scale4[c]*x[c][4Y+by-2][4X+bx-2] + shift4[c] inside the image, 3 planes of Hs x Ws.
+ * Contracts (tests/test_gpu_evaluate.py):
+ *  - reads channels 0..2 of plane 0 of x; writes all 16 slots of exactly 3 planes of y; where the grid lies outside the image, on ANY side, y holds +0 bit for
+ *    bit.  (Rows and columns of the image past the last window of the conv are written too: they meet the zero taps of the re-indexed weights.)
+ *  - at multiples of 4, Hs = H / 4 + 1 and every byte equals what dasr_lpips_s2d mode 0 writes (the same kernel); callers keep using that entry point there.
+ *  - scale4 / shift4: HOST pointers to 4 floats (3 used), read by the launcher.
+ *  - DASR_EINVAL, nothing launched or dereferenced: N <= 0; H or W < 31 (below that the network's second pool has no output); x, y, scale4 or shift4 null. */
+int dasr_lpips_s2d_any(dasr_tensor x, int32_t N, int32_t H, int32_t W, const float* scale4, const float* shift4, dasr_tensor y, void* stream);
 /* nn.MaxPool2d(3, 2) of torchvision alexnet.features[2] / [5] on H x W inputs (output (H-3)/2+1), and its backward: gather form, first
  * maximum in scan order wins (ATen); relu_mask: zero where x <= 0; accumulate: gx += (the head gradient of that layer is already there).
  * Contracts (tests/test_gpu_lpips_prelu.py):
@@ -571,7 +581,8 @@ enum { DASR_OP_CONV = 1, DASR_OP_WGRAD = 2, DASR_OP_WGRAD_REDUCE = 3, DASR_OP_PA
        /* --wgan with BatchNorm discriminators (round 6): dasr_bnorm_lrelu_jvp, dasr_bnorm_second */
        DASR_OP_BNORM_JVP = 50, DASR_OP_BNORM_SECOND = 51,
        DASR_OP_PRELU_FINAL = 52,  /* dasr_prelu_final */
-       DASR_OP_RESBLOCK = 53      /* dasr_resblock (host dasr_resblock_params, kept alive by the plan) */ };
+       DASR_OP_RESBLOCK = 53,     /* dasr_resblock (host dasr_resblock_params, kept alive by the plan) */
+       DASR_OP_LPIPS_S2D_ANY = 54 /* dasr_lpips_s2d_any */ };
 
 typedef struct {
     int32_t op;  int32_t i[8];  float f[4];  int64_t l[4];  void* p[4];  dasr_tensor t[5];
@@ -623,7 +634,21 @@ int dasr_rccl_destroy(void* comm);
  *
  * The grid sums are per-workgroup partials in `ws` (device, ws_size bytes >= dasr_img_ws_bytes(N, C, H, W, crop), 8-byte aligned) added in index order
  * by a second launch: no floating-point atomics, the same bits run to run.  Calls that share `ws` must be ordered by their stream.  sse, sse_y, ssim,
- * nan_count: device memory; nothing is synchronised.  Null pointers, N <= 0, C not 1 or 3, 2 crop >= H or W: DASR_EINVAL, nothing is launched. */
+ * nan_count: device memory; nothing is synchronised.  Null pointers, N <= 0, C not 1 or 3, 2 crop >= H or W: DASR_EINVAL, nothing is launched.
+ *
+ * The two entry points of the folder evaluator (codes/DSN/evaluate.py:44-46; dasr_amd/metrics.py pair_metrics_u8), additive under ABI 22, on the same planar
+ * uint8 images, crop and workspace -- dasr_img_ws_bytes covers both:
+ *
+ * dasr_img_ssim_box: ssim[n] = mean over every channel and every 7 x 7 window that lies wholly inside the cropped image of the SSIM of that window in the form of
+ * skimage.measure.compare_ssim(X, Y, multichannel=True) on uint8 (uniform filter, use_sample_covariance=True, data_range 255): with the window sums Sx, Sy,
+ * Sxx, Syy, Sxy over n = 49 pixels, ux = Sx / n, vx = (n Sxx - Sx^2) / (n (n - 1)) (vy, vxy likewise), C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2,
+ * S = (2 ux uy + C1)(2 vxy + C2) / ((ux^2 + uy^2 + C1)(vx + vy + C2)).  The five sums are formed as exact 32-bit integers and S is evaluated once per window in
+ * fp64 from them, so the map does not depend on the tiling; identical images give exactly 1.  A cropped side under 7 pixels: DASR_EINVAL.
+ *
+ * dasr_img_channel_sums: sums[n * C + c] = the exact integer sum of the bytes of channel c of image n over the cropped region (the mean colour of PSNR_col).
+ *
+ * Both: per-workgroup partials in ws, added in index order by a second launch (no atomics, the same bits run to run); ssim / sums: device memory.  Null pointers,
+ * N <= 0, C not 1 or 3, 2 crop >= H or W, ws_size under what the call needs: DASR_EINVAL, nothing is launched. */
 int dasr_img_ws_bytes(int32_t N, int32_t C, int32_t H, int32_t W, int32_t crop);   /* bytes, or DASR_EINVAL */
 int dasr_tensor2img_u8(const float* x, int32_t N, int32_t C, int32_t H, int32_t W, double lo, double hi, uint8_t* hwc_bgr, uint8_t* planar,
                        int32_t* nan_count, void* stream);
@@ -631,6 +656,9 @@ int dasr_img_sse(const uint8_t* a, const uint8_t* b, int32_t N, int32_t C, int32
                  void* ws, int64_t ws_size, void* stream);
 int dasr_img_ssim(const uint8_t* a, const uint8_t* b, int32_t N, int32_t C, int32_t H, int32_t W, int32_t crop, int32_t y_channel, double* ssim,
                   void* ws, int64_t ws_size, void* stream);
+int dasr_img_ssim_box(const uint8_t* a, const uint8_t* b, int32_t N, int32_t C, int32_t H, int32_t W, int32_t crop, double* ssim, void* ws, int64_t ws_size,
+                      void* stream);
+int dasr_img_channel_sums(const uint8_t* a, int32_t N, int32_t C, int32_t H, int32_t W, int32_t crop, int64_t* sums, void* ws, int64_t ws_size, void* stream);
 
 /* ---- input stage of the evaluation datasets (csrc/imgio.hip) ---------------------------------------------------------------------
  * What data.EvalFolderDataset runs per image file in place of the host's read_img / modcrop / imresize_np (codes/SRN/data/util.py:78-96, :133-145,
