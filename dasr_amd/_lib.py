@@ -302,6 +302,8 @@ _SIGS = {
     'dasr_crops_down4_u8': [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp],
     'dasr_dihedral8': [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp],
     'dasr_dihedral8_mean': [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp],
+    'dasr_bp_residual': [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    'dasr_bp_update': [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     'dasr_prof_begin': [c_i32],
     'dasr_prof_end': [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp],
 }

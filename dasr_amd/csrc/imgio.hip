@@ -12,6 +12,7 @@
 //    (per-descriptor window size and destination), the second the augmented LR crops of an HR-only set: samples of the x1/4 image of the WHOLE image, made where a crop needs them.
 //  * dihedral8 / dihedral8_mean: the geometry of the x8 self-ensemble (`"self_ensemble": true`; reference: codes/SRN/models/SR_model.py:102-140 test_x8): the eight flips /
 //    transposes of the LR image in one launch, and the mean of the eight inverse-transformed SR images in one launch with a fixed order of the adds.
+//  * bp_residual / bp_update: the two launches of one iteration of the back-projection of an SR image onto its LR input (`"back_projection"`), at the end of the file.
 // The first two are memory-bound (about 36 multiply-adds per output sample at s = 4 against 2 x 18 gathered reads), so the kernels are plain: one thread per output
 // sample, the x index on the lanes so that loads and stores of a wave are contiguous (pass 2 reads with a stride of s samples inside one row of the
 // intermediate, which the 18-tap overlap of neighbouring outputs keeps in cache), no LDS, no atomics.
@@ -460,4 +461,251 @@ extern "C" int dasr_dihedral8_mean(const float* sr_a, const float* sr_b, int32_t
     HIP_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds));   // (per call: the attribute belongs to the current device)
     DASR_LAUNCH_TAG("dihedral8_mean_kernel", k, grid, dim3(256), (size_t)lds, as_stream(stream), sr_a, sr_b, (int)H, (int)W, dst);
     return (int)hipGetLastError();
+}
+
+// ---- iterative back-projection (`"back_projection"`; reference: codes/SRN/scripts/back_projection/backprojection.m:1-20, main_bp.m; host side: dasr_amd/backproject.py) ------
+// One iteration is   d = LR - imresize(SR, 1 / s);   SR += conv2(imresize(d, s), p, 'same')   with p the squared,
+// renormalised 5 x 5 Gaussian of sigma 1 -- the outer product of u_i = exp(-i^2) / sum_j exp(-j^2), i = -2 .. 2.  Two launches:
+//  * bp_residual_kernel: d = lr - (float)down(sr), `down` bit for bit dasr_imresize_down above: the same tap tables, rows first, fp64 products rounded before
+//    they are added in tap order, one rounding to fp32 -- but both passes through LDS (the scheme of crops_bicubic_down_kernel): a workgroup stages the HR window its
+//    BP_RT x BP_CT tile of LR outputs reaches once and no fp64 intermediate goes to device memory.
+//  * bp_update_kernel: sr += G(U), U = imresize(d, s) (bicubic, NOT antialiased: 6-entry tap tables of imgio.bicubic_taps(n, s), rows first), G the separable 5-tap pass
+//    in both directions.  Per BP_UY x BP_UX tile of SR samples, all in LDS: the d window, the row pass V, U with a halo of 2, the horizontal 5-tap pass T, then the vertical
+//    5-tap pass added to the thread's own sr sample and rounded to fp32 ONCE.  In place: a thread reads sr only where it writes.
+//    Two halo rules meet here and are kept apart: the up-sampling mirrors at the IMAGE border (the tables carry the mirrored indices, which point back into the staged
+//    window); the 5 x 5 pass sees zeros beyond the IMAGE border (conv2 'same') but the real neighbours beyond a TILE border (U is evaluated on the halo).
+// Both are memory / LDS work with a few dozen fp64 operations per sample; the tiles only group outputs: every output sample is the same sequence of operations for any tile.
+// Table indices are clamped into the staged window: a damaged table reads a wrong staged sample, never outside the window or the image.
+//
+// (fp contraction is off for the whole file: every product is rounded to fp64 before it is added, in a fixed order.)
+namespace {
+
+constexpr int BP_RT = DASR_BP_RES_TILE_H, BP_CT = DASR_BP_RES_TILE_W;   // LR outputs per workgroup of the residual kernel
+constexpr int BP_UY = DASR_BP_UPD_TILE_H, BP_UX = DASR_BP_UPD_TILE_W;   // SR samples per workgroup of the update kernel
+
+// Output sample o of imresize(., 1 / S) takes the 4 S + 2 source samples from S o - OFF on (before mirroring), OFF = S + 1 + S / 2 (4, 5, 7 for S = 2, 3, 4:
+// bicubic_taps' floor(u - 2 S) at u = (o + 1) S + (1 - S) / 2).  The window is taken ONE sample wider on both sides, so it does not hinge on how that floor rounded.
+//   LDS at S = 4: in [48][144] fp32 + mid [8][4][37] fp64 + the tile's taps ([18][32] column, [8][18] row; int32 + fp64) = 27648 + 9472 + 6912 + 1728 = 45760 bytes, three workgroups on a CU.
+//   mid is stored de-interleaved by x mod S (row r, window column x at [r][x % S][x / S]): the column pass reads columns S ox + const, consecutive doubles over the lanes.
+//   Latency: a workgroup is a chain of dependent steps (stage, row pass, column pass), and with three or four workgroups on a CU nothing hides a trip to memory inside one.
+//   So EVERYTHING the workgroup reads from memory is requested before the first barrier, each thread's loads all in flight together: the window (a compile-time number of
+//   masked loads per thread into registers, then the LDS stores), the tile's rows of both tap tables (the column taps transposed to [tap][column]: read from memory in the
+//   column pass they are a stride of 4 S + 2 entries between the lanes) and the thread's own lr sample.  After the barrier the kernel touches only LDS, until its one store.
+template <int S>
+__global__ __launch_bounds__(256) void bp_residual_kernel(const float* __restrict__ sr, const float* __restrict__ lr, int H, int W, const int32_t* __restrict__ idx_h,
+                                                          const double* __restrict__ w_h, const int32_t* __restrict__ idx_w, const double* __restrict__ w_w,
+                                                          float* __restrict__ d) {
+    constexpr int TAPS = 4 * S + 2, OFF = S + 1 + S / 2;
+    constexpr int WIN_H = S * BP_RT + 3 * S + 4, WIN_W = S * BP_CT + 3 * S + 4, QS = (WIN_W + S - 1) / S + 1;
+    constexpr int NLD = (WIN_H * WIN_W + 255) / 256, NROW = (BP_RT * WIN_W + 255) / 256;
+    static_assert(BP_RT * BP_CT == 256 && BP_RT * TAPS <= 256, "one output per thread in the column pass; the row taps are staged in one step");
+    __shared__ float in[WIN_H * WIN_W];
+    __shared__ double mid[BP_RT * S * QS];
+    __shared__ double tw[TAPS * BP_CT], rw[BP_RT * TAPS];
+    __shared__ int32_t tj[TAPS * BP_CT], rj[BP_RT * TAPS];
+    const int tid = threadIdx.x;
+    const int h = H / S, w = W / S;
+    const int ox0 = blockIdx.x * BP_CT, oy0 = blockIdx.y * BP_RT;
+    const int rows = min(BP_RT, h - oy0), cols = min(BP_CT, w - ox0);
+    const int by = max(S * oy0 - OFF - 1, 0), bx = max(S * ox0 - OFF - 1, 0);
+    const int nh = min(min(S * (oy0 + rows - 1) - OFF + TAPS, H - 1) - by + 1, WIN_H), nw = min(min(S * (ox0 + cols - 1) - OFF + TAPS, W - 1) - bx + 1, WIN_W);
+#pragma unroll
+    for (int e = tid; e < BP_CT * TAPS; e += 256) {   // (rows ox0 .. ox0 + cols - 1 of the column table: one contiguous run; kept as window columns)
+        const int ox = e / TAPS, t = e - ox * TAPS;
+        if (ox < cols) {
+            tj[t * BP_CT + ox] = min(max(idx_w[(size_t)ox0 * TAPS + e] - bx, 0), nw - 1);
+            tw[t * BP_CT + ox] = w_w[(size_t)ox0 * TAPS + e];
+        }
+    }
+    if (tid < rows * TAPS) {                           // (rows oy0 .. oy0 + rows - 1 of the row table, kept as offsets of window rows)
+        rj[tid] = min(max(idx_h[(size_t)oy0 * TAPS + tid] - by, 0), nh - 1) * WIN_W;
+        rw[tid] = w_h[(size_t)oy0 * TAPS + tid];
+    }
+    const int orow = tid / BP_CT, ox = tid % BP_CT;
+    const bool live = orow < rows && ox < cols;
+    const size_t o = ((size_t)blockIdx.z * h + oy0 + min(orow, rows - 1)) * w + ox0 + min(ox, cols - 1);
+    const float lrv = lr[o];
+    const float* plane = sr + (size_t)blockIdx.z * H * W + (size_t)by * W + bx;
+    float v[NLD];
+#pragma unroll
+    for (int k = 0; k < NLD; ++k) {
+        const int e = tid + 256 * k, r = e / WIN_W, x = e - r * WIN_W;
+        v[k] = (r < nh && x < nw) ? plane[(size_t)r * W + x] : 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < NLD; ++k)
+        if (tid + 256 * k < WIN_H * WIN_W) in[tid + 256 * k] = v[k];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NROW; ++k) {
+        const int e = tid + 256 * k, r = e / WIN_W, x = e - r * WIN_W;
+        if (r < rows && x < nw) {
+            double acc = 0.0;
+#pragma unroll
+            for (int t = 0; t < TAPS; ++t) acc += rw[r * TAPS + t] * (double)in[rj[r * TAPS + t] + x];
+            mid[(r * S + x % S) * QS + x / S] = acc;
+        }
+    }
+    __syncthreads();
+    if (live) {
+        double acc = 0.0;
+#pragma unroll
+        for (int t = 0; t < TAPS; ++t) {
+            const int j = tj[t * BP_CT + ox];
+            acc += tw[t * BP_CT + ox] * mid[(orow * S + j % S) * QS + j / S];
+        }
+        d[o] = lrv - (float)acc;
+    }
+}
+
+// floor((2 Y + 1 - S) / (2 S)): the LR sample at or below SR position Y (the centre of SR sample Y sits at (Y + 0.5) / S - 0.5 in LR coordinates)
+template <int S>
+__device__ __forceinline__ int bp_lr_floor(int Y) {
+    const int a = 2 * Y + 1 - S;
+    return a >= 0 ? a / (2 * S) : -((-a + 2 * S - 1) / (2 * S));
+}
+
+struct bp_u5 { double u[5]; };
+
+// SR sample Y of imresize(., S) takes the LR samples bp_lr_floor(Y) - 2 .. + 3 (6 table entries, the outer ones with weight 0 or mirrored).  The staged d window is that
+// range for the tile and its halo of 2, one sample wider on both sides, cut at the image: at most ceil((T + 3) / S) + 8 samples along an axis with T tile samples.
+//   LDS at S = 2 (the largest): dwin [18][42] fp32 + V [20][42] + U [20][68] + T [20][64] fp64 + the taps ([6][68] column, [20][6] row; int32 + fp64)
+//   = 3024 + 6720 + 10880 + 10240 + 4896 + 1440 = 37200 bytes, four workgroups on a CU.
+//   As in bp_residual_kernel everything read from memory is requested before the first barrier: the d window, the tile's rows of both tap tables (clamped into the
+//   window; the column taps transposed to [tap][column]) and the thread's own four sr samples, which wait in registers for the last step.
+// grid (ceil(W / BP_UX), ceil(H / BP_UY), C), H = S h, W = S w
+template <int S>
+__global__ __launch_bounds__(256) void bp_update_kernel(float* __restrict__ sr, const float* __restrict__ d, int h, int w, const int32_t* __restrict__ idx_h,
+                                                        const double* __restrict__ w_h, const int32_t* __restrict__ idx_w, const double* __restrict__ w_w, bp_u5 g) {
+    constexpr int HY = BP_UY + 4, HX = BP_UX + 4;
+    constexpr int DH = (HY - 1 + S - 1) / S + 8, DW = (HX - 1 + S - 1) / S + 8;
+    constexpr int NLD = (DH * DW + 255) / 256, NOUT = BP_UY * BP_UX / 256;
+    static_assert(BP_UY * BP_UX % 256 == 0 && HY * 6 <= 256, "whole steps of 256 outputs; the row taps are staged in one step");
+    __shared__ float dwin[DH * DW];
+    __shared__ double V[HY * DW];
+    __shared__ double U[HY * HX];
+    __shared__ double T[HY * BP_UX];
+    __shared__ double cw[6 * HX], rw[HY * 6];
+    __shared__ int32_t cj[6 * HX], rj[HY * 6];
+    const int tid = threadIdx.x;
+    const int H = S * h, W = S * w;
+    const int X0 = blockIdx.x * BP_UX, Y0 = blockIdx.y * BP_UY;
+    const int ya = max(Y0 - 2, 0), yb = min(Y0 + BP_UY + 1, H - 1), xa = max(X0 - 2, 0), xb = min(X0 + BP_UX + 1, W - 1);
+    const int ly0 = max(bp_lr_floor<S>(ya) - 3, 0), lx0 = max(bp_lr_floor<S>(xa) - 3, 0);
+    const int nh = min(min(bp_lr_floor<S>(yb) + 4, h - 1) - ly0 + 1, DH), nw = min(min(bp_lr_floor<S>(xb) + 4, w - 1) - lx0 + 1, DW);
+#pragma unroll
+    for (int e = tid; e < 6 * HX; e += 256) {   // (the table rows of SR columns X0 - 2 .. X0 + BP_UX + 1 inside the image: one contiguous run)
+        const int Xl = e / 6, t = e - Xl * 6, X = X0 - 2 + Xl;
+        if (X >= 0 && X < W) {
+            cj[t * HX + Xl] = min(max(idx_w[(size_t)X * 6 + t] - lx0, 0), nw - 1);
+            cw[t * HX + Xl] = w_w[(size_t)X * 6 + t];
+        }
+    }
+    if (tid < HY * 6) {
+        const int Y = Y0 - 2 + tid / 6;
+        if (Y >= 0 && Y < H) {
+            rj[tid] = min(max(idx_h[(size_t)Y * 6 + tid % 6] - ly0, 0), nh - 1) * DW;
+            rw[tid] = w_h[(size_t)Y * 6 + tid % 6];
+        }
+    }
+    float* sp = sr + (size_t)blockIdx.z * H * W;
+    float own[NOUT];
+#pragma unroll
+    for (int k = 0; k < NOUT; ++k) {
+        const int e = tid + 256 * k, Y = Y0 + e / BP_UX, X = X0 + e % BP_UX;
+        own[k] = (Y < H && X < W) ? sp[(size_t)Y * W + X] : 0.f;
+    }
+    const float* dp = d + (size_t)blockIdx.z * h * w + (size_t)ly0 * w + lx0;
+    float v[NLD];
+#pragma unroll
+    for (int k = 0; k < NLD; ++k) {
+        const int e = tid + 256 * k, r = e / DW, x = e - r * DW;
+        v[k] = (r < nh && x < nw) ? dp[(size_t)r * w + x] : 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < NLD; ++k)
+        if (tid + 256 * k < DH * DW) dwin[tid + 256 * k] = v[k];
+    __syncthreads();
+    // row pass of the up-sampling: V[Yl][x] for SR row Y = Y0 - 2 + Yl inside the image, window column x
+#pragma unroll
+    for (int e = tid; e < HY * DW; e += 256) {
+        const int Yl = e / DW, x = e - Yl * DW, Y = Y0 - 2 + Yl;
+        if (Y < 0 || Y >= H || x >= nw) continue;
+        double acc = 0.0;
+#pragma unroll
+        for (int t = 0; t < 6; ++t) acc += rw[Yl * 6 + t] * (double)dwin[rj[Yl * 6 + t] + x];
+        V[e] = acc;
+    }
+    __syncthreads();
+    // column pass: U on the tile and its halo; zero beyond the IMAGE (conv2 'same'), the real up-sampled value beyond the tile
+#pragma unroll
+    for (int e = tid; e < HY * HX; e += 256) {
+        const int Yl = e / HX, Xl = e - Yl * HX, Y = Y0 - 2 + Yl, X = X0 - 2 + Xl;
+        double acc = 0.0;
+        if (Y >= 0 && Y < H && X >= 0 && X < W) {
+#pragma unroll
+            for (int t = 0; t < 6; ++t) acc += cw[t * HX + Xl] * V[Yl * DW + cj[t * HX + Xl]];
+        }
+        U[e] = acc;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int e = tid; e < HY * BP_UX; e += 256) {
+        const int Yl = e / BP_UX, xl = e - Yl * BP_UX;
+        const double* up = U + Yl * HX + xl;
+        double acc = 0.0;
+#pragma unroll
+        for (int b = 0; b < 5; ++b) acc += g.u[b] * up[b];
+        T[e] = acc;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NOUT; ++k) {
+        const int e = tid + 256 * k, yl = e / BP_UX, xl = e % BP_UX, Y = Y0 + yl, X = X0 + xl;
+        if (Y >= H || X >= W) continue;
+        double acc = 0.0;
+#pragma unroll
+        for (int a = 0; a < 5; ++a) acc += g.u[a] * T[(yl + a) * BP_UX + xl];
+        sp[(size_t)Y * W + X] = (float)((double)own[k] + acc);
+    }
+}
+
+template <int S>
+int bp_residual_launch(const float* sr, const float* lr, int C, int H, int W, const int32_t* idx_h, const double* w_h, const int32_t* idx_w, const double* w_w, float* d,
+                       void* stream) {
+    const dim3 grid((unsigned)((W / S + BP_CT - 1) / BP_CT), (unsigned)((H / S + BP_RT - 1) / BP_RT), (unsigned)C);
+    auto k = bp_residual_kernel<S>;
+    DASR_LAUNCH_TAG("bp_residual_kernel", k, grid, dim3(256), 0, as_stream(stream), sr, lr, H, W, idx_h, w_h, idx_w, w_w, d);
+    return (int)hipGetLastError();
+}
+
+template <int S>
+int bp_update_launch(float* sr, const float* d, int C, int h, int w, const int32_t* idx_h, const double* w_h, const int32_t* idx_w, const double* w_w, const bp_u5& g,
+                     void* stream) {
+    const dim3 grid((unsigned)((S * w + BP_UX - 1) / BP_UX), (unsigned)((S * h + BP_UY - 1) / BP_UY), (unsigned)C);
+    auto k = bp_update_kernel<S>;
+    DASR_LAUNCH_TAG("bp_update_kernel", k, grid, dim3(256), 0, as_stream(stream), sr, d, h, w, idx_h, w_h, idx_w, w_w, g);
+    return (int)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" int dasr_bp_residual(const float* sr, const float* lr, int32_t C, int32_t H, int32_t W, int32_t s, const int32_t* idx_h, const double* w_h, const int32_t* idx_w,
+                                const double* w_w, float* d, void* stream) {
+    if (!sr || !lr || !idx_h || !w_h || !idx_w || !w_w || !d || C <= 0 || C > 65535 || H <= 0 || W <= 0 || H > 65535 || W > 65535) return DASR_EINVAL;
+    if (s < 2 || s > 4 || H % s || W % s) return DASR_EINVAL;
+    return s == 2 ? bp_residual_launch<2>(sr, lr, C, H, W, idx_h, w_h, idx_w, w_w, d, stream)
+         : s == 3 ? bp_residual_launch<3>(sr, lr, C, H, W, idx_h, w_h, idx_w, w_w, d, stream)
+                  : bp_residual_launch<4>(sr, lr, C, H, W, idx_h, w_h, idx_w, w_w, d, stream);
+}
+
+extern "C" int dasr_bp_update(float* sr, const float* d, int32_t C, int32_t h, int32_t w, int32_t s, const int32_t* idx_h, const double* w_h, const int32_t* idx_w,
+                              const double* w_w, const double* u5, void* stream) {
+    if (!sr || !d || !idx_h || !w_h || !idx_w || !w_w || !u5 || C <= 0 || C > 65535 || h <= 0 || w <= 0 || s < 2 || s > 4) return DASR_EINVAL;
+    if (h > 65535 / s || w > 65535 / s) return DASR_EINVAL;
+    bp_u5 g;
+    for (int i = 0; i < 5; ++i) g.u[i] = u5[i];
+    return s == 2 ? bp_update_launch<2>(sr, d, C, h, w, idx_h, w_h, idx_w, w_w, g, stream)
+         : s == 3 ? bp_update_launch<3>(sr, d, C, h, w, idx_h, w_h, idx_w, w_w, g, stream)
+                  : bp_update_launch<4>(sr, d, C, h, w, idx_h, w_h, idx_w, w_w, g, stream);
 }

@@ -312,6 +312,8 @@ class DASR_Model(BaseModel):
     def test(self, tsamples=False):
         """inference on var_L (DASR_model.py:333-345; `chop`: quadrant inference, utils/util.py:87-147)"""
         self.fake_H = self._generate(self.var_L)
+        if not tsamples:   # (the training-sample visuals show the generator's own output)
+            self._back_project()
         if not tsamples and self.opt['val_lpips']:
             self._eval_lpips()
 

@@ -116,6 +116,16 @@ def tap_table(n_in, s, device):
     return _TABLES[key]
 
 
+def up_tap_table(n_in, s, device):
+    """device tap table of bicubic_taps(n_in, s), the up-sampling by the integer s as dasr_bp_update reads it: (int32 index, fp64 weight), both [s n_in, 6];
+    uploaded once per (device, n_in, s) for the whole process"""
+    key = (device, n_in, s, 'up')
+    if key not in _TABLES:
+        j, w = bicubic_taps(n_in, float(s))
+        _TABLES[key] = (j.to(torch.int32).contiguous().to(device), w.contiguous().to(device))
+    return _TABLES[key]
+
+
 def down4_weights():
     """the 18 weights of MATLAB's antialiased bicubic at scale 1 / 4 as a ctypes array: ONE row of bicubic_taps(n, 0.25)[1] -- the sample positions u = 4 k - 1.5 have the
     same fractional part for every k, so every output sample has bit-equal weights (tests/test_srn_device_data_host.py)"""

@@ -197,6 +197,15 @@ class BaseModel:
             return forward_chop(x, self.opt['scale'], lambda t: self.netG.forward(t).clone(), min_size=320000)
         return self.netG.forward(x).clone()
 
+    def _back_project(self):
+        """option `back_projection`: fake_H of test() / test_x8() replaced by its iterative back-projection onto var_L (codes/SRN/scripts/back_projection/backprojection.m,
+        dasr_amd/backproject.py), in front of LPIPS and of everything the drivers do with the image; off, nothing is touched"""
+        from .options import back_projection_iters
+        n = back_projection_iters(self.opt['back_projection'])
+        if n:
+            from .backproject import back_project
+            self.fake_H = back_project(self.fake_H, self.var_L, n)
+
     def test_x8(self):
         """geometric self-ensemble inference on var_L (SR_model.py:102-140), same contract as test(): sets fake_H [1, C, sH, sW] and, under `val_lpips`, LPIPS (the
         reference's test_x8 never computes it; here the drivers need no second code path).  The generator runs on the eight flips / transposes of the LR image,
@@ -211,6 +220,7 @@ class BaseModel:
         lr_a, lr_b = dihedral8(self.var_L[0])
         sr_a = self._generate(lr_a)   # (its own tensor: for a square image both batches run on the same plan)
         self.fake_H = dihedral8_mean(sr_a, self._generate(lr_b))
+        self._back_project()
         if self.opt['val_lpips']:
             self._eval_lpips()
 
@@ -510,6 +520,7 @@ class SRModel(BaseModel):
     def test(self):
         """inference on var_L (SR_model.py:87-93; `chop`: quadrant inference of DASR_model.py:333-339 / util.py:87-147)"""
         self.fake_H = self._generate(self.var_L)
+        self._back_project()
         if self.opt['val_lpips']:
             self._eval_lpips()
 

@@ -53,6 +53,7 @@ def parse(opt_path, is_train=True):
         opt['path']['results_root'] = root
         opt['path']['log'] = root
     opt['network_G']['scale'] = scale
+    back_projection_iters(opt.get('back_projection'))   # (checked here, read by the models: a bad value stops the run before a network is built)
     # codes/SRN/options/options.py:68-71 exports CUDA_VISIBLE_DEVICES = gpu_ids for its single-process nn.DataParallel.  HIP honours
     # that variable too, so under one-process-per-GPU launch (torch.distributed.run sets WORLD_SIZE / LOCAL_RANK) it would hide every
     # device but the listed ones from EVERY rank (the shipped JSONs say gpu_ids [0]: rank 1's set_device(1) would fail).  Rule:
@@ -65,6 +66,21 @@ def parse(opt_path, is_train=True):
         os.environ['CUDA_VISIBLE_DEVICES'] = gpu_list
         print('export CUDA_VISIBLE_DEVICES=' + gpu_list)
     return opt
+
+
+BACK_PROJECTION_DEFAULT = 20   # main_bp.m:7 max_iter
+
+
+def back_projection_iters(value):
+    """the iteration count the top-level key `"back_projection"` asks for: true -> 20 (codes/SRN/scripts/back_projection/main_bp.m:7), a positive integer N -> N,
+    absent / false / 0 -> 0 (off); anything else is a ValueError"""
+    if value is None or value is False:
+        return 0
+    if value is True:
+        return BACK_PROJECTION_DEFAULT
+    if isinstance(value, int) and value >= 0:
+        return value
+    raise ValueError('back_projection: expected true, false or a number of iterations >= 0, got %r' % (value,))
 
 
 class NoneDict(dict):

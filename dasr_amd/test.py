@@ -3,7 +3,7 @@
 For every dataset of the option file: feed_data -> test() -> get_current_visuals -> SR image saved under
 <results_root>/<dataset name>/imgs, and, when HR is present, PSNR / SSIM on the `scale`-pixel-cropped uint8 images in RGB and on the
 Y channel, per image and averaged (same log lines as the reference).  `device_metrics: true` quantises the images and evaluates the four numbers on the
-GPU (dasr_amd/metrics.py) instead of with the numpy helpers of dasr_amd/util.py; absent, the host path is unchanged.  `chop: true` runs the quadrant inference.  `self_ensemble: true` replaces test() by test_x8(), the x8 geometric self-ensemble (SR_model.py:102-140), everything downstream unchanged.  `val_lpips: true` adds the
+GPU (dasr_amd/metrics.py) instead of with the numpy helpers of dasr_amd/util.py; absent, the host path is unchanged.  `chop: true` runs the quadrant inference.  `self_ensemble: true` replaces test() by test_x8(), the x8 geometric self-ensemble (SR_model.py:102-140), everything downstream unchanged.  `back_projection: true | N` back-projects every SR image onto its LR image (20 | N iterations, dasr_amd/backproject.py) before it is saved and scored.  `val_lpips: true` adds the
 LPIPS(alex) distance of the 8-bit images (test.py:88-128; weights from `path.lpips_alexnet` / `path.lpips_lin`, seeded when absent).
 `save_RealorFake` needs the discriminator visual, not available here: NotImplementedError.  Datasets: `mode: "LRHR"` (HR folder, LR folder or LR made by bicubic down-sampling) and `mode: "LR"` read image folders through data.EvalFolderDataset; `mode: "synthetic"` ships
 seeded LR/HR pairs; any iterable of the reference's batch dicts works through `main(loaders=...)`.
@@ -17,7 +17,7 @@ from collections import OrderedDict
 from . import options as option
 from . import util
 from .models import create_model
-from .train import SELF_ENSEMBLE_NOTE, create_dataset, setup_logger
+from .train import BACK_PROJECTION_NOTE, SELF_ENSEMBLE_NOTE, create_dataset, setup_logger
 
 
 def evaluate(model, loader, opt, dataset_dir, logger, scale):
@@ -99,6 +99,8 @@ def main(argv=None, loaders=None):
     model = create_model(opt)
     if opt['self_ensemble']:
         logger.info(SELF_ENSEMBLE_NOTE)
+    if option.back_projection_iters(opt['back_projection']):
+        logger.info(BACK_PROJECTION_NOTE.format(option.back_projection_iters(opt['back_projection'])))
     summary = OrderedDict()
     for name, loader in loaders:
         logger.info('\nTesting [{:s}]...'.format(name))

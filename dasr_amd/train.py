@@ -96,6 +96,7 @@ def create_dataset(ds_opt, opt):
 
 
 SELF_ENSEMBLE_NOTE = 'self_ensemble: x8 self-ensemble inference is on (test_x8: the generator on the eight flips / transposes of every LR image, their SR images averaged)'
+BACK_PROJECTION_NOTE = 'back_projection: every SR image is back-projected onto its LR image, {:d} iterations on the GPU (csrc/imgio.hip), before it is saved and scored'
 
 
 def validate(model, val_set, opt, current_step, logger):
@@ -246,6 +247,8 @@ def main(argv=None):
         model.resume_training(resume_state, opt['train'])
     if opt['self_ensemble'] and val_set is not None:
         logger.info(SELF_ENSEMBLE_NOTE)
+    if option.back_projection_iters(opt['back_projection']) and val_set is not None:
+        logger.info(BACK_PROJECTION_NOTE.format(option.back_projection_iters(opt['back_projection'])))
     logger.info('Start training from epoch: {:d}, iter: {:d}'.format(start_epoch, current_step))
     for epoch in range(start_epoch, total_epochs):
         for batch in train_set:

@@ -752,6 +752,32 @@ int dasr_crops_down4_u8(const dasr_srn_u8_desc* descs_dev, const dasr_srn_u8_des
 int dasr_dihedral8(const float* x, int32_t C, int32_t H, int32_t W, float* dst_a, float* dst_b, void* stream);
 int dasr_dihedral8_mean(const float* sr_a, const float* sr_b, int32_t C, int32_t H, int32_t W, float* dst, void* stream);
 
+/* ---- iterative back-projection of an SR image onto its LR input (csrc/imgio.hip) -----------------------------------------------------
+ * One iteration of codes/SRN/scripts/back_projection/backprojection.m:12-19 as two launches (dasr_amd/backproject.py back_project):
+ * d = LR - imresize(SR, 1 / s), then SR += conv2(imresize(d, s), p, 'same').  Planar fp32 images, s in {2, 3, 4}, any LR size h, w >= 1 and C >= 1, asynchronous on
+ * `stream`, no atomics, nothing is synchronised, same inputs give the same bits.  All tables are device memory.
+ *
+ * dasr_bp_residual: sr [C][H][W], lr and d [C][H / s][W / s].  d[c][y][x] = lr[c][y][x] - (float)down(sr)[c][y][x], the subtraction in fp32, `down` bit for bit what
+ * dasr_imresize_down writes: the tap tables of data.bicubic_taps(n, 1 / s) (idx_* [n / s][4 s + 2] int32 mirrored into [0, n), w_* fp64), rows first, fp64 products
+ * rounded before they are added in tap order, one rounding to fp32.  Both passes run in LDS on the HR window a DASR_BP_RES_TILE_H x DASR_BP_RES_TILE_W tile of LR
+ * outputs reaches; there is no intermediate in device memory.  d must not overlap sr or lr.
+ *
+ * dasr_bp_update: IN PLACE on sr [C][s h][s w]; d [C][h][w].  sr[c][y][x] = (float)((double)sr[c][y][x] + sum over a, b = -2 .. 2 of u5[a + 2] * u5[b + 2] * U[c][y + a][x + b]),
+ * U = 0 outside the image and U = imresize(d, s) inside (bicubic, not antialiased): the tables of data.bicubic_taps(n, s), idx_* [s n][6] int32 mirrored into [0, n),
+ * w_* [s n][6] fp64, rows first, then columns.  The 5-tap pass runs along x first (b in order), then along y (a in order); every product and sum is fp64, the result
+ * is rounded to fp32 once.  u5 is HOST memory: 5 doubles, passed to the kernel by value (u_i = exp(-i^2) / sum_j exp(-j^2): the 2-D kernel of backprojection.m:6-8
+ * is their outer product).  One launch per call, DASR_BP_UPD_TILE_H x DASR_BP_UPD_TILE_W samples of sr per workgroup.  d must not overlap sr.
+ *
+ * A null pointer, s outside {2, 3, 4}, H or W not a multiple of s, C or a side of the HR image over 65535: DASR_EINVAL, nothing is launched. */
+#define DASR_BP_RES_TILE_H 8
+#define DASR_BP_RES_TILE_W 32
+#define DASR_BP_UPD_TILE_H 16
+#define DASR_BP_UPD_TILE_W 64
+int dasr_bp_residual(const float* sr, const float* lr, int32_t C, int32_t H, int32_t W, int32_t s, const int32_t* idx_h, const double* w_h, const int32_t* idx_w,
+                     const double* w_w, float* d, void* stream);
+int dasr_bp_update(float* sr, const float* d, int32_t C, int32_t h, int32_t w, int32_t s, const int32_t* idx_h, const double* w_h, const int32_t* idx_w,
+                   const double* w_w, const double* u5, void* stream);
+
 /* ---- profiling session (bench.py `roofline`) -----------------------------------------------------------
  * Between dasr_prof_begin and dasr_prof_end every kernel launch of the library (up to `capacity`) carries its own start/stop
  * events on its launch stream (hipExtLaunchKernel: the dispatch's begin/end timestamps, what rocprofv3 --kernel-trace prints).
