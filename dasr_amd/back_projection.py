@@ -2,20 +2,16 @@
 
     python -m dasr_amd.back_projection --lr_dir LR --sr_dir results --out_dir results_20bp [--iters 20] [--num_workers 6]
 
-Every PNG file of --sr_dir is paired with the file of the same name in --lr_dir (main_bp.m:14-16).  The files are decoded on host threads (PIL), the BYTES are
-uploaded, and everything per pixel runs on the device: byte / 255 as planar fp32 (dasr_u8_to_planar, MATLAB's im2double), `iters` iterations of
+Every PNG file of --sr_dir is paired with the file of the same name in --lr_dir (main_bp.m:14-16).  The files are decoded on host threads (PIL, imgio.decode_ahead), the BYTES are
+uploaded, and everything per pixel runs on the device: byte / 255 as planar fp32 (imgio.planar_f32: dasr_u8_to_planar, MATLAB's im2double), `iters` iterations of
 backprojection.m (backproject.back_project), the clamp and rounding to bytes (metrics.tensor2img_device, MATLAB's imwrite of a double image).  The result is
 written as PNG under the same name in --out_dir.  Accepted input is 8-bit RGB; a missing partner or an SR size that is not 2, 3 or 4 times the LR size is a
 ValueError naming both files."""
 import argparse
 import os
-from collections import deque
-from concurrent.futures import ThreadPoolExecutor
 
-import torch
-
-from . import _lib, imgio, util
-from .backproject import DEFAULT_ITERS, SCALES, _stream, back_project
+from . import imgio, util
+from .backproject import DEFAULT_ITERS, SCALES, back_project
 
 
 def parse_args(argv=None):
@@ -49,15 +45,6 @@ def list_pairs(sr_dir, lr_dir):
     return pairs
 
 
-def _planar(a, device):
-    """decoded bytes [H, W, 3] -> [1, 3, H, W] fp32 in [0, 1] on the device (one byte per sample crosses)"""
-    H, W = a.shape[:2]
-    u8 = torch.from_numpy(a).to(device)
-    out = torch.empty((1, 3, H, W), dtype=torch.float32, device=device)
-    _lib.check(_lib.lib().dasr_u8_to_planar(u8.data_ptr(), H, W, H, W, out.data_ptr(), _stream()), 'dasr_u8_to_planar')
-    return out
-
-
 def main(argv=None):
     """returns the list of written paths, in the order of the sorted file names"""
     from . import metrics
@@ -67,26 +54,17 @@ def main(argv=None):
     pairs = list_pairs(o.sr_dir, o.lr_dir)
     device = imgio.device_of(None)
     util.mkdir(o.out_dir)
-    threads = max(1, min(imgio.MAX_DECODE_THREADS, int(o.num_workers)))
     written = []
 
     def load(sr_file, lr_file, _s):
         return imgio.decode_u8(sr_file), imgio.decode_u8(lr_file)
-    with ThreadPoolExecutor(max_workers=threads) as pool:
-        todo, ahead = iter(pairs), deque()
-        for _ in range(min(len(pairs), 2 * threads)):   # decoded pairs wait in host memory at most 2 x threads at a time
-            ahead.append(pool.submit(load, *next(todo)))
-        for sr_file, _lr_file, _s in pairs:
-            sr_u8, lr_u8 = ahead.popleft().result()
-            nxt = next(todo, None)
-            if nxt is not None:
-                ahead.append(pool.submit(load, *nxt))
-            out = back_project(_planar(sr_u8, device), _planar(lr_u8, device), o.iters)
-            img = metrics.tensor2img_device(out).cpu().numpy()   # HWC BGR bytes, as util.tensor2img gives them
-            path = os.path.join(o.out_dir, os.path.basename(sr_file))
-            util.save_img(img, path)
-            written.append(path)
-            print(os.path.basename(sr_file))
+    for (sr_u8, lr_u8), (sr_file, _lr_file, _s) in zip(imgio.decode_ahead(load, pairs, o.num_workers), pairs):
+        out = back_project(imgio.planar_f32(sr_u8, device, batch=True), imgio.planar_f32(lr_u8, device, batch=True), o.iters)
+        img = metrics.tensor2img_device(out).cpu().numpy()   # HWC BGR bytes, as util.tensor2img gives them
+        path = os.path.join(o.out_dir, os.path.basename(sr_file))
+        util.save_img(img, path)
+        written.append(path)
+        print(os.path.basename(sr_file))
     return written
 
 

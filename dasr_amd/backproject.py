@@ -13,7 +13,8 @@ import math
 import torch
 
 from . import _lib
-from .imgio import tap_table, up_tap_table
+from .engine import _stream
+from .imgio import down_table_ptrs, up_tap_table
 
 DEFAULT_ITERS = 20          # main_bp.m:7
 SCALES = (2, 3, 4)
@@ -54,10 +55,6 @@ def scale_of(sr_shape, lr_shape):
     return H // h
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _u5():
     """gaussian_u5 as the host array dasr_bp_update takes (made once)"""
     global _U5
@@ -67,9 +64,7 @@ def _u5():
 
 
 def _tables(H, W, s, device):
-    (jh, wh), (jw, ww) = tap_table(H, s, device), tap_table(W, s, device)
-    (uh, vh), (uw, vw) = up_tap_table(H // s, s, device), up_tap_table(W // s, s, device)
-    return [t.data_ptr() for t in (jh, wh, jw, ww)], [t.data_ptr() for t in (uh, vh, uw, vw)]
+    return down_table_ptrs(H, W, s, device), [t.data_ptr() for n in (H // s, W // s) for t in up_tap_table(n, s, device)]
 
 
 def _checked(sr, lr):

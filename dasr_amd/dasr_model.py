@@ -23,7 +23,7 @@ from .engine import BTensor, OpList, NULL_T, Tensor, _stream
 from .gan_nets import (NLayerDiscriminatorHIP, DiscriminatorVGG128HIP, VGGFeatureHIP, VGG_MEAN, VGG_STD, nlayer_d_spec, vgg128_spec,
                        vgg128_init_state_dict)
 from .init import kaiming_state_dict
-from .lpips import load_lpips, lpips_metric
+from .lpips import load_lpips
 from .models import BaseModel, AdamHIP, MultiStepLR, _define_G
 
 logger = logging.getLogger('base')
@@ -309,17 +309,9 @@ class DASR_Model(BaseModel):
             self._acc_snapshot = None
         return self.log_dict
 
-    def test(self, tsamples=False):
-        """inference on var_L (DASR_model.py:333-345; `chop`: quadrant inference, utils/util.py:87-147)"""
-        self.fake_H = self._generate(self.var_L)
-        if not tsamples:   # (the training-sample visuals show the generator's own output)
-            self._back_project()
-        if not tsamples and self.opt['val_lpips']:
-            self._eval_lpips()
-
-    def _eval_lpips(self):
-        """LPIPS of fake_H against the ground truth of the last feed_data (DASR_model.py:340-344)"""
-        self.LPIPS = lpips_metric(self.cri_fea_lpips, self.fake_H, self.var_H)
+    @property
+    def ground_truth(self):
+        return getattr(self, 'var_H', None) if getattr(self, 'needHR', True) else None
 
     def filter_high(self, x):
         """self.filter_high of the reference (DASR_model.py:58,61-66: FilterHigh(kernel_size=fs_kernel_size, gaussian = fs is not 'avgpool'),

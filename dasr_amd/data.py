@@ -26,7 +26,7 @@ import torch
 
 from . import _lib
 from .engine import _stream
-from .imgio import bicubic_taps, decode_u8, device_of, down4_weights, fill_crop_desc, image_header, load_resident, tap_table, u8_to_chw, upload
+from .imgio import bicubic_taps, decode_u8, device_of, down4_weights, down_table_ptrs, fill_crop_desc, image_header, load_resident, planar_f32, u8_to_chw, upload
 
 IMG_EXTENSIONS = ('.jpg', '.JPG', '.jpeg', '.JPEG', '.png', '.PNG', '.ppm', '.PPM', '.bmp', '.BMP')
 
@@ -407,10 +407,7 @@ class EvalFolderDataset:
             raise ValueError('{}: {} x {} is smaller than the scale {}'.format(path, H, W, crop_to))
         if torch.is_tensor(a):
             return a.to(self.device)[:, :Hc, :Wc].contiguous()[None]
-        u8 = torch.from_numpy(a).to(self.device)     # one byte per sample crosses to the device
-        out = torch.empty((1, 3, Hc, Wc), dtype=torch.float32, device=self.device)
-        _lib.check(_lib.lib().dasr_u8_to_planar(u8.data_ptr(), H, W, Hc, Wc, out.data_ptr(), _stream()), 'dasr_u8_to_planar')
-        return out
+        return planar_f32(a, self.device, window=(Hc, Wc), batch=True)     # one byte per sample crosses to the device
 
     def _read(self, path, crop_to=None):
         return self.to_device(self.decode(path), crop_to, path)
@@ -424,14 +421,13 @@ class EvalFolderDataset:
             raise ValueError('downsample takes one image, got a batch of %d' % n)
         if s not in (2, 3, 4) or H % s or W % s:
             raise NotImplementedError('LR images are made on the fly for scale 2, 3 or 4 and sizes that are multiples of it (got scale %d, %d x %d); provide LR files' % (s, H, W))
-        (jh, wh), (jw, ww) = tap_table(H, s, self.device), tap_table(W, s, self.device)
         tmp = self._tmp.get((c, H, W))
         if tmp is None:
             self._tmp = {(c, H, W): torch.empty((c, H // s, W), dtype=torch.float64, device=self.device)}   # one shape at a time: a folder of mixed sizes does not pile them up
             tmp = self._tmp[(c, H, W)]
         out = torch.empty((1, c, H // s, W // s), dtype=torch.float32, device=self.device)
-        _lib.check(_lib.lib().dasr_imresize_down(x.data_ptr(), c, H, W, s, jh.data_ptr(), wh.data_ptr(), jw.data_ptr(), ww.data_ptr(), tmp.data_ptr(), out.data_ptr(),
-                                                 _stream()), 'dasr_imresize_down')
+        _lib.check(_lib.lib().dasr_imresize_down(x.data_ptr(), c, H, W, s, *down_table_ptrs(H, W, s, self.device), tmp.data_ptr(), out.data_ptr(), _stream()),
+                   'dasr_imresize_down')
         return out
 
     def item(self, index):

@@ -3,8 +3,8 @@ codes/DSN/evaluate.py on the MI355X.
 
     python -m dasr_amd.dsn_evaluate --dir results/ --gt_dir gt/ [--border_crop 4] --lpips_alexnet alexnet.pth --lpips_lin alex.pth [--num_workers 6]
 
-The files are decoded on host threads (PIL), the BYTES are uploaded, and everything per pixel runs on the device: the planar re-layout
-(dasr_u8_to_planar, dasr_tensor2img_u8), the squared-error and channel sums, the 7 x 7 box SSIM (csrc/metrics.hip) and LPIPS on byte / 255 at any image
+The files are decoded on host threads (PIL, imgio.decode_ahead), the BYTES are uploaded, and everything per pixel runs on the device: the planar re-layout
+(metrics.u8_planes: imgio.planar_f32, dasr_tensor2img_u8), the squared-error and channel sums, the 7 x 7 box SSIM (csrc/metrics.hip) and LPIPS on byte / 255 at any image
 size from 31 x 31 (LPIPSAlexHIP.distance; dasr_lpips_s2d_any where a side is no multiple of 4).  One read-back per pair brings the integer and fp64 result
 words to the host, where the two PSNRs are formed in double (dasr_amd/metrics.py pair_metrics_u8).
 
@@ -15,8 +15,6 @@ which gives a wrong average).  The LPIPS weights come from --lpips_alexnet / --l
 network and every LPIPS value is labelled LPIPS(random)."""
 import argparse
 import os
-from collections import deque
-from concurrent.futures import ThreadPoolExecutor
 
 import torch
 
@@ -92,22 +90,13 @@ def main(argv=None):
     device = imgio.device_of(None)
     net = load_lpips({'path': {'lpips_alexnet': o.lpips_alexnet, 'lpips_lin': o.lpips_lin}, 'allow_random_perceptual': o.allow_random_perceptual}, device)
     label = lpips_label(net)
-    threads = max(1, min(imgio.MAX_DECODE_THREADS, int(o.num_workers)))
     rows, keys = [], ('psnr', 'psnr_col', 'ssim', 'lpips')
-    with ThreadPoolExecutor(max_workers=threads) as pool:
-        todo, ahead = iter(pairs), deque()
-        for _ in range(min(len(pairs), 2 * threads)):   # decoded pairs wait in host memory at most 2 x threads at a time
-            ahead.append(pool.submit(load_pair, *next(todo), border))
-        for file, gt_file in pairs:
-            img, gt = ahead.popleft().result()
-            nxt = next(todo, None)
-            if nxt is not None:
-                ahead.append(pool.submit(load_pair, *nxt, border))
-            if os.path.basename(file) != os.path.basename(gt_file):
-                print('WARNING: file and gt_file do not have the same name')
-            m = score_pair(net, img, gt, border, device)
-            rows.append(dict(m, file=file, gt_file=gt_file))
-            print('%s: PSNR %s PSNR_col %s SSIM %s %s %s' % (os.path.basename(file), m['psnr'], m['psnr_col'], m['ssim'], label, m['lpips']))
+    for (img, gt), (file, gt_file) in zip(imgio.decode_ahead(lambda f, g: load_pair(f, g, border), pairs, o.num_workers), pairs):
+        if os.path.basename(file) != os.path.basename(gt_file):
+            print('WARNING: file and gt_file do not have the same name')
+        m = score_pair(net, img, gt, border, device)
+        rows.append(dict(m, file=file, gt_file=gt_file))
+        print('%s: PSNR %s PSNR_col %s SSIM %s %s %s' % (os.path.basename(file), m['psnr'], m['psnr_col'], m['ssim'], label, m['lpips']))
     out = {k: sum(r[k] for r in rows) / len(rows) for k in keys}
     print('PSNR: ' + str(out['psnr']))
     print('PSNR_col: ' + str(out['psnr_col']))

@@ -1,14 +1,17 @@
-"""Host side of csrc/imgio.hip, shared by the SRN datasets (data.py) and the DSN datasets (dsn_data.py): the one PIL decode, the store of decoded bytes resident in
-device memory, the fp64 tap tables of MATLAB's bicubic with their device cache, and the descriptor upload in front of the batch-assembly launches.  Imports neither
-of the two dataset modules; both import this one."""
+"""Host side of csrc/imgio.hip, shared by the SRN datasets (data.py), the DSN datasets (dsn_data.py) and the folder CLIs: the one PIL decode and its decode-ahead loop,
+the hand-off of decoded bytes to a planar fp32 device image, the store of decoded bytes resident in device memory, the fp64 tap tables of MATLAB's bicubic with their
+device cache, and the descriptor upload in front of the batch-assembly launches.  Imports neither of the two dataset modules; both import this one."""
 import ctypes as C
+import itertools
 import math
+from collections import deque
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
 from . import _lib
-from .engine import ensure_runtime_ready
+from .engine import _stream, ensure_runtime_ready
 
 MAX_DECODE_THREADS = 16
 
@@ -35,6 +38,33 @@ def u8_to_chw(a):
     """decoded bytes [H, W, 3] -> CHW fp32 in [0, 1] (`to_tensor`: one correctly rounded division by 255, bit for bit np.float32(a) / 255.0; a permuted view,
     not contiguous)"""
     return torch.from_numpy(a).permute(2, 0, 1).float().div_(255.0)
+
+
+def planar_f32(a, device=None, window=None, batch=False):
+    """THE hand-off of decoded bytes: uint8 [H, W, 3], a numpy array (uploaded to `device`, None: the current GPU; one byte per sample crosses) or a device tensor -> the planar fp32 device
+    image [3, Hc, Wc] = byte / 255 correctly rounded (bit for bit u8_to_chw), `window` (Hc, Wc): that top-left window only (None: the whole image), `batch`: with a
+    leading axis of 1.  One dasr_u8_to_planar launch on the current stream."""
+    u8 = a if torch.is_tensor(a) else torch.from_numpy(a).to(device_of(device))
+    H, W = u8.shape[:2]
+    Hc, Wc = window or (H, W)
+    out = torch.empty(((1, 3, Hc, Wc) if batch else (3, Hc, Wc)), dtype=torch.float32, device=u8.device)
+    _lib.check(_lib.lib().dasr_u8_to_planar(u8.data_ptr(), H, W, Hc, Wc, out.data_ptr(), _stream()), 'dasr_u8_to_planar')
+    return out
+
+
+def decode_ahead(load, jobs, threads):
+    """yields load(*job) for every job, in order, from a pool of `threads` host threads (clamped to [1, MAX_DECODE_THREADS]) that runs ahead of the consumer: 2 x threads
+    jobs are submitted at the start, then one more behind every result taken from the queue, so at most 2 x threads results are decoded or wait in host memory next to
+    the one the consumer holds.  An exception of `load` surfaces at its item."""
+    threads = max(1, min(MAX_DECODE_THREADS, int(threads)))
+    with ThreadPoolExecutor(max_workers=threads) as pool:
+        todo = iter(jobs)
+        ahead = deque(pool.submit(load, *job) for job in itertools.islice(todo, 2 * threads))
+        while ahead:
+            result = ahead.popleft().result()
+            for job in itertools.islice(todo, 1):
+                ahead.append(pool.submit(load, *job))
+            yield result
 
 
 def device_of(device):
@@ -114,6 +144,12 @@ def tap_table(n_in, s, device):
         j, w = bicubic_taps(n_in, 1.0 / s)
         _TABLES[key] = (j.to(torch.int32).contiguous().to(device), w.contiguous().to(device))
     return _TABLES[key]
+
+
+def down_table_ptrs(H, W, s, device):
+    """the device pointers (row index, row weight, column index, column weight) of the tap_table pair of an H x W image shrunk by s, in the argument order of
+    dasr_imresize_down and dasr_bp_residual"""
+    return [t.data_ptr() for n in (H, W) for t in tap_table(n, s, device)]
 
 
 def up_tap_table(n_in, s, device):

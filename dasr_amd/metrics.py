@@ -1,6 +1,6 @@
 """Device-side image quality of the SRN validation / evaluation drivers (opt-in: top-level option `device_metrics: true`).
 
-What `test.evaluate` / `train.validate` otherwise do on the host with numpy (util.tensor2img, calculate_psnr, calculate_ssim, bgr2ycbcr;
+What `test.evaluate` / `train.validate` otherwise do on the host with numpy (train.sr_and_scores: util.tensor2img, then util.host_scores;
 reference codes/SRN/utils/util.py:180-204, :236-291, data/util.py:169-190) runs here on csrc/metrics.hip: the fp32 SR / HR images the trainer holds
 after test() are quantised to uint8 on the device, the squared-error sums (integer for RGB, fp64 for Y) and the fp64 SSIM means are formed there,
 and ONE small read-back per call brings them to the host, where PSNR is formed in double with util.calculate_psnr's formula.  Numerics: DESIGN.md.
@@ -8,20 +8,16 @@ and ONE small read-back per call brings them to the host, where PSNR is formed i
 Also the numbers of the folder evaluator (dasr_amd/dsn_evaluate.py; reference codes/DSN/evaluate.py:44-46, scikit-image's compare_psnr / compare_ssim) on two
 uint8 device images: pair_metrics_u8, with its own kernels for the 7 x 7 box SSIM and the channel sums.
 """
-import ctypes as C
 import logging
 import math
 
 import torch
 
-from . import _lib, util
+from . import _lib, imgio, util
+from .engine import _stream
 
 SSIM_WINDOW = 11
 _bufs = {}
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _as_batch(t):
@@ -75,23 +71,12 @@ def _psnr(sse, count):
 
 
 def _host_metrics(sr, hr, crop, ssim, y, min_max):
-    """the drivers' host sequence (test.py), image by image: where the device SSIM has no valid region the host function decides what happens"""
-    out = {'psnr': [], 'ssim': [], 'psnr_y': [], 'ssim_y': []}
-    c = crop
+    """the drivers' host sequence (util.host_scores), image by image: where the device SSIM has no valid region the host function decides what happens"""
+    out = {}
     for i in range(sr.shape[0]):
-        a, b = util.tensor2img(sr[i], min_max=min_max) / 255., util.tensor2img(hr[i], min_max=min_max) / 255.
-        a3, b3 = (a, b) if a.ndim == 3 else (a[:, :, None], b[:, :, None])
-        ca, cb = a3[c:a.shape[0] - c, c:a.shape[1] - c, :], b3[c:a.shape[0] - c, c:a.shape[1] - c, :]
-        out['psnr'].append(util.calculate_psnr(ca * 255, cb * 255))
-        if ssim:
-            out['ssim'].append(util.calculate_ssim(ca * 255, cb * 255))
-        if y and a.ndim == 3:
-            ay, by = util.bgr2ycbcr(a, only_y=True), util.bgr2ycbcr(b, only_y=True)
-            cay, cby = ay[c:a.shape[0] - c, c:a.shape[1] - c], by[c:a.shape[0] - c, c:a.shape[1] - c]
-            out['psnr_y'].append(util.calculate_psnr(cay * 255, cby * 255))
-            if ssim:
-                out['ssim_y'].append(util.calculate_ssim(cay * 255, cby * 255))
-    return {k: v for k, v in out.items() if v}
+        for k, v in util.host_scores(util.tensor2img(sr[i], min_max=min_max), util.tensor2img(hr[i], min_max=min_max), crop, ssim, y).items():
+            out.setdefault(k, []).append(v)
+    return out
 
 
 def batch_metrics(sr, hr, crop, ssim=True, y=True, min_max=(0, 1)):
@@ -160,17 +145,14 @@ def psnr_col_from_sums(sums_a, sums_b, pixels):
 
 def u8_planes(hwc):
     """decoded bytes on the device, uint8 [H, W, 3] -> (fp32 planar [3, H, W] = byte / 255 correctly rounded, uint8 planar [3, H, W]), both by kernels:
-    dasr_u8_to_planar, then dasr_tensor2img_u8 on its output (rint(float32(u / 255) * 255) == u for all 256 bytes, tests/test_evaluate_host.py)"""
+    dasr_u8_to_planar (imgio.planar_f32), then dasr_tensor2img_u8 on its output (rint(float32(u / 255) * 255) == u for all 256 bytes, tests/test_evaluate_host.py)"""
     if hwc.dtype != torch.uint8 or hwc.dim() != 3 or hwc.shape[2] != 3 or not hwc.is_cuda:
         raise TypeError('expected a uint8 [H, W, 3] device tensor, got %s %s on %s' % (hwc.dtype, tuple(hwc.shape), hwc.device))
-    hwc = hwc.contiguous()
     h, w = hwc.shape[:2]
-    L, st = _lib.lib(), _stream()
     with torch.cuda.device(hwc.device):
-        f = torch.empty((3, h, w), dtype=torch.float32, device=hwc.device)
+        f = imgio.planar_f32(hwc.contiguous())
         u = torch.empty((3, h, w), dtype=torch.uint8, device=hwc.device)
-        _lib.check(L.dasr_u8_to_planar(hwc.data_ptr(), h, w, h, w, f.data_ptr(), st), 'dasr_u8_to_planar')
-        _lib.check(L.dasr_tensor2img_u8(f.data_ptr(), 1, 3, h, w, 0.0, 1.0, None, u.data_ptr(), None, st), 'dasr_tensor2img_u8')
+        _lib.check(_lib.lib().dasr_tensor2img_u8(f.data_ptr(), 1, 3, h, w, 0.0, 1.0, None, u.data_ptr(), None, _stream()), 'dasr_tensor2img_u8')
     return f, u
 
 

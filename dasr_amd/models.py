@@ -178,10 +178,7 @@ class BaseModel:
     def current_metrics(self, crop):
         """PSNR / SSIM (and their Y forms for 3 channels) of image 0 of the last test() against the ground truth of the last feed_data, on the device:
         dict of floats 'psnr', 'ssim', 'psnr_y', 'ssim_y' (metrics.image_metrics)"""
-        hr = getattr(self, 'real_H', None)          # SRModel
-        if hr is None and getattr(self, 'needHR', True):
-            hr = getattr(self, 'var_H', None)       # DASR_Model
-        sr = self.fake_H
+        hr, sr = self.ground_truth, self.fake_H
         if hr is None or sr is None:
             raise RuntimeError('current_metrics needs test() on a batch that carried an HR image (feed_data was given no HR)')
         if hr.shape[1:] != sr.shape[1:]:
@@ -189,6 +186,8 @@ class BaseModel:
         return self._device_metrics().image_metrics(sr.detach()[:1], hr.detach()[:1], crop)
 
     # ---- inference ----------------------------------------------------------------------------------------------------------------
+    ground_truth = None   # a property of the trainers: the HR batch of the last feed_data, None when it carried none
+
     def _generate(self, x):
         """the generator as test() runs it on a batch x: netG.forward, inside the quadrant inference of util.forward_chop under `chop` (DASR_model.py:333-339,
         util.py:87-147).  The result is the caller's own (netG.forward returns a plan's output buffer, which the next forward of that shape overwrites)."""
@@ -206,6 +205,27 @@ class BaseModel:
             from .backproject import back_project
             self.fake_H = back_project(self.fake_H, self.var_L, n)
 
+    def _eval_lpips(self):
+        """LPIPS of fake_H against the ground truth of the last feed_data (SR_model.py:95-99, DASR_model.py:340-344); the metric network is loaded on first use
+        where the trainer did not build it"""
+        from .lpips import load_lpips, lpips_metric
+        if getattr(self, 'cri_fea_lpips', None) is None:
+            self.cri_fea_lpips = load_lpips(self.opt, self.device)
+        self.LPIPS = lpips_metric(self.cri_fea_lpips, self.fake_H, self.ground_truth)
+
+    def _finish_test(self):
+        """what test() and test_x8() end in: fake_H back-projected (option `back_projection`), then LPIPS under `val_lpips`"""
+        self._back_project()
+        if self.opt['val_lpips']:
+            self._eval_lpips()
+
+    def test(self, tsamples=False):
+        """inference on var_L (SR_model.py:87-93, DASR_model.py:333-345; `chop`: quadrant inference of util.py:87-147).  tsamples (the DASR trainer's training-sample
+        visuals, which show the generator's own output): nothing behind the generator"""
+        self.fake_H = self._generate(self.var_L)
+        if not tsamples:
+            self._finish_test()
+
     def test_x8(self):
         """geometric self-ensemble inference on var_L (SR_model.py:102-140), same contract as test(): sets fake_H [1, C, sH, sW] and, under `val_lpips`, LPIPS (the
         reference's test_x8 never computes it; here the drivers need no second code path).  The generator runs on the eight flips / transposes of the LR image,
@@ -220,9 +240,7 @@ class BaseModel:
         lr_a, lr_b = dihedral8(self.var_L[0])
         sr_a = self._generate(lr_a)   # (its own tensor: for a square image both batches run on the same plan)
         self.fake_H = dihedral8_mean(sr_a, self._generate(lr_b))
-        self._back_project()
-        if self.opt['val_lpips']:
-            self._eval_lpips()
+        self._finish_test()
 
     def get_network_description(self, network):
         n = network.params.total
@@ -517,19 +535,9 @@ class SRModel(BaseModel):
             self.check_finite()
         return self.log_dict
 
-    def test(self):
-        """inference on var_L (SR_model.py:87-93; `chop`: quadrant inference of DASR_model.py:333-339 / util.py:87-147)"""
-        self.fake_H = self._generate(self.var_L)
-        self._back_project()
-        if self.opt['val_lpips']:
-            self._eval_lpips()
-
-    def _eval_lpips(self):
-        """LPIPS of fake_H against the ground truth of the last feed_data (SR_model.py:95-99)"""
-        from .lpips import load_lpips, lpips_metric
-        if getattr(self, 'cri_fea_lpips', None) is None:
-            self.cri_fea_lpips = load_lpips(self.opt, self.device)
-        self.LPIPS = lpips_metric(self.cri_fea_lpips, self.fake_H, self.real_H)
+    @property
+    def ground_truth(self):
+        return getattr(self, 'real_H', None)
 
     def get_current_visuals(self, need_HR=True):
         out = OrderedDict()

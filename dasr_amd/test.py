@@ -1,9 +1,9 @@
 """`python -m dasr_amd.test -opt X.json` -- SRN inference / evaluation driver (reference: codes/SRN/test.py:17-138).
 
-For every dataset of the option file: feed_data -> test() -> get_current_visuals -> SR image saved under
+For every dataset of the option file: feed_data -> train.run_inference -> train.sr_and_scores -> SR image saved under
 <results_root>/<dataset name>/imgs, and, when HR is present, PSNR / SSIM on the `scale`-pixel-cropped uint8 images in RGB and on the
 Y channel, per image and averaged (same log lines as the reference).  `device_metrics: true` quantises the images and evaluates the four numbers on the
-GPU (dasr_amd/metrics.py) instead of with the numpy helpers of dasr_amd/util.py; absent, the host path is unchanged.  `chop: true` runs the quadrant inference.  `self_ensemble: true` replaces test() by test_x8(), the x8 geometric self-ensemble (SR_model.py:102-140), everything downstream unchanged.  `back_projection: true | N` back-projects every SR image onto its LR image (20 | N iterations, dasr_amd/backproject.py) before it is saved and scored.  `val_lpips: true` adds the
+GPU (dasr_amd/metrics.py) instead of with util.host_scores on get_current_visuals; absent, the host path is unchanged.  `chop: true` runs the quadrant inference.  `self_ensemble: true` replaces test() by test_x8(), the x8 geometric self-ensemble (SR_model.py:102-140), everything downstream unchanged.  `back_projection: true | N` back-projects every SR image onto its LR image (20 | N iterations, dasr_amd/backproject.py) before it is saved and scored.  `val_lpips: true` adds the
 LPIPS(alex) distance of the 8-bit images (test.py:88-128; weights from `path.lpips_alexnet` / `path.lpips_lin`, seeded when absent).
 `save_RealorFake` needs the discriminator visual, not available here: NotImplementedError.  Datasets: `mode: "LRHR"` (HR folder, LR folder or LR made by bicubic down-sampling) and `mode: "LR"` read image folders through data.EvalFolderDataset; `mode: "synthetic"` ships
 seeded LR/HR pairs; any iterable of the reference's batch dicts works through `main(loaders=...)`.
@@ -17,7 +17,7 @@ from collections import OrderedDict
 from . import options as option
 from . import util
 from .models import create_model
-from .train import BACK_PROJECTION_NOTE, SELF_ENSEMBLE_NOTE, create_dataset, setup_logger
+from .train import BACK_PROJECTION_NOTE, SELF_ENSEMBLE_NOTE, create_dataset, run_inference, setup_logger, sr_and_scores
 
 
 def evaluate(model, loader, opt, dataset_dir, logger, scale):
@@ -26,42 +26,21 @@ def evaluate(model, loader, opt, dataset_dir, logger, scale):
         need_HR = 'HR' in data
         model.feed_data(data, False)
         img_name = os.path.splitext(os.path.basename(data['LR_path'][0]))[0]
-        if opt['self_ensemble']:
-            model.test_x8()
-        else:
-            model.test()
-        dev = bool(opt['device_metrics'])
-        if dev:     # quantised on the device (BaseModel.current_sr_u8): the same bytes as tensor2img of the fp32 image
-            sr_img = model.current_sr_u8()
-        else:
-            visuals = model.get_current_visuals(need_HR=need_HR)
-            sr_img = util.tensor2img(visuals['SR'])
+        run_inference(model, opt)
+        sr_img, m, lpips = sr_and_scores(model, opt, need_HR, scale)   # `device_metrics`: quantised and scored on the GPU, the same bytes and numbers
         suffix = opt['suffix']
         util.save_img(sr_img, os.path.join(dataset_dir, img_name + (suffix or '') + '.png'))
         if not need_HR:
             logger.info(img_name)
             continue
-        c = scale
-        if dev:
-            m = model.current_metrics(c)
-            psnr, ssim = m['psnr'], m['ssim']
-        else:
-            gt_img = util.tensor2img(visuals['HR']) / 255.
-            sr_img = sr_img / 255.
-            csr, cgt = sr_img[c:-c, c:-c, :], gt_img[c:-c, c:-c, :]
-            psnr, ssim = util.calculate_psnr(csr * 255, cgt * 255), util.calculate_ssim(csr * 255, cgt * 255)
+        psnr, ssim = m['psnr'], m['ssim']
         res['psnr'].append(psnr)
         res['ssim'].append(ssim)
-        lpips = float(model.LPIPS if dev else visuals['LPIPS']) if opt['val_lpips'] else None      # test.py:88-100
-        if lpips is not None:
+        if lpips is not None:      # test.py:88-100
+            lpips = float(lpips)
             res['lpips'].append(lpips)
         if sr_img.ndim == 3 and sr_img.shape[2] == 3:
-            if dev:
-                psnr_y, ssim_y = m['psnr_y'], m['ssim_y']
-            else:
-                sr_y, gt_y = util.bgr2ycbcr(sr_img, only_y=True), util.bgr2ycbcr(gt_img, only_y=True)
-                psnr_y = util.calculate_psnr(sr_y[c:-c, c:-c] * 255, gt_y[c:-c, c:-c] * 255)
-                ssim_y = util.calculate_ssim(sr_y[c:-c, c:-c] * 255, gt_y[c:-c, c:-c] * 255)
+            psnr_y, ssim_y = m['psnr_y'], m['ssim_y']
             res['psnr_y'].append(psnr_y)
             res['ssim_y'].append(ssim_y)
             if lpips is not None:

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import options as option
+from . import util
 from .dist import DataParallelGroup, shard_minibatch
 from .models import create_model
 
@@ -99,9 +100,29 @@ SELF_ENSEMBLE_NOTE = 'self_ensemble: x8 self-ensemble inference is on (test_x8: 
 BACK_PROJECTION_NOTE = 'back_projection: every SR image is back-projected onto its LR image, {:d} iterations on the GPU (csrc/imgio.hip), before it is saved and scored'
 
 
+def run_inference(model, opt):
+    """the drivers' inference pass on the batch of the last feed_data: test_x8() under `self_ensemble` (the x8 geometric self-ensemble, same outputs), else test()"""
+    if opt['self_ensemble']:
+        model.test_x8()
+    else:
+        model.test()
+
+
+def sr_and_scores(model, opt, need_HR, crop, ssim=True, y=True):
+    """what the drivers take from the trainer after run_inference: (the SR image as uint8 HWC BGR / HW, the util.host_scores dict against the ground truth or None
+    without HR, LPIPS or None without `val_lpips`).  `device_metrics`: the image is quantised and the four numbers are formed on the GPU (BaseModel.current_sr_u8 /
+    current_metrics, dasr_amd/metrics.py, imported only then); absent: get_current_visuals and util.host_scores (`ssim`, `y`: what the host path evaluates)."""
+    if opt['device_metrics']:
+        sr_img, lpips = model.current_sr_u8(), (model.LPIPS if opt['val_lpips'] else None)
+        return sr_img, (model.current_metrics(crop) if need_HR else None), lpips
+    visuals = model.get_current_visuals(need_HR=need_HR)
+    sr_img = util.tensor2img(visuals['SR'])
+    scores = util.host_scores(sr_img, util.tensor2img(visuals['HR']), crop, ssim, y) if 'HR' in visuals else None
+    return sr_img, scores, (visuals['LPIPS'] if opt['val_lpips'] else None)
+
+
 def validate(model, val_set, opt, current_step, logger):
     """validation pass of codes/SRN/train.py:174-235: test() per image, SR image saved, PSNR on the `scale`-pixel-cropped uint8 images"""
-    from . import util
     avg_psnr, avg_lpips, idx = 0.0, 0.0, 0
     for val_data in val_set:
         idx += 1
@@ -109,29 +130,17 @@ def validate(model, val_set, opt, current_step, logger):
         img_dir = os.path.join(opt['path']['val_images'], img_name)
         util.mkdir(img_dir)
         model.feed_data(val_data, False)
-        if opt['self_ensemble']:   # x8 geometric self-ensemble (BaseModel.test_x8), same outputs as test()
-            model.test_x8()
-        else:
-            model.test()
-        dev = bool(opt['device_metrics'])   # image quantised and PSNR formed on the GPU (dasr_amd/metrics.py); absent: the host path below
-        if dev:
-            sr_img, lpips = model.current_sr_u8(), (model.LPIPS if opt['val_lpips'] else None)
-        else:
-            visuals = model.get_current_visuals()
-            sr_img, lpips = util.tensor2img(visuals['SR']), (visuals['LPIPS'] if opt['val_lpips'] else None)
+        run_inference(model, opt)
+        # `device_metrics`: image quantised and PSNR formed on the GPU (dasr_amd/metrics.py); absent: on the host, where PSNR is all that is evaluated
+        sr_img, scores, lpips = sr_and_scores(model, opt, 'HR' in val_data, opt['scale'], ssim=False, y=False)
         log_info = '{}'.format(val_data['HR_path'][0].split('/')[-1])
         if opt['val_lpips']:      # train.py:194-197
             avg_lpips += float(lpips)
             log_info += '         {}:{:.3f}'.format(model.lpips_label, float(lpips))
         logger.info(log_info)
         util.save_img(sr_img, os.path.join(img_dir, '{:s}_{:d}.png'.format(img_name, current_step)))
-        if dev:
-            if 'HR' in val_data:
-                avg_psnr += model.current_metrics(opt['scale'])['psnr']
-        elif 'HR' in visuals:
-            gt_img = util.tensor2img(visuals['HR'])
-            c = opt['scale']
-            avg_psnr += util.calculate_psnr((sr_img / 255.)[c:-c, c:-c, :] * 255, (gt_img / 255.)[c:-c, c:-c, :] * 255)
+        if scores is not None:
+            avg_psnr += scores['psnr']
     avg_psnr = avg_psnr / max(idx, 1)
     logger.info('# Validation # PSNR: {:.4e}'.format(avg_psnr))
     if opt['val_lpips']:

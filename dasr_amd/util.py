@@ -12,6 +12,9 @@ import os
 import numpy as np
 import torch
 
+from . import _lib
+from .engine import _stream
+
 
 def mkdir(path):
     os.makedirs(path, exist_ok=True)
@@ -129,6 +132,23 @@ def calculate_ssim(img1, img2):
     raise ValueError('Wrong input image dimensions.')
 
 
+def host_scores(sr_img, gt_img, crop, ssim=True, y=True):
+    """THE host scoring of the drivers (codes/SRN/test.py:72-86) of two uint8 images as tensor2img returns them (HWC BGR or HW), `crop` pixels cut from every side:
+    dict of 'psnr', 'ssim' (if `ssim`) and, for three channels, 'psnr_y' (if `y`) and 'ssim_y' (if both).  The reference's arithmetic order: / 255 before the crop,
+    * 255 after it.  A cropped side under the 11-pixel window: numpy's ValueError out of calculate_ssim."""
+    a, b = sr_img / 255., gt_img / 255.
+    region = (slice(crop, a.shape[0] - crop), slice(crop, a.shape[1] - crop))
+    out = {'psnr': calculate_psnr(a[region] * 255, b[region] * 255)}
+    if ssim:
+        out['ssim'] = calculate_ssim(a[region] * 255, b[region] * 255)
+    if y and a.ndim == 3 and a.shape[2] == 3:
+        ay, by = bgr2ycbcr(a, only_y=True)[region] * 255, bgr2ycbcr(b, only_y=True)[region] * 255
+        out['psnr_y'] = calculate_psnr(ay, by)
+        if ssim:
+            out['ssim_y'] = calculate_ssim(ay, by)
+    return out
+
+
 def forward_chop(img, scale, model, shave=20, min_size=160000):
     """Inference on four overlapping quadrants (recursively while a quadrant has >= min_size pixels), outputs stitched without the
     `shave` overlap.  `model` maps [n,3,h,w] -> [n,3,h*scale,w*scale]; the quadrants of one level are run as one batch of 4."""
@@ -190,23 +210,21 @@ def dihedral8_mean_reference(srs):
 
 def dihedral8(x):
     """device: planar fp32 image [C, H, W] -> ([4, C, H, W] members 0..3, [4, C, W, H] members 4..7), one launch (dasr_dihedral8)"""
-    from . import _lib
     x = x.contiguous().float()
     C_, H, W = x.shape
     a = torch.empty((4, C_, H, W), dtype=torch.float32, device=x.device)
     b = torch.empty((4, C_, W, H), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().dasr_dihedral8(x.data_ptr(), C_, H, W, a.data_ptr(), b.data_ptr(), torch.cuda.current_stream().cuda_stream), 'dihedral8')
+    _lib.check(_lib.lib().dasr_dihedral8(x.data_ptr(), C_, H, W, a.data_ptr(), b.data_ptr(), _stream()), 'dihedral8')
     return a, b
 
 
 def dihedral8_mean(sr_a, sr_b):
     """device: the SR batches of dihedral8's two outputs, [4, C, H, W] and [4, C, W, H] -> their inverse-transformed mean [1, C, H, W], one launch with a
     fixed order of the adds (dasr_dihedral8_mean)"""
-    from . import _lib
     n, C_, H, W = sr_a.shape
     if n != 4 or tuple(sr_b.shape) != (4, C_, W, H):
         raise ValueError('dihedral8_mean: expected [4, C, H, W] and [4, C, W, H], got %s and %s' % (tuple(sr_a.shape), tuple(sr_b.shape)))
     sr_a, sr_b = sr_a.contiguous().float(), sr_b.contiguous().float()
     out = torch.empty((1, C_, H, W), dtype=torch.float32, device=sr_a.device)
-    _lib.check(_lib.lib().dasr_dihedral8_mean(sr_a.data_ptr(), sr_b.data_ptr(), C_, H, W, out.data_ptr(), torch.cuda.current_stream().cuda_stream), 'dihedral8_mean')
+    _lib.check(_lib.lib().dasr_dihedral8_mean(sr_a.data_ptr(), sr_b.data_ptr(), C_, H, W, out.data_ptr(), _stream()), 'dihedral8_mean')
     return out
