@@ -682,6 +682,9 @@ dasr_red dasr_red_scratch(const void* key_acc, hipStream_t s, unsigned nblocks, 
 }
 
 // ---- profiling session (see DASR_LAUNCH in common.h) ------------------------------------------------------------------------
+// A record carries the kind, the time-bucket tag and (on the op's first launch) the flops / bytes of the op dasr_run_ops is dispatching on this thread.
+// Rule: a launch made OUTSIDE dasr_run_ops -- a plain entry point such as dasr_adam, dasr_fill_f32, dasr_add_flat -- records kind 0, bucket 0, no flops
+// and no bytes: dasr_run_ops clears the three thread-locals below when it returns, on success and on failure.
 namespace {
 struct ProfRec {
     hipEvent_t e0, e1;
@@ -690,12 +693,19 @@ struct ProfRec {
     int op;
 };
 ProfRec* g_prof = nullptr;
-int g_prof_cap = 0;
+int g_prof_alloc = 0;   // records of g_prof that have their events (only ever grows)
+int g_prof_cap = 0;     // capacity of the open (or last) session, <= g_prof_alloc
 std::atomic<int> g_prof_n{0};
 std::atomic<bool> g_prof_on{false};
 // algorithmic work of the op being dispatched (consumed by its first launch); per enqueue thread (dasr_run_ops_mt)
 thread_local double g_prof_flops = 0.0, g_prof_bytes = 0.0;
 thread_local int g_prof_op = 0;
+struct ProfOpScope {   // dasr_run_ops: whatever its last op was, nothing of it outlives the call
+    ~ProfOpScope() {
+        g_prof_flops = g_prof_bytes = 0.0;
+        g_prof_op = 0;
+    }
+};
 char g_prof_filter[128] = {0};   // non-empty: only launches whose tag contains it get events (dasr_prof_filter)
 }  // namespace
 
@@ -729,16 +739,17 @@ extern "C" int dasr_prof_filter(const char* substr) {
 
 extern "C" int dasr_prof_begin(int32_t capacity) {
     if (capacity <= 0) return DASR_EINVAL;
-    if (capacity > g_prof_cap) {
+    if (capacity > g_prof_alloc) {
         ProfRec* np = (ProfRec*)realloc(g_prof, sizeof(ProfRec) * (size_t)capacity);
         if (!np) return DASR_EINVAL;
         g_prof = np;
-        for (int i = g_prof_cap; i < capacity; ++i) {
+        for (int i = g_prof_alloc; i < capacity; ++i) {
             HIP_TRY(hipEventCreate(&g_prof[i].e0));
             HIP_TRY(hipEventCreate(&g_prof[i].e1));
-            g_prof_cap = i + 1;
+            g_prof_alloc = i + 1;
         }
     }
+    g_prof_cap = capacity;   // (not the largest capacity ever asked for: a session after a larger one holds what IT asked for)
     g_prof_n.store(0);
     g_prof_on.store(true);
     return 0;
@@ -763,6 +774,7 @@ extern "C" int dasr_prof_end(int32_t max_out, float* us_out, double* flops_out, 
 
 extern "C" int dasr_run_ops(const dasr_op* ops, int32_t n, void* stream0) {
     void* stream = stream0;  // DASR_OP_SET_STREAM redirects the following ops
+    ProfOpScope prof_scope;   // a launch behind this call belongs to no op (see the profiling section)
     for (int k = 0; k < n; ++k) {
         const dasr_op& o = ops[k];
         int rc = 0;

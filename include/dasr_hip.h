@@ -784,7 +784,9 @@ int dasr_bp_update(float* sr, const float* d, int32_t C, int32_t h, int32_t w, i
  * dasr_prof_end synchronises the device and returns, per launch in issue order: duration in microseconds, the algorithmic
  * flops / bytes of the op it belongs to (dasr_op.flops / .bytes, attributed to the op's first launch), the op kind (bits 0-7; bits 8-15: the
  * plan builder's time-bucket tag dasr_op.i[7], which no kernel reads) and a
- * static string naming the kernel variant.  Returns the number of records written (<= max_out) or a negative error. */
+ * static string naming the kernel variant.  Returns the number of records written (<= max_out) or a negative error.
+ * A launch made outside dasr_run_ops (a plain entry point: dasr_adam, dasr_fill_f32, dasr_add_flat, ...) records kind 0, bucket 0, no flops and no
+ * bytes, whatever list ran before it on the thread.  `capacity` is that of the session it opens, whatever earlier sessions asked for; <= 0: DASR_EINVAL. */
 int dasr_prof_begin(int32_t capacity);
 int dasr_prof_end(int32_t max_out, float* us_out, double* flops_out, double* bytes_out, int32_t* op_out, const char** tag_out);
 /* Restricts the NEXT profiling sessions to launches whose tag (kernel name / launcher signature) contains `substr` (NULL or "": every launch again).  A session over
