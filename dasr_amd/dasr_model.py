@@ -19,7 +19,7 @@ import torch
 
 from . import _lib
 from ._lib import make_op
-from .engine import BTensor, OpList, NULL_T, Tensor, _stream
+from .engine import BTensor, OpList, NULL_T, Tensor, _stream, set_reduce_scale
 from .gan_nets import (NLayerDiscriminatorHIP, DiscriminatorVGG128HIP, VGGFeatureHIP, VGG_MEAN, VGG_STD, nlayer_d_spec, vgg128_spec,
                        vgg128_init_state_dict)
 from .init import kaiming_state_dict
@@ -579,11 +579,5 @@ class _StepPlan:
         self.ds_step = sstep
 
     def set_d_grad_scale(self, scale):
-        for ol in (self.d_step, self.ds_step):
-            for o in ol.ops:
-                if o.op == _lib.OP_WGRAD_REDUCE and o.get('scale') != scale:
-                    o.set('scale', scale)
-                    ol._arr = None
-                if o.op == _lib.OP_BNORM_BWD and o.get('pscale') != scale:   # dgamma / dbeta of the BatchNorm layers
-                    o.set('pscale', scale)
-                    ol._arr = None
+        """(the BatchNorm backward ops of these lists come from bwd_full: every one writes dgamma / dbeta and takes the scale)"""
+        return set_reduce_scale((self.d_step, self.ds_step), scale)

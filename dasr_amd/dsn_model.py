@@ -28,7 +28,7 @@ import torch
 from . import _lib
 from ._lib import make_op
 from .engine import (BTensor, ParamStore, PackRegistry, OpList, WgradGroup, WgradGroup3, Workspace, conv_op, ceil_div, Tensor,
-                     ensure_runtime_ready, _stream)
+                     ensure_runtime_ready, _stream, patch, set_reduce_scale)
 from .gan_nets import NLayerDiscriminatorHIP, BatchNormDiscriminatorHIP, VGGFeatureHIP, VGG16_CFG, fsd_spec, dsn_nld_spec, fold_batchnorm_fsd
 from .models import AdamHIP
 from .dasr_model import gaussian_kernel2d, vgg_random_state_dict, _nview, _ragan_ops
@@ -273,10 +273,7 @@ class _GPlan:
         def wg(key, g, inp, cout, cin, hi, wi, ho, wo, stride=1):
             grp = WgradGroup(3, stride)
             grp.add_conv(g.view, True, g.planes, inp.view, True, inp.planes, cout, cin, hi, wi, ho, wo, N, P.off(key + 'weight'), P.off(key + 'bias'))
-            grp.finalize(self.ws, dev)
-            for op in grp.ops(G):
-                b.add(op)
-            b.keep.append(grp)
+            grp.emit(b, self.ws, dev, G)
 
         def prelu_grad(key, y, gx, h, w, f16=False):
             o = make_op(_lib.OP_PRELU_GRAD, y=y.view(), gx=gx.view(), N=N, C=64, H=h, W=w, slope=sp(key), scratch256=self.scratch.data_ptr(),
@@ -317,7 +314,7 @@ class _GPlan:
         wgrp = None
         if b16 and nb:
             wgrp = WgradGroup3()
-            wgrp.f16, wgrp.g_scale, wgrp.flops = True, self.gscale, 0.0
+            wgrp.f16, wgrp.g_scale = True, self.gscale
 
         def wg16_part(key, g16, inp16):
             """weight gradient of a 64 -> 64 conv from the f16 shadows (g16 holds gscale * dL/dy) as one part of the grouped launch: the 64 input
@@ -369,10 +366,7 @@ class _GPlan:
             b.add(self._prelu_final)
             b.keep += [self.prelu_part, self.prelu_slopes, self.prelu_dsts]
         if wgrp is not None:   # all 2 nb residual-block weight gradients: one launch of 2 nb parts, one reduce
-            wgrp.finalize(self.ws, dev)
-            for op in wgrp.ops(G):
-                b.add(op)
-            b.keep.append(wgrp)
+            wgrp.emit(b, self.ws, dev, G)
         # s[0] = PReLU(conv_in(x)): apply PReLU' to dL/ds0, then the input conv's weight gradient
         b.add(make_op(_lib.OP_AXPBY, x=gs.view(), a=1.0, N=N, C=64, H=H, W=W, out_f32=self.g_h.view(), gamma=1.0, mask=self.s[0].view(), slope=0.25,
                       slope_ptr=sp('block_input.1.weight')))
@@ -382,14 +376,11 @@ class _GPlan:
         self.ws.finalize()
 
     def set_grad_scale(self, scale):
-        for o in self.bwd.ops:
-            if o.op == _lib.OP_WGRAD_REDUCE:
-                o.set('scale', scale)
+        set_reduce_scale([self.bwd], scale)
         for o in self._prelu_ops:
-            o.set('scale', scale)
+            patch(o, scale=scale)
         if getattr(self, '_prelu_final', None) is not None:   # (the fused form: data-parallel factor x 1 / pre-scale of the 16-bit backward)
-            self._prelu_final.set('scale', scale / self.gscale)
-        self.bwd._arr = None
+            patch(self._prelu_final, scale=scale / self.gscale)
 
 
 def symmetry_code(k_rot, flip_rows, flip_cols):
@@ -893,10 +884,7 @@ class _GradPenaltyPlan:
             grp.add_conv(g0.view, True, g0.planes, x0.view, True, x0.planes, L['cout'], L['cin'], hi, wi, ho, wo, N, P.off(L['key'] + 'weight'),
                          P.off(L['key'] + 'bias') if (bias and L['bias']) else None, pad=L['pad'], f16=net.prec == 4, g_scale=GS if net.prec == 4 else 0.0,
                          more_pairs=[(gg.view, xx.view) for gg, xx in more])
-            grp.finalize(self.ws, dev)
-            for op in grp.ops(self.grad.data_ptr()):
-                ops.add(op)
-            ops.keep.append(grp)
+            grp.emit(ops, self.ws, dev, self.grad.data_ptr())
 
         i = nl - 1
         wgrad(i, [(gz, adot[i - 1])], bias=False)     # the last conv's bias does not enter the directional derivative
@@ -1097,13 +1085,7 @@ class _DSNPlan:
     def set_grad_scale(self, scale):
         self.scale = scale
         self.g.set_grad_scale(scale)
-        for ol in (self.d_bwd, self.g_bwd) + ((self.gp.ops,) if self.gp is not None else ()):
-            for o in ol.ops:
-                if o.op == _lib.OP_WGRAD_REDUCE:
-                    o.set('scale', scale)
-                elif (o.op == _lib.OP_BNORM_BWD and o.get('dgamma')) or o.op == _lib.OP_BNORM_SECOND:   # dgamma / dbeta of a BatchNorm discriminator
-                    o.set('pscale', scale)
-            ol._arr = None
+        set_reduce_scale((self.d_bwd, self.g_bwd) + ((self.gp.ops,) if self.gp is not None else ()), scale)   # (with dgamma / dbeta of a BatchNorm discriminator)
 
 
 DDM_RF = 17  # receptive field of the reference's conv table [[5,1,2]] * 4 for FSD (create_dataset_modified.py:120-121)

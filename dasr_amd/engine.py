@@ -181,11 +181,49 @@ class PackRegistry:
 
 
 # --------------------------------------------------------------------------------------------------
+_GEN = 0   # bumped by patch(): the ctypes image of every OpList built before it is stale
+_CONV_FIELDS = frozenset(n for n, _ in ConvParams._fields_)
+
+
+def patch(op, **args):
+    """Change arguments of an op AFTER recording: the one way to do it.  An Op object may sit in several lists (OpList.extend / slice), each with
+    a ctypes image of its own; the generation bump makes every list rebuild its image before it runs next.  Names: ConvParams fields for
+    OP_CONV, OP_ARGS names (what Op.set takes) for every other kind, 'tag' for both."""
+    global _GEN
+    for name, value in args.items():
+        if op.op == _lib.OP_CONV and name != 'tag':
+            if name not in _CONV_FIELDS:
+                raise TypeError('dasr_conv_params has no field %r' % name)
+            setattr(op.conv, name, value)
+        else:
+            op.set(name, value)
+    _GEN += 1
+
+
+def set_reduce_scale(lists, scale):
+    """fold the data-parallel 1 / world into every gradient that leaves the op lists `lists`: `scale` of the weight-gradient reductions, `pscale` of
+    the BatchNorm backward ops that write dgamma / dbeta and of the second-order BatchNorm ops.  True if anything changed."""
+    scale = C.c_float(scale).value   # what the op stores: a scale that is no fp32 number must not read as changed every step
+    changed = False
+    for ol in lists:
+        for o in ol.ops:
+            if o.op == _lib.OP_WGRAD_REDUCE:
+                name = 'scale'
+            elif (o.op == _lib.OP_BNORM_BWD and o.get('dgamma')) or o.op == _lib.OP_BNORM_SECOND:
+                name = 'pscale'
+            else:
+                continue
+            if o.get(name) != scale:
+                patch(o, **{name: scale})
+                changed = True
+    return changed
+
+
 class OpList:
     def __init__(self):
         self.ops = []
         self.keep = []  # device tables that must outlive the list
-        self._arr = None
+        self._arr, self._gen = None, -1   # ctypes image of ops and the patch generation it was built at (_image)
 
     def add(self, o):
         self.ops.append(o)
@@ -196,20 +234,37 @@ class OpList:
         self.keep.extend(other.keep)
         self._arr = None
 
+    def slice(self, lo=0, hi=None):
+        """a list of the SAME Op objects ops[lo:hi] (patch() reaches them in both).  It does not take `keep`: hold this list while the slice is in use."""
+        ol = OpList()
+        ol.ops = self.ops[lo:hi]
+        return ol
+
+    def pop(self, idx):
+        """remove and return op `idx`"""
+        self._arr = None
+        return self.ops.pop(idx)
+
     def tag(self, bucket, start=0, end=None):
         """time-bucket tag (argument 'tag' of every op, read by no kernel; bench.py's per-bucket table) on the not yet tagged ops [start, end)"""
         for o in self.ops[start:end]:
             if o.get('tag') == 0:
-                o.set('tag', bucket)
-        self._arr = None
+                patch(o, tag=bucket)
         return self
 
     def set(self, idx, name, value):
-        """patch argument `name` of op `idx` in place (recorded list AND its ctypes image): for the few arguments that change from call to
-        call while the plan stays recorded (e.g. the random symmetry of DSN --lpips_rot_flip)"""
+        """patch argument `name` of op `idx` in place (recorded list AND its ctypes image, no rebuild of any list): for the few arguments that change
+        from call to call while the plan stays recorded (e.g. the random symmetry of DSN --lpips_rot_flip).  Only valid for an op that THIS list alone
+        holds: the image of another list with the same Op object keeps the old value.  Everything else goes through patch()."""
         self.ops[idx].set(name, value)
         if self._arr is not None:
             self._arr[idx].set(name, value)
+
+    def _image(self):
+        """the ctypes array dasr_run_ops reads, rebuilt when the sequence changed or an op was patched since it was built"""
+        if self._arr is None or self._gen != _GEN:
+            self._arr, self._gen = (Op * len(self.ops))(*self.ops), _GEN
+        return self._arr
 
     def safe_cuts(self, chunk):
         """[0, c1, c2, ..., len]: chunk boundaries of about `chunk` ops at which no stream redirect (OP_SET_STREAM) is open"""
@@ -231,13 +286,11 @@ class OpList:
         """enqueue ops[lo:hi] on the current stream"""
         if not self.ops:
             return
-        if self._arr is None:
-            self._arr = (Op * len(self.ops))(*self.ops)
         hi = len(self.ops) if hi is None else min(hi, len(self.ops))
         if hi <= lo:
             return
         L = _lib.lib()
-        rc = L.dasr_run_ops(C.c_void_p(C.addressof(self._arr) + lo * C.sizeof(Op)), hi - lo, _stream())
+        rc = L.dasr_run_ops(C.c_void_p(C.addressof(self._image()) + lo * C.sizeof(Op)), hi - lo, _stream())
         if rc != 0:
             k = L.dasr_last_failed_op() + lo
             raise _lib.DasrHipError('dasr_run_ops: op #%d (kind %d) failed with code %d' % (k, self.ops[k].op if 0 <= k < len(self.ops) else -1, rc))
@@ -266,10 +319,7 @@ def run_parallel(lists, streams):
     if len(lists) == 1 or os.environ.get('DASR_ENQ', 'mt') == 'chunk' or torch.cuda.is_current_stream_capturing():
         return run_interleaved(lists, streams)
     n = len(lists)
-    for l in lists:
-        if l._arr is None:
-            l._arr = (Op * len(l.ops))(*l.ops)
-    ptrs = (C.c_void_p * n)(*[C.addressof(l._arr) for l in lists])
+    ptrs = (C.c_void_p * n)(*[C.addressof(l._image()) for l in lists])
     cnts = (C.c_int32 * n)(*[len(l.ops) for l in lists])
     sts = (C.c_void_p * n)(*[st.cuda_stream for st in streams])
     L = _lib.lib()
@@ -348,12 +398,31 @@ class ConvChain:
             raise RuntimeError('conv chain: device error word %d (bit 1: a neighbour wait gave up)' % e)
 
 
-class WgradGroup:
+class _WgradEmit:
+    """what the two weight-gradient groups share: the operand format of the launch and the way into an op list"""
+
+    def __init__(self):
+        self.parts = []
+        self.f16, self.g_scale = False, 0.0   # f16 operands, the gradient pre-scaled by the power of two g_scale (the reduce op undoes it)
+        self.flops = 0.0                      # algorithmic FLOPs of the launch (bench.py)
+        self.ppu = 0
+
+    def emit(self, ops, workspace, device, grad_ptr, **finalize_kw):
+        """finalize(workspace, device, **finalize_kw), append the [wgrad, reduce] ops to the OpList `ops` and keep the group alive with it"""
+        self.finalize(workspace, device, **finalize_kw)
+        pair = self.ops(grad_ptr)
+        for o in pair:
+            ops.add(o)
+        ops.keep.append(self)
+        return pair
+
+
+class WgradGroup(_WgradEmit):
     """Parts of one wgrad launch (same kernel size / stride) + the matching reduce table."""
 
     def __init__(self, kh, stride):
+        super().__init__()   # parts: (WgradPart, WgradReducePart | None, variants)
         self.kh, self.stride = kh, stride
-        self.parts = []  # (WgradPart, WgradReducePart)
 
     def add_conv(self, g, g_f32, g_planes_total, inp, in_f32, in_planes_total, cout, cin, Hin, Win, Hout, Wout, N,
                  dst_w_off, dst_b_off, pad=None, ups=0, f16=False, g_scale=0.0, split=None, more_pairs=()):
@@ -366,12 +435,13 @@ class WgradGroup:
         of the DSN's --wgan penalty: dW = adj_z (x) a + adj_zdot (x) adot); same mechanism, the bias partials come from the first pair only."""
         assert not f16 or (g_f32 and in_f32)
         assert split is None or f16
-        self.f16 = bool(f16) or getattr(self, 'f16', False)
-        self.g_scale = float(g_scale) if f16 and g_scale else getattr(self, 'g_scale', 0.0)
+        self.f16 = bool(f16) or self.f16
+        if f16 and g_scale:
+            self.g_scale = float(g_scale)
         ntaps = self.kh * self.kh
         tpp = ntaps if ntaps <= 16 else 10  # WCfg::TAPS_PER_PART
         self.tpp = tpp
-        self.flops = getattr(self, 'flops', 0.0) + 2.0 * N * Hout * Wout * ntaps * cin * cout
+        self.flops += 2.0 * N * Hout * Wout * ntaps * cin * cout
         pad = (self.kh - 1) // 2 if pad is None else pad
         cin_pad = ceil_div(cin, 16) * 16
         variants = ([(g, inp)] if split is None else [(g, inp), (g, split[1]), (split[0], inp)]) + list(more_pairs)
@@ -438,9 +508,9 @@ class WgradGroup:
         """[wgrad, reduce] ops; the workspace pointer is patched in by Workspace.finalize()."""
         f32s = set((p[0].g_f32, p[0].in_f32) for p in self.parts)
         assert f32s in ({(0, 0)}, {(1, 1)}), 'a wgrad group must be all-bf16 or all-f32'
-        a = make_op(_lib.OP_WGRAD, flops=float(getattr(self, 'flops', 0.0)), parts_dev=self.w_dev.data_ptr(), nparts=len(self.parts), nsplit=self.nsplit,
-                    kh=self.kh, stride=self.stride, f32=self.parts[0][0].g_f32 | (2 if getattr(self, 'f16', False) else 0))
-        gs = getattr(self, 'g_scale', 0.0)
+        a = make_op(_lib.OP_WGRAD, flops=float(self.flops), parts_dev=self.w_dev.data_ptr(), nparts=len(self.parts), nsplit=self.nsplit,
+                    kh=self.kh, stride=self.stride, f32=self.parts[0][0].g_f32 | (2 if self.f16 else 0))
+        gs = self.g_scale
         b = make_op(_lib.OP_WGRAD_REDUCE, parts_dev=self.r_dev.data_ptr(), nparts=self.n_red, grad_flat=grad_ptr, scale=scale,
                     # few_splits: one reduce workgroup per output channel
                     few_splits=1 if (self.tpp <= 16 and all(rp is None or rp.nsplit <= 4 for _, rp, _ in self.parts)) else 0,
@@ -449,14 +519,11 @@ class WgradGroup:
         return [a, b]
 
 
-class WgradGroup3:
+class WgradGroup3(_WgradEmit):
     """Parts of one 6-wave 3x3 wgrad launch (csrc/wgrad.hip, wgrad3_kernel): a part = one 64-channel input block x up
-    to three consecutive 32-oc tiles of a gradient tensor; every (part, oc tile) has its own reduce descriptor."""
+    to three consecutive 32-oc tiles of a gradient tensor; every (part, oc tile) has its own reduce descriptor.  parts: (WgradPart, [(ot, dict)])"""
 
     kh, stride = 3, 1
-
-    def __init__(self):
-        self.parts = []   # (WgradPart, [(ot, dict)])
 
     def add_block(self, g_view, g_planes, in_view, in_planes, n_ctiles, Hin, Win, Hout, Wout, N, tiles, want_bias, f32=False, ups=0):
         """tiles: per oc tile of the part: dict(dst_w_off, dst_b_off|None, cout, cin, oc0, c0, n_ctiles) or None (unused tile)"""
@@ -509,10 +576,9 @@ class WgradGroup3:
         self.r_dev = torch.frombuffer(bytearray(bytes(ra)), dtype=torch.uint8).to(device)
 
     def ops(self, grad_ptr, scale=1.0):
-        f16 = getattr(self, 'f16', False)   # 16-bit f16 tensors (gradient pre-scaled by g_scale): f16 MFMA, reduce scale x 1 / g_scale
-        a = make_op(_lib.OP_WGRAD, flops=float(getattr(self, 'flops', 0.0)), parts_dev=self.w_dev.data_ptr(), nparts=len(self.parts),
-                    nsplit=self.nsplit | (getattr(self, 'ppu', 0) << 16), kh=33, stride=1, f32=2 if f16 else self.parts[0][0].g_f32)
-        gs = getattr(self, 'g_scale', 0.0)
+        f16, gs = self.f16, self.g_scale   # 16-bit f16 tensors (gradient pre-scaled by g_scale): f16 MFMA, reduce scale x 1 / g_scale
+        a = make_op(_lib.OP_WGRAD, flops=float(self.flops), parts_dev=self.w_dev.data_ptr(), nparts=len(self.parts),
+                    nsplit=self.nsplit | (self.ppu << 16), kh=33, stride=1, f32=2 if f16 else self.parts[0][0].g_f32)
         b = make_op(_lib.OP_WGRAD_REDUCE, parts_dev=self.r_dev.data_ptr(), nparts=self.n_red, grad_flat=grad_ptr, scale=scale,
                     few_splits=1 if self.nsplit <= 4 else 0,   # (9 taps): one reduce workgroup per output channel
                     inv_prescale=1.0 / gs if (f16 and gs) else 0.0)
@@ -538,8 +604,60 @@ class Workspace:
     def finalize(self):
         self.buf = torch.zeros(max(self.need, 1), dtype=torch.float32, device=self.device)
         for o in self.pending:
-            o.set('ws', self.buf.data_ptr())
+            patch(o, ws=self.buf.data_ptr())
         self.pending = []
+
+
+class GradScale:
+    """The power of two `gscale` that f16-storage gradient tensors of a trunk carry, shared by the plans of one (N, h, w) -- the sub-batch replicas
+    of a step -- and what the trainers expect of a plan's `store`.  The magnitude of dL/d(trunk output) depends on the weights, so the scale is
+    calibrated from the data: the trainers measure max |dL/d(trunk output)| behind the HR tail on the first step and every CALIB_EVERY steps after
+    it (calibrate_due / set_gscale_from: one host sync), and every registered op is patched.  f16 has 30 normal binades and the calibration puts
+    the largest entry at ~1, so a drift of 2^+-8 between two calibrations is harmless; an overflow reaches Adam's non-finite guard."""
+
+    CALIB_EVERY = 256
+
+    def __init__(self, f16, headroom=1.0):
+        """headroom: the first scaled tensor holds headroom * gscale * dL/d(trunk output)"""
+        self.f16, self.headroom = bool(f16), float(headroom)
+        self.gscale = 1.0
+        self.steps_since_calib = None
+        self._scaled, self._reduces = [], []
+
+    def calibrate_due(self):
+        """True when the gradient scale has to be (re-)measured before this step's trunk backward (f16 storage only)"""
+        if not self.f16:
+            return False
+        due = self.steps_since_calib is None or self.steps_since_calib >= self.CALIB_EVERY
+        if not due:
+            self.steps_since_calib += 1
+        return due
+
+    def register_scaled(self, op, has_alpha, base_gamma=1.0):
+        """conv op whose 16-bit output carries the gradient scale (gamma = base_gamma * gscale) and, with has_alpha, whose scaled accumulator is
+        un-scaled for the fp32 gradient stream (alpha = 1 / gscale)"""
+        self._scaled.append((op, (bool(has_alpha), float(base_gamma))))   # pairs: (op, how it carries the scale)
+
+    def register_reduce(self, op):
+        """weight-gradient reduction of a scaled 16-bit gradient (inv_prescale = 1 / gscale)"""
+        self._reduces.append(op)
+
+    def set_gscale_from(self, g_t0_absmax):
+        """g_t0_absmax: max |dL/d(trunk output)| (host float); headroom * gscale * that is brought to ~1.  Returns the scale."""
+        import math
+        a = self.headroom * float(g_t0_absmax)
+        s = 1.0 if not (a > 0.0 and math.isfinite(a)) else float(2.0 ** max(-60, min(60, -int(math.ceil(math.log2(a))))))
+        self.steps_since_calib = 0
+        if s != self.gscale:
+            self.gscale = s
+            for o, (has_alpha, bg) in self._scaled:
+                patch(o, gamma=bg * s, **({'alpha': 1.0 / s} if has_alpha else {}))
+            for o in self._reduces:
+                patch(o, inv_prescale=1.0 / s)
+        return s
+
+    def set_grad_scale(self, scale):
+        return False   # (no reductions of its own: the plans' lists take the data-parallel scale, set_reduce_scale)
 
 
 def ensure_runtime_ready():

@@ -375,10 +375,7 @@ class _DPlan:
                 grp.add_conv(gz.view, True, gz.planes, inp.view, True, inp.planes, L['cout'], L['cin'], hi, wi, ho, wo, N,
                              P.off(L['key'] + 'weight'), P.off(L['key'] + 'bias') if L['bias'] else None, pad=L['pad'],
                              f16=net.prec == 4, g_scale=4096.0 if net.prec == 4 else 0.0, split=split)
-                grp.finalize(self.ws, net.device)
-                for o in grp.ops(P.grad.data_ptr()):
-                    ops.add(o)
-                ops.keep.append(grp)
+                grp.emit(ops, self.ws, net.device, P.grad.data_ptr())
             if i > 0:
                 prev = net.layers[i - 1]
                 if prev['norm']:

@@ -383,14 +383,13 @@ class SRModel(BaseModel):
             ws.extend(loss_ops)
             plan.buckets, prev = [], 0
             for idx, lo, hi in plan._marks:
-                ws.ops.extend(plan.bwd.ops[prev:idx])
+                ws.extend(plan.bwd.slice(prev, idx))
                 ev = plan._event()
-                ws.ops.append(make_op(_lib.OP_EVENT_RECORD, event=ev))
+                ws.add(make_op(_lib.OP_EVENT_RECORD, event=ev))
                 plan.buckets.append((ev, lo, hi))
                 prev = idx
-            ws.ops.extend(plan.bwd.ops[prev:])
-            ws.keep.extend(plan.bwd.keep)
-            ws._arr = None
+            ws.extend(plan.bwd.slice(prev))
+            ws.keep.append(plan.bwd)
             plan.whole_step = ws
             plan.whole_step_gen = getattr(plan, 'whole_step_gen', 0) + 1   # identifies THIS recording (id() of a rebuilt list can repeat)
         return plan.whole_step
@@ -457,8 +456,8 @@ class SRModel(BaseModel):
                     loss_ops, hr_buf = self._ops_for(plan, N)
                     hr_buf.copy_(self.real_H[plan.n0:plan.n0 + plan.N])
                     plan.set_input(self.var_L[plan.n0:plan.n0 + plan.N])
-                    if dp_on and plan.set_grad_scale(self.dp.grad_scale) and hasattr(plan, 'whole_step'):
-                        del plan.whole_step  # the recorded list holds copies of the patched reduce ops
+                    if dp_on:
+                        plan.set_grad_scale(self.dp.grad_scale)   # (engine.patch: whole_step refreshes its image by itself)
                 steps.append(self._whole_step(plan, loss_ops))
             run_parallel(steps, self._streams)
             g = self.netG.params.grad

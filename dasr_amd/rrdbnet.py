@@ -12,7 +12,8 @@ from collections import OrderedDict
 import torch
 
 from . import _lib
-from .engine import (BTensor, ParamStore, PackRegistry, OpList, WgradGroup, WgradGroup3, Workspace, conv_op, ceil_div, SLOPE, ConvChain)
+from .engine import (BTensor, ParamStore, PackRegistry, OpList, WgradGroup, WgradGroup3, Workspace, conv_op, ceil_div, SLOPE, ConvChain, GradScale,
+                     set_reduce_scale)
 from ._lib import Op, Tensor, make_op
 
 GC = 32  # growth channels are hard-wired to 32 in the reference (architecture.py:183)
@@ -336,7 +337,7 @@ def rdb_wgrad_parts(grp, nf, pre, P, Gs, S, h, w, N):
     return n, 2.0 * N * h * w * 9 * sum((nf + (j - 1) * GC) * (GC if j < 5 else nf) for j in range(1, 6))
 
 
-class TrunkStore:
+class TrunkStore(GradScale):
     """Forward slabs and gradient slabs of ALL dense blocks for a whole batch of N images (one allocation per RDB; sub-batch replicas work on
     image ranges of it), and the deferred weight-gradient phase over them: after the data-gradient chain has filled every gradient slab, the
     weight gradients of the 3 nb dense blocks are computed by a few grouped launches (4 RRDBs per launch: every
@@ -349,15 +350,9 @@ class TrunkStore:
         sc = nf + 4 * GC
         mk = lambda: torch.zeros((N, ceil_div(sc, 16), h, w, 16), dtype=torch.float16 if net.rdb_f16 else torch.bfloat16, device=dev)
         # f16 dense blocks: every gradient slab holds gscale * dL/d(.); ONE power of two for the whole batch (the replicas of a step share the slabs and
-        # the grouped weight-gradient launches), sized like the HR tail's: dL/d(trunk) of a mean loss is ~1 / (N 3 16 h w), brought to ~2^-3
-        import math
-        # The magnitude of dL/d(trunk) depends on the weights (kaiming x 0.1 at init: ~1e-5 of dL/dSR; a trained net: orders of magnitude more), so the
-        # scale is CALIBRATED from data: the trainers measure max |dL/d(trunk output)| behind the HR tail (calibrate_due / set_gscale: on the first
-        # step of a plan and every CALIB_EVERY steps after it, one host sync) and every op that carries the scale is patched in place.  f16 has
-        # 30 normal binades; the calibration puts the largest slab entry at ~1, so a drift of 2^+-8 between two calibrations is harmless, and
-        # an overflow reaches Adam's non-finite guard.
-        self.gscale = 1.0
-        self._scaled_ops, self._plans, self.steps_since_calib = [], [], None
+        # the grouped weight-gradient launches), calibrated from the data (engine.GradScale).  The first planes of the first gradient slab hold
+        # 0.04 * gscale * dL/d(trunk output): the head-room factor
+        super().__init__(net.rdb_f16, headroom=0.04)
         self.slab_t = [mk() for _ in range(3 * nb)]
         self.gslab_t = [mk() for _ in range(3 * nb)]
         self.sc = sc
@@ -392,7 +387,6 @@ class TrunkStore:
                 G *= 2
             lo_rrdb = hi_rrdb - G
             grp = WgradGroup3()
-            grp.flops = 0.0
             for i in range(hi_rrdb - 1, lo_rrdb - 1, -1):
                 for r in (3, 2, 1):
                     ridx = 3 * i + (r - 1)
@@ -400,66 +394,18 @@ class TrunkStore:
                     grp.flops += fl
             if net.rdb_f16:
                 grp.f16, grp.g_scale = True, self.gscale
-            grp.finalize(self.ws, net.device, target_wgs=target, ppu=ppu)
             first = len(self.phase.ops)
-            for o in grp.ops(P.grad.data_ptr()):
-                self.phase.add(o)
-            self.phase.keep.append(grp)
+            reduce_op = grp.emit(self.phase, self.ws, net.device, P.grad.data_ptr(), target_wgs=target, ppu=ppu)[1]
+            if net.rdb_f16:
+                self.register_reduce(reduce_op)
             lo = P.off('model.1.sub.%d.RDB1.conv1.0.weight' % lo_rrdb)
             hi = P.off('model.1.sub.%d.RDB1.conv1.0.weight' % hi_rrdb) if hi_rrdb < nb else P.off('model.1.sub.%d.weight' % nb)
             self.groups.append((first, len(self.phase.ops), lo, hi))
             hi_rrdb = lo_rrdb
         self.phase.tag(5)
 
-    CALIB_EVERY = 256
-
-    def register_scaled(self, op, base_gamma, has_alpha):
-        """conv op whose 16-bit output carries the gradient scale (gamma = base_gamma * gscale) and, with has_alpha, whose accumulator is un-scaled
-        for the fp32 gradient stream (alpha = 1 / gscale)"""
-        self._scaled_ops.append((op, float(base_gamma), bool(has_alpha)))
-
-    def calibrate_due(self):
-        """f16 dense blocks: True when the gradient scale has to be (re-)measured before this step's dense-block backward"""
-        if not self.net.rdb_f16:
-            return False
-        due = self.steps_since_calib is None or self.steps_since_calib >= self.CALIB_EVERY
-        if not due:
-            self.steps_since_calib += 1
-        return due
-
-    def set_gscale_from(self, g_t0_absmax):
-        """g_t0_absmax: max |dL/d(trunk output)| (host float).  The first planes of the first gradient slab hold 0.04 * gscale * that: brought to ~1."""
-        import math
-        a = 0.04 * float(g_t0_absmax)
-        s = 1.0 if not (a > 0.0 and math.isfinite(a)) else float(2.0 ** max(-60, min(60, -int(math.ceil(math.log2(a))))))
-        self.steps_since_calib = 0
-        if s == self.gscale:
-            return s
-        self.gscale = s
-        for o, bg, has_alpha in self._scaled_ops:
-            o.conv.gamma = bg * s
-            if has_alpha:
-                o.conv.alpha = 1.0 / s
-        for o in self.phase.ops:
-            if o.op == _lib.OP_WGRAD_REDUCE:
-                o.set('inv_prescale', 1.0 / s)
-        self.phase._arr = None
-        for pl in self._plans:   # every recorded list that holds copies of the patched ops
-            pl.bwd._arr = None
-            pl._segments = None
-            if hasattr(pl, 'whole_step'):
-                pl.whole_step._arr = None
-        return s
-
     def set_grad_scale(self, scale):
-        changed = False
-        for o in self.phase.ops:
-            if o.op == _lib.OP_WGRAD_REDUCE and o.get('scale') != scale:
-                o.set('scale', scale)
-                changed = True
-        if changed:
-            self.phase._arr = None
-        return changed
+        return set_reduce_scale([self.phase], scale)
 
 
 class _Plan:
@@ -537,8 +483,7 @@ class _Plan:
             return None
         o = self.bwd.ops[0]
         assert o.op == _lib.OP_CVT_F16 and o.get('y').p == self.g_sr16.view().p
-        del self.bwd.ops[0]
-        self.bwd._arr = None
+        self.bwd.pop(0)
         self.tail_end -= 1
         self._marks = [(idx - 1, lo, hi) for idx, lo, hi in self._marks]
         self._segments = None
@@ -705,10 +650,7 @@ class _Plan:
         grp = WgradGroup(3, 1)
         grp.add_conv(g.view, g_f32, g.planes, inp.view, in_f32, inp.planes, cout, cin, Hin, Win, Hout, Wout, self.N,
                      P.off(conv_key + 'weight'), P.off(conv_key + 'bias'), ups=ups, f16=f16, g_scale=self.gscale)
-        grp.finalize(self.ws, self.net.device)
-        for o in grp.ops(self.grad.data_ptr()):
-            ops.add(o)
-        ops.keep.append(grp)
+        grp.emit(ops, self.ws, self.net.device, self.grad.data_ptr())
 
     def _subpixel_dgrad(self, ops, name, g_hi, g_lo, hl, wl, mask):
         """g_lo[hl x wl] = (mask') * sum over output parities of the transposed 2x2 conv of g_hi's parity sub-grid (g_hi: 2hl x 2wl).
@@ -747,7 +689,6 @@ class _Plan:
         ops.tag(3)
         self.tail_end = len(ops.ops)   # ops [0, tail_end): the HR tail's backward; self.g_t0 = dL/d(trunk output) is complete behind them
         self._build_backward_trunk(ops)
-        self.store._plans.append(self)
 
     def _wg3_target(self, nparts):
         """workgroups of a 12-wave weight-gradient launch (one per CU, nothing co-resides with them): the whole chip for a single plan, an equal
@@ -771,10 +712,7 @@ class _Plan:
         if f16:
             grp.f16, grp.g_scale = True, self.gscale if g_scale is None else g_scale
         grp.flops = 2.0 * N * Hout * Wout * 9 * cin * cout
-        grp.finalize(self.ws, self.net.device, target_wgs=self._wg3_target(len(grp.parts)))
-        for o in grp.ops(self.grad.data_ptr()):
-            ops.add(o)
-        ops.keep.append(grp)
+        grp.emit(ops, self.ws, self.net.device, self.grad.data_ptr(), target_wgs=self._wg3_target(len(grp.parts)))
 
     def _build_backward_tail_f16(self, ops):
         """HR tail in f16 storage: every gradient tensor holds gscale * dL/d(.) in f16; the last 2x2 down-sum hands dL/d(trunk output) back in
@@ -865,7 +803,7 @@ class _Plan:
         ops.add(conv_op(pack, pk['lr_b'], self.g_t0.view(), True, nf, h, w, h, w, N, out_f32=G.view(),
                         out_bf16=self.gslab[gs_cur].view(0), gamma=0.04 * gsc, out16_f16=f16))
         if f16:
-            self.store.register_scaled(ops.ops[-1], 0.04, False)
+            self.store.register_scaled(ops.ops[-1], False, base_gamma=0.04)
         # RRDB chain, reversed.  No weight-gradient launch inside the chain: every RDB keeps its gradient slab and TrunkStore.phase computes all
         # of them afterwards (grouped launches over the whole batch).
         # DASR_CHAIN=1 (see _build_forward): the 15 nb data-gradient convs as one persistent chained launch (bf16 storage only: the f16 path patches
@@ -899,7 +837,7 @@ class _Plan:
                                     res1=Gout.view(), beta1=1.0, res2=Grr.view(), beta2=1.0, out_f32=Gin.view(), out_bf16=nxt, gamma=0.04 * gsc, alpha=1.0 / gsc,
                                     out16_f16=f16))
                 if f16:
-                    self.store.register_scaled(ops.ops[-1], 0.04 if r == 1 else 0.2, True)
+                    self.store.register_scaled(ops.ops[-1], True, base_gamma=0.04 if r == 1 else 0.2)
                 Gout = Gin
                 gs_cur += 1
             G = Gout
@@ -931,10 +869,9 @@ class _Plan:
         if not self.shared_store:   # this plan owns the whole batch: the weight-gradient phase follows the chain in the same list
             st = self.store
             for first_op, end_op, lo, hi in st.groups:
-                ops.ops.extend(st.phase.ops[first_op:end_op])
+                ops.extend(st.phase.slice(first_op, end_op))
                 self._marks.append((len(ops.ops), lo, hi))
             ops.keep.append(st)
-            ops._arr = None
         # ShortcutBlock: g_fea = g_chain + g_t0
         ops.add(make_op(_lib.OP_AXPBY, x=G.view(), a=1.0, z=self.g_t0.view(), b=1.0, N=N, C=nf, H=h, W=w, out_f32=self.g_fea.view(), gamma=1.0))
         self._wg(ops, 'model.0.', self.g_fea, True, self.x_in, True, nf, net.in_nc, h, w, h, w)
@@ -945,15 +882,7 @@ class _Plan:
 
     def set_grad_scale(self, scale):
         """fold 1/world_size into the deterministic wgrad reduction (data-parallel mean gradient); True if anything changed"""
-        changed = False
-        for o in self.bwd.ops:
-            if o.op == _lib.OP_WGRAD_REDUCE and o.get('scale') != scale:
-                o.set('scale', scale)
-                changed = True
-        if changed:
-            self.bwd._arr = None
-            self._segments = None
-        return changed
+        return set_reduce_scale([self.bwd], scale)
 
     def run_backward_dp(self, dp, g):
         """the backward list in gradient-bucket segments, every finished bucket handed to the exchange (dp.reduce_async: SUM all-reduce on the
@@ -983,9 +912,7 @@ class _Plan:
         if self._segments is None:
             segs, prev_idx = [], 0
             for idx, lo, hi in self._marks:
-                ol = OpList()
-                ol.ops = self.bwd.ops[prev_idx:idx]
-                segs.append((ol, (lo, hi)))
+                segs.append((self.bwd.slice(prev_idx, idx), (lo, hi)))
                 prev_idx = idx
             self._segments = segs
         return self._segments

@@ -21,7 +21,7 @@ import torch
 
 from . import _lib
 from ._lib import make_op
-from .engine import BTensor, ParamStore, PackRegistry, OpList, Workspace, conv_op, NULL_T
+from .engine import BTensor, ParamStore, PackRegistry, OpList, Workspace, conv_op, NULL_T, GradScale
 from .rrdbnet import RRDBNetHIP, _Plan as _RRDBPlan
 
 logger = logging.getLogger('base')
@@ -58,61 +58,10 @@ def check_options(upscale=4, norm_type=None, mode='CNA'):
                                   % os.environ['DASR_HR_PREC'])
 
 
-class _TrunkScale:
+class _TrunkScale(GradScale):
     """What the trainers expect of a plan's `store` (rrdbnet.TrunkStore).  SRResNet defers no weight gradients (every one is part of its plan's
-    backward list), but its f16-storage trunk (trunk_prec 2) keeps the 16-bit gradient shadows pre-scaled by a power of two.  The scale is
-    shared by the plans of one (N, h, w), i.e. by the sub-batch replicas of a step.  Like TrunkStore's, it is calibrated from the data: the
-    trainers measure max |dL/d(trunk output)| behind the HR tail on the first step and every CALIB_EVERY steps after it (calibrate_due /
-    set_gscale_from), and every recorded op that carries the scale is patched in place."""
-
-    CALIB_EVERY = 256
-
-    def __init__(self, f16):
-        self.f16 = bool(f16)
-        self.gscale = 1.0
-        self.steps_since_calib = None
-        self._plans, self._scaled, self._reduces = [], [], []
-
-    def calibrate_due(self):
-        if not self.f16:
-            return False
-        due = self.steps_since_calib is None or self.steps_since_calib >= self.CALIB_EVERY
-        if not due:
-            self.steps_since_calib += 1
-        return due
-
-    def register_scaled(self, op, has_alpha):
-        """conv op whose 16-bit output is gscale * dL/d(.) (gamma = gscale) and, with has_alpha, whose scaled accumulator is un-scaled for the
-        fp32 gradient stream (alpha = 1 / gscale)"""
-        self._scaled.append((op, bool(has_alpha)))
-
-    def register_reduce(self, op):
-        """weight-gradient reduction of a scaled 16-bit gradient (second scale factor 1 / gscale)"""
-        self._reduces.append(op)
-
-    def set_gscale_from(self, g_t0_absmax):
-        """g_t0_absmax: max |dL/d(trunk output)| (host float); the gradient shadows start at about that size: brought to ~1"""
-        a = float(g_t0_absmax)
-        s = 1.0 if not (a > 0.0 and math.isfinite(a)) else float(2.0 ** max(-60, min(60, -int(math.ceil(math.log2(a))))))
-        self.steps_since_calib = 0
-        if s == self.gscale:
-            return s
-        self.gscale = s
-        for o, has_alpha in self._scaled:
-            o.conv.gamma = s
-            if has_alpha:
-                o.conv.alpha = 1.0 / s
-        for o in self._reduces:
-            o.set('inv_prescale', 1.0 / s)
-        for pl in self._plans:   # every recorded list that holds the patched ops
-            pl.bwd._arr = None
-            pl._segments = None
-            if hasattr(pl, 'whole_step'):
-                pl.whole_step._arr = None
-        return s
-
-    def set_grad_scale(self, scale):
-        return False   # (no deferred phase: the plans' own reductions take the data-parallel scale, _Plan.set_grad_scale)
+    backward list), but its f16-storage trunk (trunk_prec 2) keeps the 16-bit gradient shadows pre-scaled by a power of two, shared by the plans
+    of one (N, h, w) and calibrated from the data as TrunkStore's is.  The gradient shadows start at about max |dL/d(trunk output)|: head-room 1."""
 
 
 class SRResNetHIP(RRDBNetHIP):
