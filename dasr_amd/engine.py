@@ -367,8 +367,9 @@ def conv_op(pack, ref, inp, in_f32, cin, Hin, Win, Hout, Wout, N, bias=None, kh=
 class ConvChain:
     """One persistent launch for a chain of dense-block conv ops of one geometry (dasr_conv_chain, include/dasr_hip.h): the forward trunk of the
     generator without kernel boundaries between its layers.  `ops`: the conv Ops in execution order (their parameter blocks are copied);
-    dep_chunks[i]: first 16-channel input chunk of layer i that holds layer i - 1's output (<= 0: all of them).  flags / err: shared per (N, h, w)
-    plan -- the flag words count stages monotonically across launches, err stays zero unless a launch went wrong (check())."""
+    dep_chunks[i]: first 16-channel input chunk of layer i that holds layer i - 1's output (<= 0: all of them).  flags: one buffer per chain (allocated
+    here unless given): the flag words count stages on from launch to launch and belong to the launches of one geometry (include/dasr_hip.h, dasr_conv_chain);
+    err: shared per (N, h, w) plan, stays zero unless a launch went wrong (check())."""
 
     def __init__(self, ops, dep_chunks, n_images, n_tiles, device, flags=None, err=None, form='layer'):
         assert len(ops) == len(dep_chunks) and ops

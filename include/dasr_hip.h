@@ -106,6 +106,19 @@ int dasr_conv(const dasr_conv_params* p, void* stream);
  * hosts the tiles of its own images).
  * `flags`: N * tiles + 8 words (the last eight: per-XCD ticket counters).  `err` (device word, zero at allocation): bit 1 a neighbour wait gave
  * up -- the results are then not valid (pass the word to dasr_adam as gate_flag: such a step then never reaches the weights).
+ * What the kernels rely on in `flags` (both forms; held by tests/test_gpu_chain.py), beyond "zero at allocation":
+ *   - The words COUNT ON from launch to launch: a launch of nlayers layers leaves every tile word it owns nlayers higher (layer L of a tile publishes
+ *     start + L + 1) and every ticket word higher by the launch's workgroups per XCD (64 here, q in the input-stationary form); nothing is reset, and the
+ *     caller never writes the buffer between launches.  Every comparison is a signed difference, (int)(word - target) < 0: the tile words may wrap 2^32.
+ *   - ALL TILE WORDS A LAUNCH USES ARE EQUAL WHEN IT STARTS (the first N * tiles words of the buffer).  A tile reads its own word as its start value and compares its eight neighbours' words with targets
+ *     counted from that value, never from theirs: a neighbour whose word starts higher looks finished before it has begun (its halo is read too early), one
+ *     that starts lower is waited for until the wait gives up.
+ *   - A workgroup takes tile (ticket % workgroups per XCD) of its XCD: within a launch the tickets of an XCD must be that many CONSECUTIVE integers.  Counters
+ *     that only launches of one geometry have advanced are a multiple of that number and are never touched by two launches at a time; where the number is not a
+ *     power of two (input-stationary form, q = 18, 27, ...) a counter must not pass 2^32 (2^32 / 32 launches of one buffer at the least).
+ *   - So a flag buffer belongs to the launches of ONE geometry (N, H, W and form: another one owns another set of tile words, which the first has left
+ *     unequal to the rest, and keeps its ticket words elsewhere -- behind 512 tile words here, behind N * ceil(H / 4) * ceil(W / 32) in the input-stationary
+ *     form), one launch at a time.  engine.ConvChain allocates one buffer per chain (rrdbnet.py: every forward and data-gradient chain of a plan its own).
  * OPERATIONAL CONTRACT: the launch needs the device to itself -- a whole 256-CU MI355X (no CPX / DPX partition), no other process on it, and no
  * other kernel of this process in flight on another stream (a collective's kernels on a communication stream included) while it runs: all 512
  * workgroups must be resident at once, 64 per XCD.  See INTEGRATION.md "Chained launches: operational contract".
@@ -123,7 +136,8 @@ int dasr_conv_chain(const dasr_conv_params* dev_layers, const dasr_conv_params* 
  * the height that minimises (tiles per workgroup) x (measured chain time of one tile at that height).  Constraints (DASR_EINVAL otherwise): bf16 storage, nlayers a multiple
  * of 5, N a multiple of 8, T <= 32 and such a q exists for one of the heights (16 x 128^2: 16 rows, q 32, two tiles each; 8 x 128^2: 16 rows, one tile; 16 crops of
  * 32 x 32: 4 rows, q 16).  flags: N * ceil(H / 4) * ceil(W / 32) + 8 words, zero at allocation (sized for the finest tiles whichever height runs; the last eight: per-XCD
- * ticket counters); err / operational contract: as dasr_conv_chain (the launch needs all 256 CUs of the device to itself: up to 256 workgroups with 160 KB of LDS each, all
+ * ticket counters; a launch leaves the words of the tiles of the height that ran 5 higher per dense block, the words behind them as they were, the tickets q higher: see
+ * dasr_conv_chain for what the kernel relies on); err / operational contract: as dasr_conv_chain (the launch needs all 256 CUs of the device to itself: up to 256 workgroups with 160 KB of LDS each, all
  * resident). */
 int dasr_rdb_chain(const dasr_conv_params* dev_layers, const dasr_conv_params* host_layers, int32_t nlayers, uint32_t* dev_flags, int32_t* dev_err,
                    void* stream);
