@@ -71,6 +71,11 @@ class SrnU8Desc(C.Structure):
     _fields_ = [('src', c_vp), ('H', c_i32), ('W', c_i32), ('y0', c_i32), ('x0', c_i32), ('size', c_i32), ('flags', c_i32), ('dst', c_vp)]
 
 
+class WindowDesc(C.Structure):
+    """dasr_window_desc"""
+    _fields_ = [('y0', c_i32), ('x0', c_i32)]
+
+
 class Op(C.Structure):
     """dasr_op: one recorded launch.  OP_CONV carries a ConvParams; every other kind passes its arguments in the untyped slots i / f / l / p / t,
     laid out by OP_ARGS (build with make_op, read and patch with get / set)."""
@@ -304,6 +309,8 @@ _SIGS = {
     'dasr_dihedral8_mean': [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp],
     'dasr_bp_residual': [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     'dasr_bp_update': [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    'dasr_windows_down_u8': [c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    'dasr_imresize_up': [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp],
     'dasr_prof_begin': [c_i32],
     'dasr_prof_end': [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp],
 }

@@ -6,7 +6,10 @@ post-process that makes the SR image consistent with the LR image it came from).
 
 back_project runs it on the device, two launches per iteration (csrc/imgio.hip: dasr_bp_residual, dasr_bp_update) and no host synchronisation;
 back_project_fp64 is the restatement on the host in float64 the tests compare against.  The option key `"back_projection"` (options.back_projection_iters) puts it
-behind test() / test_x8() of the SRN models, `python -m dasr_amd.back_projection` runs it on folders of PNG files (main_bp.m)."""
+behind test() / test_x8() of the SRN models, `python -m dasr_amd.back_projection` runs it on folders of PNG files (main_bp.m).
+
+reverse_filter / reverse_filter_fp64, at the end, are the second post-process the reference ships (main_reverse_filter.m): the same residual, up-sampled without the
+Gaussian (csrc/imgio.hip: dasr_imresize_up); `--reverse_filter` of the folder CLI."""
 import ctypes as C
 import math
 
@@ -156,3 +159,47 @@ def back_project_fp64(sr, lr, iters=DEFAULT_ITERS, trace=None):
     if trace is not None:
         trace.append(float((im_l - imresize_matlab(im_h, 1.0 / s)).abs().max()))
     return im_h[None] if batched else im_h
+
+
+def reverse_filter(sr, lr, iters=DEFAULT_ITERS):
+    """`iters` iterations of the reverse filter (codes/SRN/scripts/back_projection/main_reverse_filter.m:18-22) on the device:
+
+        J = imresize(LR, s);   out = out + (J - imresize(imresize(out, 1 / s), s))
+
+    Bicubic up-sampling is linear, so J - up(down(out)) = up(LR - down(out)): every iteration is dasr_bp_residual (d = lr - down(out)) and one dasr_imresize_up that adds
+    up(d) onto out with one rounding; J is never formed.  The contract is back_project's: sr [1, C, s h, s w], lr [1, C, h, w], fp32 device tensors, s in {2, 3, 4} from
+    the shapes; a new tensor, the inputs left as they are, iters == 0 a bit-equal copy, no clamp, nothing synchronised, ValueError naming the shapes."""
+    from .bicubic import upsample
+    s = _checked(sr, lr)
+    iters = int(iters)
+    if iters < 0:
+        raise ValueError('reverse_filter: iters must be >= 0, got %d' % iters)
+    out = sr.detach().clone(memory_format=torch.contiguous_format)
+    if iters == 0:
+        return out
+    lr = lr.detach().contiguous()
+    _, c, H, W = out.shape
+    d = torch.empty_like(lr)
+    down, _ = _tables(H, W, s, out.device)
+    L, st = _lib.lib(), _stream()
+    for _ in range(iters):
+        _lib.check(L.dasr_bp_residual(out.data_ptr(), lr.data_ptr(), c, H, W, s, *down, d.data_ptr(), st), 'dasr_bp_residual')
+        upsample(d, s, into=out)
+    return out
+
+
+def reverse_filter_fp64(sr, lr, iters=DEFAULT_ITERS, literal=True):
+    """main_reverse_filter.m:18-22 on the host, all float64: sr [1, C, s h, s w] (or [C, s h, s w]) and lr likewise, any float dtype, CPU.  `literal`: the MATLAB lines
+    as they stand, J formed once; otherwise the form the device runs, out + up(lr - down(out)).  Returns the float64 image in the shape of sr."""
+    from .data import imresize_matlab
+    batched = sr.dim() == 4
+    s = scale_of(sr.shape if batched else (1,) + tuple(sr.shape), lr.shape if lr.dim() == 4 else (1,) + tuple(lr.shape))
+    im_lr = (lr[0] if lr.dim() == 4 else lr).detach().cpu().to(torch.float64)
+    im_out = (sr[0] if batched else sr).detach().cpu().to(torch.float64).clone()
+    J = imresize_matlab(im_lr, float(s))                                                              # :18 J = imresize(im_LR, 4, 'bicubic')
+    for _ in range(int(iters)):                                                                       # :20 for m = 1:max_iter
+        if literal:
+            im_out = im_out + (J - imresize_matlab(imresize_matlab(im_out, 1.0 / s), float(s)))       # :21
+        else:
+            im_out = im_out + imresize_matlab(im_lr - imresize_matlab(im_out, 1.0 / s), float(s))
+    return im_out[None] if batched else im_out

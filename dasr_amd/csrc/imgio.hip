@@ -12,7 +12,9 @@
 //    (per-descriptor window size and destination), the second the augmented LR crops of an HR-only set: samples of the x1/4 image of the WHOLE image, made where a crop needs them.
 //  * dihedral8 / dihedral8_mean: the geometry of the x8 self-ensemble (`"self_ensemble": true`; reference: codes/SRN/models/SR_model.py:102-140 test_x8): the eight flips /
 //    transposes of the LR image in one launch, and the mean of the eight inverse-transformed SR images in one launch with a fixed order of the adds.
-//  * bp_residual / bp_update: the two launches of one iteration of the back-projection of an SR image onto its LR input (`"back_projection"`), at the end of the file.
+//  * bp_residual / bp_update: the two launches of one iteration of the back-projection of an SR image onto its LR input (`"back_projection"`), near the end of the file.
+//  * windows_down_u8 / imresize_up: the bicubic LR and Bic images of windows of a resident 8-bit image (`python -m dasr_amd.prepare_data`) and the up-sampling of the
+//    reverse filter, at the end of the file.
 // The first two are memory-bound (about 36 multiply-adds per output sample at s = 4 against 2 x 18 gathered reads), so the kernels are plain: one thread per output
 // sample, the x index on the lanes so that loads and stores of a wave are contiguous (pass 2 reads with a stride of s samples inside one row of the
 // intermediate, which the 18-tap overlap of neighbouring outputs keeps in cache), no LDS, no atomics.
@@ -708,4 +710,262 @@ extern "C" int dasr_bp_update(float* sr, const float* d, int32_t C, int32_t h, i
     return s == 2 ? bp_update_launch<2>(sr, d, C, h, w, idx_h, w_h, idx_w, w_w, g, stream)
          : s == 3 ? bp_update_launch<3>(sr, d, C, h, w, idx_h, w_h, idx_w, w_w, g, stream)
                   : bp_update_launch<4>(sr, d, C, h, w, idx_h, w_h, idx_w, w_w, g, stream);
+}
+
+// ---- dataset preparation (`python -m dasr_amd.prepare_data`; reference: codes/SRN/scripts/generate_mod_LR_bic.m:50-64, back_projection/main_reverse_filter.m:18-22; host side:
+// dasr_amd/bicubic.py, backproject.reverse_filter) ----------------------------------------------------------------------------------------------------------------------
+//  * windows_down_u8_kernel: L = imresize(window / 255.0, 1 / s) of n windows of one resident 8-bit image, the scheme of bp_residual_kernel (the window a tile of LR outputs
+//    reaches is staged once, both passes in LDS, everything read from memory requested before the first barrier) with three differences.  The tap tables are those of the
+//    WINDOW (hh x ww), so the mirror edge is the window's edge.  The staged samples are the interleaved BYTES as they lie in memory, all three channels of a pixel in one
+//    workgroup: a window row is one run of 3 nw bytes, fetched as the aligned 4-byte words that cover it (rows of 3 W bytes start at any of the four byte phases, so the
+//    phase of each staged row is kept with its row offset) -- a word that would end beyond the image, or any word of an image whose pointer is not 4-byte aligned, is put
+//    together from single bytes.  im2double is a 256-entry table of (double)b / 255.0 in LDS, filled by the workgroup's 256 threads: one correctly rounded division per
+//    thread instead of one per tap.
+//      LDS at S = 4: bytes [48][436] + lut [256] fp64 + mid [3][8][4][37] fp64 + the tile's taps (6912 + 1728) = 20928 + 2048 + 28416 + 8640 = 60032 bytes, two workgroups on a CU.
+//  * imresize_up_kernel: the up-sampling stage of bp_update_kernel on its own (no halo, no 5 x 5 pass), for fp32 or fp64 planes, writing fp32 (plain or accumulated onto
+//    dst with one rounding) or interleaved bytes.  With byte output a workgroup walks the C channels of its tile one after the other, so the C bytes of a pixel are written
+//    by one workgroup within a few hundred cycles and meet in the cache; the planar modes take one plane per workgroup.
+namespace {
+
+constexpr int WD_RT = DASR_WD_TILE_H, WD_CT = DASR_WD_TILE_W;   // LR outputs per workgroup of the window kernel
+constexpr int UP_TY = DASR_UP_TILE_H, UP_TX = DASR_UP_TILE_W;   // output samples per workgroup of the up-sampling kernel
+
+// MATLAB's im2uint8 of a double: min(255, max(0, floor(x * 255 + 0.5))), every step rounded to fp64 (contraction is off)
+__device__ __forceinline__ uint8_t quant_u8(double x) {
+    return (uint8_t)(int)fmin(255.0, fmax(0.0, floor(x * 255.0 + 0.5)));
+}
+
+// grid (ceil(ww / S / WD_CT), ceil(hh / S / WD_RT), n)
+template <int S>
+__global__ __launch_bounds__(256) void windows_down_u8_kernel(const uint8_t* __restrict__ src, int H, int W, int wide, const dasr_window_desc* __restrict__ wins, int hh, int ww,
+                                                              const int32_t* __restrict__ idx_h, const double* __restrict__ w_h, const int32_t* __restrict__ idx_w,
+                                                              const double* __restrict__ w_w, uint8_t* __restrict__ lr_u8, double* __restrict__ lr_f64) {
+    constexpr int TAPS = 4 * S + 2, OFF = S + 1 + S / 2;
+    constexpr int WIN_H = S * WD_RT + 3 * S + 4, WIN_W = S * WD_CT + 3 * S + 4, QS = (WIN_W + S - 1) / S + 1;
+    constexpr int ROWD = (3 * WIN_W + 3 + 3) / 4, ROWB = 4 * ROWD;   // words / bytes of a staged row: 3 WIN_W bytes behind a phase of up to 3
+    constexpr int NLD = (WIN_H * ROWD + 255) / 256, NROW = (WD_RT * 3 * WIN_W + 255) / 256;
+    static_assert(WD_RT * WD_CT == 256 && WD_RT * TAPS <= 256, "one output pixel per thread in the column pass; the row taps are staged in one step");
+    __shared__ uint32_t in32[WIN_H * ROWD];
+    __shared__ double lut[256];
+    __shared__ double mid[3 * WD_RT * S * QS];
+    __shared__ double tw[TAPS * WD_CT], rw[WD_RT * TAPS];
+    __shared__ int32_t tj[TAPS * WD_CT], rj[WD_RT * TAPS];
+    const int tid = threadIdx.x;
+    const int h = hh / S, w = ww / S;
+    const int ox0 = blockIdx.x * WD_CT, oy0 = blockIdx.y * WD_RT;
+    const int rows = min(WD_RT, h - oy0), cols = min(WD_CT, w - ox0);
+    // (the host checked the corners; clamped all the same: a damaged descriptor reads a wrong window, never outside the image)
+    const int y0 = min(max(wins[blockIdx.z].y0, 0), H - hh), x0 = min(max(wins[blockIdx.z].x0, 0), W - ww);
+    const int by = max(S * oy0 - OFF - 1, 0), bx = max(S * ox0 - OFF - 1, 0);   // window coordinates: the window is the image of bp_residual_kernel
+    const int nh = min(min(S * (oy0 + rows - 1) - OFF + TAPS, hh - 1) - by + 1, WIN_H), nw = min(min(S * (ox0 + cols - 1) - OFF + TAPS, ww - 1) - bx + 1, WIN_W);
+    const size_t total = (size_t)H * W * 3, pitch = (size_t)W * 3;
+    const size_t g0 = ((size_t)(y0 + by) * W + x0 + bx) * 3;                     // byte offset of staged sample (0, 0), channel 0
+    lut[tid] = (double)tid / 255.0;
+#pragma unroll
+    for (int e = tid; e < WD_CT * TAPS; e += 256) {
+        const int ox = e / TAPS, t = e - ox * TAPS;
+        if (ox < cols) {
+            tj[t * WD_CT + ox] = min(max(idx_w[(size_t)ox0 * TAPS + e] - bx, 0), nw - 1);
+            tw[t * WD_CT + ox] = w_w[(size_t)ox0 * TAPS + e];
+        }
+    }
+    if (tid < rows * TAPS) {   // (kept as the byte offset of the staged row's first sample: row offset plus the row's phase)
+        const int r = min(max(idx_h[(size_t)oy0 * TAPS + tid] - by, 0), nh - 1);
+        rj[tid] = r * ROWB + (int)((g0 + (size_t)r * pitch) & 3);
+        rw[tid] = w_h[(size_t)oy0 * TAPS + tid];
+    }
+    uint32_t v[NLD];
+#pragma unroll
+    for (int k = 0; k < NLD; ++k) {
+        const int e = tid + 256 * k, r = e / ROWD, q = e - r * ROWD;
+        const size_t g = g0 + (size_t)r * pitch, a = (g & ~(size_t)3) + 4 * (size_t)q;   // the q-th aligned word of staged row r
+        v[k] = 0u;
+        if (r < nh && a < g + 3 * (size_t)nw) {
+            if (wide && a + 4 <= total) {
+                v[k] = *reinterpret_cast<const uint32_t*>(src + a);
+            } else {
+#pragma unroll
+                for (int b = 0; b < 4; ++b)
+                    if (a + b < total) v[k] |= (uint32_t)src[a + b] << (8 * b);
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NLD; ++k)
+        if (tid + 256 * k < WIN_H * ROWD) in32[tid + 256 * k] = v[k];
+    __syncthreads();
+    const uint8_t* inb = reinterpret_cast<const uint8_t*>(in32);
+#pragma unroll
+    for (int k = 0; k < NROW; ++k) {
+        const int e = tid + 256 * k, r = e / (3 * WIN_W), xb = e - r * (3 * WIN_W);
+        if (r < rows && xb < 3 * nw) {
+            double acc = 0.0;
+#pragma unroll
+            for (int t = 0; t < TAPS; ++t) acc += rw[r * TAPS + t] * lut[inb[rj[r * TAPS + t] + xb]];
+            const int x = xb / 3, c = xb - 3 * x;
+            mid[((c * WD_RT + r) * S + x % S) * QS + x / S] = acc;
+        }
+    }
+    __syncthreads();
+    const int orow = tid / WD_CT, ox = tid % WD_CT;
+    if (orow < rows && ox < cols) {
+        const size_t o = ((size_t)blockIdx.z * h + oy0 + orow) * w + ox0 + ox;   // pixel index in [n][h][w]
+        const size_t plane = (size_t)h * w;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            double acc = 0.0;
+#pragma unroll
+            for (int t = 0; t < TAPS; ++t) {
+                const int j = tj[t * WD_CT + ox];
+                acc += tw[t * WD_CT + ox] * mid[((c * WD_RT + orow) * S + j % S) * QS + j / S];
+            }
+            if (lr_f64) lr_f64[((size_t)blockIdx.z * 3 + c) * plane + (size_t)(oy0 + orow) * w + ox0 + ox] = acc;
+            if (lr_u8) lr_u8[o * 3 + c] = quant_u8(acc);
+        }
+    }
+}
+
+// grid (ceil(W / UP_TX), ceil(H / UP_TY), MODE == DASR_UP_U8 ? N : N C), H = S h, W = S w.  The staged window is the LR range bp_lr_floor(Y) - 2 .. + 3 of the tile's
+// rows and columns, one sample wider on both sides, cut at the image (bp_update_kernel's, without the halo): at most ceil((T - 1) / S) + 8 samples along an axis.
+//   LDS at S = 2 (the largest): window [16][40] + V [16][40] fp64 + the taps ([6][64] column, [16][6] row; int32 + fp64) = 5120 + 5120 + 4608 + 1152 = 16000 bytes.
+template <int S, typename TIn, int MODE>
+__global__ __launch_bounds__(256) void imresize_up_kernel(const TIn* __restrict__ x, int C, int h, int w, const int32_t* __restrict__ idx_h, const double* __restrict__ w_h,
+                                                          const int32_t* __restrict__ idx_w, const double* __restrict__ w_w, void* __restrict__ dst) {
+    constexpr int DH = (UP_TY - 1 + S - 1) / S + 8, DW = (UP_TX - 1 + S - 1) / S + 8;
+    constexpr int NLD = (DH * DW + 255) / 256, NOUT = UP_TY * UP_TX / 256;
+    static_assert(UP_TY * UP_TX % 256 == 0 && UP_TY * 6 <= 256, "whole steps of 256 outputs; the row taps are staged in one step");
+    __shared__ double dwin[DH * DW];
+    __shared__ double V[UP_TY * DW];
+    __shared__ double cw[6 * UP_TX], rw[UP_TY * 6];
+    __shared__ int32_t cj[6 * UP_TX], rj[UP_TY * 6];
+    const int tid = threadIdx.x;
+    const int H = S * h, W = S * w;
+    const int X0 = blockIdx.x * UP_TX, Y0 = blockIdx.y * UP_TY;
+    const int yb = min(Y0 + UP_TY - 1, H - 1), xb = min(X0 + UP_TX - 1, W - 1);
+    const int ly0 = max(bp_lr_floor<S>(Y0) - 3, 0), lx0 = max(bp_lr_floor<S>(X0) - 3, 0);
+    const int nh = min(min(bp_lr_floor<S>(yb) + 4, h - 1) - ly0 + 1, DH), nw = min(min(bp_lr_floor<S>(xb) + 4, w - 1) - lx0 + 1, DW);
+#pragma unroll
+    for (int e = tid; e < 6 * UP_TX; e += 256) {
+        const int Xl = e / 6, t = e - Xl * 6, X = X0 + Xl;
+        if (X < W) {
+            cj[t * UP_TX + Xl] = min(max(idx_w[(size_t)X * 6 + t] - lx0, 0), nw - 1);
+            cw[t * UP_TX + Xl] = w_w[(size_t)X * 6 + t];
+        }
+    }
+    if (tid < UP_TY * 6) {
+        const int Y = Y0 + tid / 6;
+        if (Y < H) {
+            rj[tid] = min(max(idx_h[(size_t)Y * 6 + tid % 6] - ly0, 0), nh - 1) * DW;
+            rw[tid] = w_h[(size_t)Y * 6 + tid % 6];
+        }
+    }
+    const int np = MODE == DASR_UP_U8 ? C : 1;   // planes this workgroup walks
+    for (int p = 0; p < np; ++p) {
+        const size_t plane = (size_t)blockIdx.z * np + p;
+        float own[NOUT];
+        if (MODE == DASR_UP_F32_ACC) {
+            const float* sp = static_cast<const float*>(dst) + plane * H * W;
+#pragma unroll
+            for (int k = 0; k < NOUT; ++k) {
+                const int e = tid + 256 * k, Y = Y0 + e / UP_TX, X = X0 + e % UP_TX;
+                own[k] = (Y < H && X < W) ? sp[(size_t)Y * W + X] : 0.f;
+            }
+        }
+        const TIn* dp = x + plane * h * w + (size_t)ly0 * w + lx0;
+        TIn v[NLD];
+#pragma unroll
+        for (int k = 0; k < NLD; ++k) {
+            const int e = tid + 256 * k, r = e / DW, c = e - r * DW;
+            v[k] = (r < nh && c < nw) ? dp[(size_t)r * w + c] : (TIn)0;
+        }
+        // (a second plane overwrites dwin only after every thread has passed the barrier behind the row pass that read it, and V only after the barrier below, which a
+        // thread reaches with its column pass over the previous plane done)
+#pragma unroll
+        for (int k = 0; k < NLD; ++k)
+            if (tid + 256 * k < DH * DW) dwin[tid + 256 * k] = (double)v[k];
+        __syncthreads();
+#pragma unroll
+        for (int e = tid; e < UP_TY * DW; e += 256) {
+            const int Yl = e / DW, c = e - Yl * DW;
+            if (Y0 + Yl >= H || c >= nw) continue;
+            double acc = 0.0;
+#pragma unroll
+            for (int t = 0; t < 6; ++t) acc += rw[Yl * 6 + t] * dwin[rj[Yl * 6 + t] + c];
+            V[e] = acc;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < NOUT; ++k) {
+            const int e = tid + 256 * k, Yl = e / UP_TX, Xl = e % UP_TX, Y = Y0 + Yl, X = X0 + Xl;
+            if (Y >= H || X >= W) continue;
+            double acc = 0.0;
+#pragma unroll
+            for (int t = 0; t < 6; ++t) acc += cw[t * UP_TX + Xl] * V[Yl * DW + cj[t * UP_TX + Xl]];
+            if (MODE == DASR_UP_U8)
+                static_cast<uint8_t*>(dst)[(((size_t)blockIdx.z * H + Y) * W + X) * C + p] = quant_u8(acc);
+            else if (MODE == DASR_UP_F32_ACC)
+                static_cast<float*>(dst)[(plane * H + Y) * W + X] = (float)((double)own[k] + acc);
+            else
+                static_cast<float*>(dst)[(plane * H + Y) * W + X] = (float)acc;
+        }
+    }
+}
+
+template <int S>
+int windows_down_launch(const uint8_t* src, int H, int W, const dasr_window_desc* wins, int n, int hh, int ww, const int32_t* idx_h, const double* w_h, const int32_t* idx_w,
+                        const double* w_w, uint8_t* lr_u8, double* lr_f64, void* stream) {
+    const dim3 grid((unsigned)((ww / S + WD_CT - 1) / WD_CT), (unsigned)((hh / S + WD_RT - 1) / WD_RT), (unsigned)n);
+    const int wide = ((uintptr_t)src & 3) == 0;
+    auto k = windows_down_u8_kernel<S>;
+    DASR_LAUNCH_TAG("windows_down_u8_kernel", k, grid, dim3(256), 0, as_stream(stream), src, H, W, wide, wins, hh, ww, idx_h, w_h, idx_w, w_w, lr_u8, lr_f64);
+    return (int)hipGetLastError();
+}
+
+template <int S, typename TIn, int MODE>
+int imresize_up_launch(const void* x, int N, int C, int h, int w, const int32_t* idx_h, const double* w_h, const int32_t* idx_w, const double* w_w, void* dst, void* stream) {
+    const dim3 grid((unsigned)((S * w + UP_TX - 1) / UP_TX), (unsigned)((S * h + UP_TY - 1) / UP_TY), (unsigned)(MODE == DASR_UP_U8 ? N : N * C));
+    auto k = imresize_up_kernel<S, TIn, MODE>;
+    DASR_LAUNCH_TAG("imresize_up_kernel", k, grid, dim3(256), 0, as_stream(stream), static_cast<const TIn*>(x), C, h, w, idx_h, w_h, idx_w, w_w, dst);
+    return (int)hipGetLastError();
+}
+
+template <int S, typename TIn>
+int imresize_up_mode(int mode, const void* x, int N, int C, int h, int w, const int32_t* idx_h, const double* w_h, const int32_t* idx_w, const double* w_w, void* dst,
+                     void* stream) {
+    return mode == DASR_UP_F32     ? imresize_up_launch<S, TIn, DASR_UP_F32>(x, N, C, h, w, idx_h, w_h, idx_w, w_w, dst, stream)
+         : mode == DASR_UP_F32_ACC ? imresize_up_launch<S, TIn, DASR_UP_F32_ACC>(x, N, C, h, w, idx_h, w_h, idx_w, w_w, dst, stream)
+                                   : imresize_up_launch<S, TIn, DASR_UP_U8>(x, N, C, h, w, idx_h, w_h, idx_w, w_w, dst, stream);
+}
+
+template <int S>
+int imresize_up_type(int x_f64, int mode, const void* x, int N, int C, int h, int w, const int32_t* idx_h, const double* w_h, const int32_t* idx_w, const double* w_w, void* dst,
+                     void* stream) {
+    return x_f64 ? imresize_up_mode<S, double>(mode, x, N, C, h, w, idx_h, w_h, idx_w, w_w, dst, stream)
+                 : imresize_up_mode<S, float>(mode, x, N, C, h, w, idx_h, w_h, idx_w, w_w, dst, stream);
+}
+
+}  // namespace
+
+extern "C" int dasr_windows_down_u8(const uint8_t* src, int32_t H, int32_t W, const dasr_window_desc* wins_dev, const dasr_window_desc* wins_host, int32_t n, int32_t hh,
+                                    int32_t ww, int32_t s, const int32_t* idx_h, const double* w_h, const int32_t* idx_w, const double* w_w, uint8_t* lr_u8, double* lr_f64,
+                                    void* stream) {
+    if (!src || !wins_dev || !wins_host || !idx_h || !w_h || !idx_w || !w_w || (!lr_u8 && !lr_f64)) return DASR_EINVAL;
+    if (H <= 0 || W <= 0 || H > 65535 || W > 65535 || n <= 0 || n > 65535 || s < 2 || s > 4) return DASR_EINVAL;
+    if (hh <= 0 || ww <= 0 || hh % s || ww % s || hh > H || ww > W) return DASR_EINVAL;
+    for (int k = 0; k < n; ++k)
+        if (wins_host[k].y0 < 0 || wins_host[k].x0 < 0 || wins_host[k].y0 > H - hh || wins_host[k].x0 > W - ww) return DASR_EINVAL;
+    return s == 2 ? windows_down_launch<2>(src, H, W, wins_dev, n, hh, ww, idx_h, w_h, idx_w, w_w, lr_u8, lr_f64, stream)
+         : s == 3 ? windows_down_launch<3>(src, H, W, wins_dev, n, hh, ww, idx_h, w_h, idx_w, w_w, lr_u8, lr_f64, stream)
+                  : windows_down_launch<4>(src, H, W, wins_dev, n, hh, ww, idx_h, w_h, idx_w, w_w, lr_u8, lr_f64, stream);
+}
+
+extern "C" int dasr_imresize_up(const void* x, int32_t x_f64, int32_t N, int32_t C, int32_t h, int32_t w, int32_t s, const int32_t* idx_h, const double* w_h,
+                                const int32_t* idx_w, const double* w_w, void* dst, int32_t mode, void* stream) {
+    if (!x || !dst || !idx_h || !w_h || !idx_w || !w_w || x == dst || (x_f64 != 0 && x_f64 != 1)) return DASR_EINVAL;
+    if (N <= 0 || C <= 0 || N > 65535 || C > 65535 || (long long)N * C > 65535 || h <= 0 || w <= 0 || s < 2 || s > 4) return DASR_EINVAL;
+    if (h > 65535 / s || w > 65535 / s) return DASR_EINVAL;
+    if (mode != DASR_UP_F32 && mode != DASR_UP_F32_ACC && mode != DASR_UP_U8) return DASR_EINVAL;
+    return s == 2 ? imresize_up_type<2>(x_f64, mode, x, N, C, h, w, idx_h, w_h, idx_w, w_w, dst, stream)
+         : s == 3 ? imresize_up_type<3>(x_f64, mode, x, N, C, h, w, idx_h, w_h, idx_w, w_w, dst, stream)
+                  : imresize_up_type<4>(x_f64, mode, x, N, C, h, w, idx_h, w_h, idx_w, w_w, dst, stream);
 }

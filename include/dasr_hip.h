@@ -792,6 +792,42 @@ int dasr_bp_residual(const float* sr, const float* lr, int32_t C, int32_t H, int
 int dasr_bp_update(float* sr, const float* d, int32_t C, int32_t h, int32_t w, int32_t s, const int32_t* idx_h, const double* w_h, const int32_t* idx_w,
                    const double* w_w, const double* u5, void* stream);
 
+/* ---- dataset preparation: bicubic LR and Bic images of windows of a resident 8-bit image (csrc/imgio.hip) ---------------------------
+ * codes/SRN/scripts/generate_mod_LR_bic.m:50-64 on the device (dasr_amd/bicubic.py, `python -m dasr_amd.prepare_data`), and the up-sampling half of
+ * back_projection/main_reverse_filter.m:18-22 (backproject.reverse_filter).  Plain vector loads and stores, no atomics, asynchronous on `stream`, nothing is
+ * synchronised, same inputs give the same bits.  Every product and sum is fp64, in tap order, the product rounded before it is added (the convention of
+ * dasr_imresize_down); rows first, then columns.  All tables are device memory.
+ * q(x) = min(255, max(0, floor(x * 255 + 0.5))) evaluated in fp64: MATLAB's imwrite of a double image (im2uint8).
+ *
+ * dasr_windows_down_u8: src = a decoded image, uint8 [H][W][3] interleaved; n windows of hh x ww pixels (multiples of s) with their top-left corners in wins_dev[k]
+ * (device memory; wins_host is the same array in HOST memory, read before the launch for the bounds check only).  Per window
+ * L = imresize(window / 255.0, 1 / s) with the tables of data.bicubic_taps(hh, 1 / s) and (ww, 1 / s) (idx_* [hh / s][4 s + 2] int32 mirrored into [0, hh), w_* fp64):
+ * the mirror edge is the WINDOW's edge, a window never reads its neighbours' pixels.  Both passes run in LDS on the window bytes a DASR_WD_TILE_H x DASR_WD_TILE_W
+ * tile of LR outputs reaches; there is no intermediate in device memory.  lr_u8 [n][hh / s][ww / s][3] = q(L), lr_f64 [n][3][hh / s][ww / s] = L; either may be
+ * null, not both.  Rows of 3 W bytes are read as aligned 4-byte words where src is 4-byte aligned and the word lies inside the image, byte by byte elsewhere.
+ *
+ * dasr_imresize_up: MATLAB's imresize(x, s) (bicubic, not antialiased, symmetric edge) of planes x [N][C][h][w], fp32 (x_f64 = 0) or fp64 (x_f64 = 1), any h, w >= 1:
+ * the tables of data.bicubic_taps(n, s), idx_* [s n][6] int32 mirrored into [0, n), w_* [s n][6] fp64 (what dasr_bp_update reads).  mode DASR_UP_F32: dst fp32
+ * [N][C][s h][s w] = (float)up(x); DASR_UP_F32_ACC: dst = (float)((double)dst + up(x)), one rounding; DASR_UP_U8: dst uint8 [N][s h][s w][C] = q(up(x)), interleaved.
+ * DASR_UP_TILE_H x DASR_UP_TILE_W output samples per workgroup.  dst must not overlap x.
+ *
+ * A null pointer, s outside {2, 3, 4}, hh or ww not a multiple of s, a side of an image or window, n, N or N C over 65535, a window that does not lie inside the image,
+ * an unknown mode: DASR_EINVAL, nothing is launched. */
+#define DASR_WD_TILE_H 8
+#define DASR_WD_TILE_W 32
+#define DASR_UP_TILE_H 16
+#define DASR_UP_TILE_W 64
+#define DASR_UP_F32 0
+#define DASR_UP_F32_ACC 1
+#define DASR_UP_U8 2
+typedef struct {
+    int32_t y0, x0;   /* top-left corner of the window in the image */
+} dasr_window_desc;
+int dasr_windows_down_u8(const uint8_t* src, int32_t H, int32_t W, const dasr_window_desc* wins_dev, const dasr_window_desc* wins_host, int32_t n, int32_t hh, int32_t ww,
+                         int32_t s, const int32_t* idx_h, const double* w_h, const int32_t* idx_w, const double* w_w, uint8_t* lr_u8, double* lr_f64, void* stream);
+int dasr_imresize_up(const void* x, int32_t x_f64, int32_t N, int32_t C, int32_t h, int32_t w, int32_t s, const int32_t* idx_h, const double* w_h, const int32_t* idx_w,
+                     const double* w_w, void* dst, int32_t mode, void* stream);
+
 /* ---- profiling session (bench.py `roofline`) -----------------------------------------------------------
  * Between dasr_prof_begin and dasr_prof_end every kernel launch of the library (up to `capacity`) carries its own start/stop
  * events on its launch stream (hipExtLaunchKernel: the dispatch's begin/end timestamps, what rocprofv3 --kernel-trace prints).
