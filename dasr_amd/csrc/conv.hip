@@ -1026,6 +1026,163 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv_glds_kernel(con
 }
 
 // ---------------------------------------------------------------------------------------------------
+// conv_subpix_dgrad_kernel: data gradient of nearest-x2 + 3x3 (upconv_blcok, block.py:854-861) in its sub-pixel form on f16 tensors
+// (dasr_conv_params::ups == 2).  The input is the gradient g on the (2 Hout) x (2 Wout) grid, the output lives on the Hout x Wout grid:
+//   out[m][n] = sum over the four parities (py, px) and the taps (a, b) of a 2x2 kernel  Wp[py][px][a][b] . g[2 (m - py + a) + py][2 (n - px + b) + px]
+// where Wp are the 16 tap sums of the transposed 3x3 weights (PackRegistry tapmasks, rounded to f16 once): 16 MFMA steps per 16-channel
+// chunk into ONE accumulator set instead of 36 on four times the pixels, no gradient tensor at the high resolution and no 2x2 sum behind it.
+// A pipeline stage is one (chunk, parity) pair: the DMA de-interleaves that parity's sub-grid of the tile -- 17 x 33 pixels for a tile of
+// 16 x 32 outputs -- into the LDS image layout of conv_glds_kernel (every lane chooses which global 16 bytes it fetches), so the fragment
+// addressing carries over; the two x-parities of a row are consecutive stages and share their 64-byte runs in the L2.  Per stage 20 KB of
+// activations + 4 MT KB of weights, double-buffered: 56 KB at MT 2, two workgroups per CU.  Zero padding of g is the buffer's range check.
+// ---------------------------------------------------------------------------------------------------
+template <int MT>
+struct SCfg {
+    static constexpr int NT = 4, NTH = 256, TH = 16, TW = 32, IH = TH + 1, IW = TW + 1, NPIX = IH * IW;
+    static constexpr int AR = (NPIX * 2 + NTH - 1) / NTH;      // activation DMA pieces per thread (16 B each)
+    static constexpr int ACT_BYTES = AR * NTH * 16;            // >= NPIX * 32
+    static constexpr int WPIECE = 4 * MT * 64;                 // 16-byte pieces of a stage's weights (2x2 taps)
+    static constexpr int WR = (WPIECE + NTH - 1) / NTH;
+    static constexpr int W_BYTES = WPIECE * 16;
+    static constexpr int BUF_BYTES = ACT_BYTES + W_BYTES;
+    static constexpr int LDS_BYTES = 2 * BUF_BYTES;
+};
+
+// one 16-byte-per-lane DMA piece of stage sk = 4 * chunk + parity: piece i < AR activations of plane ckp, else weights
+template <int MT>
+__device__ __forceinline__ void subpix_dma_piece(int i, int sk, char* buf, __amdgpu_buffer_rsrc_t rin, __amdgpu_buffer_rsrc_t rw, const unsigned* gbase,
+                                                 const unsigned* vbits, unsigned par_delta, unsigned in_chunk_bytes, int wave, int tid) {
+    using C = SCfg<MT>;
+    typedef __attribute__((address_space(3))) void* lds_ptr;
+    if (i < C::AR) {
+        const unsigned off = ((vbits[i] >> (sk & 3)) & 1u) ? gbase[i] - par_delta : OOB;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rin, (lds_ptr)(buf + (i * C::NTH + wave * 64) * 16), 16, off, (unsigned)(sk >> 2) * in_chunk_bytes, 0, 0);
+    } else {
+        const int r = i - C::AR;
+        if (r * C::NTH + wave * 64 < C::WPIECE)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr)(buf + C::ACT_BYTES + (r * C::NTH + wave * 64) * 16), 16, (unsigned)(tid + r * C::NTH) * 16u,
+                                                     (unsigned)sk * (4u * MT * 1024u), 0, 0);
+    }
+}
+
+template <int MT, int EPI>
+__global__ __launch_bounds__(256, 2) void conv_subpix_dgrad_kernel(const dasr_conv_params p) {
+    using C = SCfg<MT>;
+    constexpr int NT = C::NT;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int cout_tiles = (p.cout + 31) >> 5;
+    const int MG = (cout_tiles + MT - 1) / MT;
+    const int tiles_x = (p.Wout + C::TW - 1) / C::TW, tiles_y = (p.Hout + C::TH - 1) / C::TH;
+    int bid = blockIdx.x;
+    {   // XCD-aware tile order (as conv_glds_kernel): neighbouring tiles, which share halo lines, on one XCD
+        const int total = (int)gridDim.x;
+        const int remapped = (bid & 7) * (total >> 3) + (bid >> 3);
+        bid = ((p.xcd_remap & 1) && (total & 7) == 0) ? remapped : bid;
+    }
+    const int mg = bid % MG;
+    bid /= MG;
+    const int tx = bid % tiles_x;
+    bid /= tiles_x;
+    const int ty = bid % tiles_y;
+    const int n = bid / tiles_y;
+    const int oy0 = ty * C::TH, ox0 = tx * C::TW;
+    const int nstages = (p.cin >> 4) * 4;
+    float bias_reg = 0.f;
+    {
+        const int oc = mg * MT * 32 + tid;
+        const unsigned bo = ((p.bias != nullptr) & (tid < 32 * MT) & (oc < p.cout)) ? (unsigned)oc * 4u : OOB;
+        bias_reg = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(make_rsrc(p.bias), bo, 0, 0));
+    }
+    // ---- DMA source offsets: piece q = tid + 256 r -> LDS slot q -> sub-image pixel pp = q >> 1 = (iy, ix), stored half q & 1 holds channel half
+    // (q & 1) ^ bit3(pp).  Parity (py, px) reads sub-grid pixel (oy0 + iy - py, ox0 + ix - px), i.e. pixel (2 (oy0 + iy) - py, 2 (ox0 + ix) - px) of g:
+    // gbase is the byte offset at parity (0, 0), the parity shifts it by (py Win + px) pixels; vbits bit (2 py + px): inside the sub-grid
+    unsigned gbase[C::AR], vbits[C::AR];
+#pragma unroll
+    for (int r = 0; r < C::AR; ++r) {
+        const int q = tid + r * C::NTH;
+        const int pp = q >> 1, h = (q & 1) ^ ((pp >> 3) & 1);
+        const int iy = pp / C::IW, ix = pp - iy * C::IW;
+        const int sy = oy0 + iy, sx = ox0 + ix;
+        const bool in = pp < C::NPIX;
+        const bool y0 = sy < p.Hout, y1 = (sy >= 1) & (sy <= p.Hout), x0 = sx < p.Wout, x1 = (sx >= 1) & (sx <= p.Wout);
+        vbits[r] = in ? ((unsigned)(y0 & x0) | ((unsigned)(y0 & x1) << 1) | ((unsigned)(y1 & x0) << 2) | ((unsigned)(y1 & x1) << 3)) : 0u;
+        // (unsigned arithmetic: slots of a partial tile beyond the image may wrap, they are never used -- vbits selects the out-of-range offset)
+        gbase[r] = ((2u * (unsigned)sy * (unsigned)p.Win + 2u * (unsigned)sx) * 16u + 8u * (unsigned)h) * 2u;
+    }
+    const __amdgpu_buffer_rsrc_t rin = make_rsrc((const bf16_t*)p.in.p + (size_t)n * p.in.n_stride);
+    const unsigned in_chunk_bytes = (unsigned)(p.in.cb_stride * 2);
+    const __amdgpu_buffer_rsrc_t rw = make_rsrc((const bf16_t*)p.w + (size_t)mg * nstages * 4 * MT * 512);
+    const unsigned row_bytes = (unsigned)p.Win * 32u;
+    constexpr int NP = C::AR + C::WR;
+#pragma unroll
+    for (int i = 0; i < NP; ++i) subpix_dma_piece<MT>(i, 0, smem, rin, rw, gbase, vbits, 0u, in_chunk_bytes, wave, tid);
+    // ---- fragment read addresses: row rr (0..4) of this wave's 5 sub-image rows, column shift b; lane (nn, kh2)
+    const int nn = lane & 31, kh2 = lane >> 5;
+    int baddr[5][2];
+#pragma unroll
+    for (int rr = 0; rr < 5; ++rr)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const int pp = (wave * NT + rr) * C::IW + nn + b;
+            baddr[rr][b] = ((pp << 1) + (kh2 ^ ((pp >> 3) & 1))) << 4;
+        }
+    const int aoff = lane * 16;   // relative to the stage's weight image
+
+    f32x16 acc[MT][NT];
+#pragma unroll
+    for (int mi = 0; mi < MT; ++mi)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+            for (int j = 0; j < 16; ++j) acc[mi][nt][j] = 0.f;
+
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this wave's DMA pieces have landed
+    __syncthreads();
+
+    bf16x8 fb[2][5], fa[2][MT];
+    for (int sk = 0; sk < nstages; ++sk) {
+        const char* buf = smem + (sk & 1) * C::BUF_BYTES;   // activation image of this (chunk, parity)
+        const char* wbuf = buf + C::ACT_BYTES;              // its 2x2 taps
+        char* nbuf = smem + ((sk + 1) & 1) * C::BUF_BYTES;
+        const bool more = sk + 1 < nstages;
+        const unsigned ndelta = (((sk + 1) >> 1) & 1) * row_bytes + ((sk + 1) & 1) * 32u;   // parity of the next stage: py = bit 1, px = bit 0
+        // step s = b * 2 + a (tap row a, tap column b; packed tap a * 2 + b); B rows of column shift b live in fb[b], A of step s in fa[s & 1]
+#pragma unroll
+        for (int rr = 0; rr < 5; ++rr) fb[0][rr] = *(const bf16x8*)(buf + baddr[rr][0]);
+#pragma unroll
+        for (int mi = 0; mi < MT; ++mi) fa[0][mi] = *(const bf16x8*)(wbuf + aoff + (0 * MT + mi) * 1024);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int b = s >> 1, a = s & 1;
+            if (s + 1 < 4) {
+                const int b1 = (s + 1) >> 1, a1 = (s + 1) & 1;
+#pragma unroll
+                for (int mi = 0; mi < MT; ++mi) fa[(s + 1) & 1][mi] = *(const bf16x8*)(wbuf + aoff + ((a1 * 2 + b1) * MT + mi) * 1024);
+                if (s == 0) {   // rows of the second column shift, requested one step before they are needed
+#pragma unroll
+                    for (int rr = 0; rr < 5; ++rr) fb[1][rr] = *(const bf16x8*)(buf + baddr[rr][1]);
+                }
+            }
+            if (more && s < 2) {   // the next stage is requested in the first steps: it has the rest of this one to land
+#pragma unroll
+                for (int i = s * NP / 2; i < (s + 1) * NP / 2; ++i) subpix_dma_piece<MT>(i, sk + 1, nbuf, rin, rw, gbase, vbits, ndelta, in_chunk_bytes, wave, tid);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int mi = 0; mi < MT; ++mi)
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+                    acc[mi][nt] = mfma16<true>(fa[s & 1][mi], fb[b][nt + a], acc[mi][nt]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        __builtin_amdgcn_s_waitcnt(0x0F70);
+        __syncthreads();
+    }
+    conv_epilogue<false, MT, NT, 1, EPI, 1, false>(p, acc, smem, bias_reg, tid, mg, n, oy0, ox0, nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------------
 // conv_chain_kernel (round 4): a CHAIN of dense-block convs in ONE persistent launch -- the forward trunk of the generator
 // (conv1-4 + conv5 of every RDB, 5 x 3 x nb layers of the same geometry) without a kernel boundary between layers.
 //
@@ -1340,6 +1497,49 @@ int launch_glds(const dasr_conv_params& p, hipStream_t s) {
     return (int)hipGetLastError();
 }
 
+// dasr_conv_params::ups == 2: the sub-pixel data gradient of nearest-x2 + 3x3 on f16 tensors (conv_subpix_dgrad_kernel)
+template <int MT, int EPI>
+int launch_subpix_dgrad(const dasr_conv_params& p, hipStream_t s) {
+    using C = SCfg<MT>;
+    static bool attr_set = false;
+    auto kfn = conv_subpix_dgrad_kernel<MT, EPI>;
+    if (!attr_set) {
+        HIP_TRY(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES));
+        attr_set = true;
+    }
+    const int cout_tiles = (p.cout + 31) >> 5;
+    const int MG = (cout_tiles + MT - 1) / MT;
+    const int tiles_x = (p.Wout + C::TW - 1) / C::TW, tiles_y = (p.Hout + C::TH - 1) / C::TH;
+    const long long grid = (long long)MG * tiles_x * tiles_y * p.N;
+    if (grid <= 0 || grid >= (1LL << 31)) return DASR_EINVAL;
+    DASR_LAUNCH_TAG(__PRETTY_FUNCTION__, kfn, dim3((unsigned)grid), dim3(C::NTH), C::LDS_BYTES, s, p);
+    return (int)hipGetLastError();
+}
+
+int classify_epi(const dasr_conv_params& p);
+
+int subpix_dgrad(const dasr_conv_params& p, hipStream_t s) {
+    if (p.in_f32 || p.prec != 2 || p.kh != 3 || p.stride != 1 || p.pad != 1 || (p.pad_x >= 0 && p.pad_x != 1) || p.in_stride > 1 || p.out_stride > 1) return DASR_EINVAL;
+    if (p.Hout <= 0 || p.Wout <= 0 || p.N <= 0 || p.Hin != 2 * p.Hout || p.Win != 2 * p.Wout) return DASR_EINVAL;
+    if (p.in_wrap || p.out16_lo || p.res1_lo || p.prelu_part) return DASR_EINVAL;
+    if (p.mt != 1 && p.mt != 2) return DASR_EINVAL;
+    // epilogue terms of a data gradient, and no others: LeakyReLU' mask (constant slope), alpha / gamma, fp32 and / or f16 output on the dense low-resolution grid
+    if (p.bias || p.act || p.res1.p || p.res2.p || p.slope_ptr || p.out_oy || p.out_ox || p.out_W) return DASR_EINVAL;
+    if (!p.out_f32.p && !p.out_bf16.p) return DASR_EINVAL;
+    if (p.out_bf16.p && !p.out16_f16) return DASR_EINVAL;   // the 16-bit output format of this kernel is f16, its operand format
+    // 32-bit byte offsets inside one image: a plane of g, and the planes of one image together
+    if ((long long)(p.Hin + 1) * p.Win * 32 > 0x7fffffffLL || (long long)(p.cin >> 4) * p.in.cb_stride * 2 > 0xffffffffLL) return DASR_EINVAL;
+    const int e = classify_epi(p);
+    if (p.mt == 2) {
+        switch (e) {
+            case 68: return launch_subpix_dgrad<2, 68>(p, s);     // LeakyReLU' mask -> f16 gradient (upconv2)
+            case 160: return launch_subpix_dgrad<2, 160>(p, s);   // alpha -> fp32 gradient of the trunk output (upconv1)
+            default: return launch_subpix_dgrad<2, 0>(p, s);
+        }
+    }
+    return launch_subpix_dgrad<1, 0>(p, s);
+}
+
 template <int PREC, bool IN_F32, int MT, int KH, int STRIDE, int NT, int KS = 1, bool DBUF = false, int MODE = 0, int EPI = 0>
 int launch(const dasr_conv_params& p, hipStream_t s) {
     // KS / DBUF / MODE stay in the signature only because bench.py and profiles/pmc_*.json key on the printed name (conv_kernel<3, true, 1, 3, 1, 4, 1, false, 0, 0>)
@@ -1599,6 +1799,7 @@ extern "C" int dasr_conv(const dasr_conv_params* pp, void* stream) {
     if (p.kh < 1 || p.kh > 5) return DASR_EINVAL;
     if (p.mask.p && (p.mask_f32 != 0) != (p.in_f32 != 0)) return DASR_EINVAL;  // mask dtype is tied to the input dtype
     if (p.ups && !p.in_f32 && p.prec != 2) return DASR_EINVAL;
+    if (p.ups == 2) return subpix_dgrad(p, s);
     if (p.in_wrap < 0 || p.out16_lo < 0 || p.res1_lo < 0) return DASR_EINVAL;
     if (p.in_wrap || p.out16_lo || p.res1_lo) {   // split 16-bit tensors: the LDS-DMA kernel only (a 16-bit input, 3x3 / stride 1 / pad 1, one-pass precisions)
         if (p.in_f32 || p.kh != 3 || p.stride != 1 || p.pad != 1 || !(p.prec == 1 || p.prec == 2) || p.ups || p.out_stride > 1) return DASR_EINVAL;

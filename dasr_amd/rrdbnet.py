@@ -21,6 +21,14 @@ GC = 32  # growth channels are hard-wired to 32 in the reference (architecture.p
 _SUBPIXEL_ROWS = {0: ((0,), (1, 2)), 1: ((0, 1), (2,))}
 
 
+def subpixel_dgrad_tapmasks():
+    """tap masks (bit ky * 3 + kx of the 3x3 kernel) of the 16 packed taps of the sub-pixel DATA GRADIENT of nearest-x2 + 3x3 in one launch
+    (dasr_conv_params ups = 2): packed tap 4 (2 py + px) + 2 a + b is the sum of the 3x3 taps that carry gradient pixel
+    (2 (m - py + a) + py, 2 (n - px + b) + px) to input pixel (m, n) -- the forward taps of parity (py, px) in reversed order."""
+    rows = _SUBPIXEL_ROWS
+    return [sum(1 << (ky * 3 + kx) for ky in rows[py][1 - a] for kx in rows[px][1 - b]) for py in (0, 1) for px in (0, 1) for a in (0, 1) for b in (0, 1)]
+
+
 def rrdbnet_param_spec(in_nc, out_nc, nf, nb, upsample_mode='upconv'):
     """state_dict keys / shapes of the reference RRDBNet.  upsample_mode 'upconv' (what define_G selects,
     networks.py:96-99): nearest x2 -> conv nf->nf -> LeakyReLU at model.{2,3,4} / {5,6,7}; 'pixelshuffle' (block.py:838-851): conv nf->4nf
@@ -121,8 +129,14 @@ class RRDBNetHIP:
         if self.hr_f16s:   # direct 3x3 forms on 16-bit tensors (nearest x2 folded into the DMA addresses of the dense-conv kernel)
             mtH = 2 if nf % 64 == 0 else 1
             ups = (('up1', 'model.2.weight', 4 * nf), ('up2', 'model.5.weight', 4 * nf)) if self.ps else (('up1', 'model.3.weight', nf), ('up2', 'model.6.weight', nf))
+            # The data gradient of a nearest-x2 upconv runs in its sub-pixel form, one launch on the low-resolution grid (dasr_conv_params ups = 2): its
+            # pack is ONE 16-tap image of sums of the transposed 3x3 taps, formed from the fp32 masters and rounded to f16 once.
+            bw16 = subpixel_dgrad_tapmasks()
             for name, key, co in ups + (('hr0', 'model.8.weight', nf),):
                 self.pk[name] = self.pack.add(co, nf, 9, mtH, 2, [self._seg_fwd(key, co, nf)])
+                if not self.ps and name != 'hr0':
+                    self.pk[name + '_b'] = self.pack.add(nf, nf, 16, mtH, 2, [(P.off(key), nf, nf, 0, nf, 0, 1)], tapmap=[0] * 16, src_ntaps=9, tapmasks=bw16)
+                    continue
                 self.pk[name + '_b'] = self.pack.add(nf, co, 9, mtH, 2, [(P.off(key), co, nf, 0, co, 0, 1)])
             self.pk['hr1'] = self.pack.add(self.out_nc, nf, 9, 1, 2, [self._seg_fwd('model.10.weight', self.out_nc, nf)])
             self.pk['hr1_b'] = self.pack.add(nf, 16, 9, mtH, 2, [(P.off('model.10.weight'), self.out_nc, nf, 0, self.out_nc, 0, 1)])
@@ -462,7 +476,7 @@ class _Plan:
         self.g4a = Bh(nf, H4, W4)
         self.g4b = Bh(nf, H4, W4)
         self.g2a = Bh(nf, H2, W2)
-        self.g2b = Bh(nf, H2, W2)
+        self.g2b = None if hs else Bh(nf, H2, W2)   # (f16 storage: no gradient tensor of upconv1's up-sampled input, see _build_backward_tail_f16)
         self.g_t0 = B(nf, h, w, True)
         self.gstream = [B(nf, h, w, True) for _ in range(4)]
         # one gradient slab per RDB (kept for the deferred weight-gradient phase), in the order the backward chain visits them (RDB 3 nb - 1 first)
@@ -715,18 +729,13 @@ class _Plan:
         grp.emit(ops, self.ws, self.net.device, self.grad.data_ptr(), target_wgs=self._wg3_target(len(grp.parts)))
 
     def _build_backward_tail_f16(self, ops):
-        """HR tail in f16 storage: every gradient tensor holds gscale * dL/d(.) in f16; the last 2x2 down-sum hands dL/d(trunk output) back in
+        """HR tail in f16 storage: every gradient tensor holds gscale * dL/d(.) in f16; the data gradient of upconv1 hands dL/d(trunk output) back in
         f32, un-scaled"""
         net, N, h, w = self.net, self.N, self.h, self.w
         nf, pack, pk, gs = net.nf, net.pack, net.pk, self.gscale
         H2, W2, H4, W4 = 2 * h, 2 * w, 4 * h, 4 * w
-        g_h0, g_u2, g_up2, g_u1, g_up1 = self.g4a, self.g4b, self.g4a, self.g2a, self.g2b
+        g_h0, g_u2, g_u1 = self.g4a, self.g4b, self.g2a
         sl = net.act_slope
-
-        def downsum(src, hl, wl, mask, dst_f32, dst_f16, out_scale):
-            ops.add(make_op(_lib.OP_DOWNSUM_F16, src=src.view(), N=N, C=nf, H=hl, W=wl, mask=mask and mask.view(), slope=sl, out_scale=out_scale,
-                            dst_f32=dst_f32 and dst_f32.view(), dst_f16=dst_f16 and dst_f16.view()))
-
         ops.add(make_op(_lib.OP_CVT_F16, x=self.g_sr.view(), N=N, C=net.out_nc, H=H4, W=W4, scale=gs, y=self.g_sr16.view()))
         # HR_conv1
         self._wg3(ops, 'model.10.', self.g_sr16, self.h0, net.out_nc, nf, H4, W4, H4, W4)
@@ -747,14 +756,15 @@ class _Plan:
                 else:
                     ops.add(conv_op(pack, pk[name + '_b'], g_pre.view(), False, 4 * nf, hl, wl, hl, wl, N, out_bf16=g_lo.view(), out16_f16=1))
             return
-        # upconv2: weight gradient on the up-sampled u1; data gradient on the 4h x 4w grid, then the 2x2 sum with LeakyReLU'(u1)
+        # upconv2: weight gradient on the up-sampled u1; data gradient in its sub-pixel form: ONE launch on the 2h x 2w grid sums the four parities'
+        # 2x2 transposed convs of g_u2 and applies LeakyReLU'(u1) (no gradient tensor on the 4h x 4w grid, no 2x2 sum behind it); FLOPs as the 3x3 form
         self._wg3(ops, 'model.6.', g_u2, self.u1, nf, nf, H2, W2, H4, W4, ups=1)
-        ops.add(conv_op(pack, pk['up2_b'], g_u2.view(), False, nf, H4, W4, H4, W4, N, out_bf16=g_up2.view(), out16_f16=1))
-        downsum(g_up2, H2, W2, self.u1, None, g_u1, 1.0)
-        # upconv1: its input is the (linear) trunk output: no mask; the sum leaves the f16 / scaled domain
+        ops.add(conv_op(pack, pk['up2_b'], g_u2.view(), False, nf, H4, W4, H2, W2, N, ups=2, mask=self.u1.view(), mask_f32=0, slope=sl, out_bf16=g_u1.view(),
+                        out16_f16=1, flops=2.0 * N * H4 * W4 * 9 * nf * nf))
+        # upconv1: its input is the (linear) trunk output: no mask; the result leaves the f16 / scaled domain
         self._wg3(ops, 'model.3.', g_u1, self.t0h, nf, nf, h, w, H2, W2, ups=1)
-        ops.add(conv_op(pack, pk['up1_b'], g_u1.view(), False, nf, H2, W2, H2, W2, N, out_bf16=g_up1.view(), out16_f16=1))
-        downsum(g_up1, h, w, None, self.g_t0, None, 1.0 / gs)
+        ops.add(conv_op(pack, pk['up1_b'], g_u1.view(), False, nf, H2, W2, h, w, N, ups=2, alpha=1.0 / gs, out_f32=self.g_t0.view(),
+                        flops=2.0 * N * H2 * W2 * 9 * nf * nf))
 
     def _build_backward_tail_f32(self, ops, f16, gs):
         net, N, h, w = self.net, self.N, self.h, self.w

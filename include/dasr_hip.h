@@ -35,7 +35,7 @@ typedef struct {
  * Replaces nn.Conv2d fwd (+bias, +LeakyReLU/ReLU, + residual scale-add) of conv_block
  * (codes/SRN/models/modules/block.py:130-156), the torch.cat of ResidualDenseBlock_5C
  * (block.py:280-286: input = first cin/16 planes of a dense slab, output written into its own
- * planes), nn.Upsample(nearest,2) of upconv_blcok (block.py:854-861, `ups`), the 4x4 convs of
+ * planes), nn.Upsample(nearest,2) of upconv_blcok (block.py:854-861, `ups` = 1; its data gradient, `ups` = 2), the 4x4 convs of
  * NLayerDiscriminator (architecture.py:983-1024) and VGG19 convs (architecture.py:1060-1088).
  * The data-gradient of a stride-1 conv is the same op on flipped/transposed packed weights
  * with `mask` = forward activation (LeakyReLU'/ReLU').
@@ -49,6 +49,14 @@ typedef struct {
  */
 typedef struct {
     dasr_tensor in;  int32_t in_f32;  int32_t Hin, Win;  int32_t ups;  int32_t cin; /* cin % 16 == 0 */
+    /* ups: 0 plain conv; 1 the input is nearest-x2 up-sampled on the fly (Hout x Wout = (2 Hin) x (2 Win));
+     * 2: the DATA GRADIENT of nearest-x2 + 3x3 (upconv_blcok, block.py:854-861) in its sub-pixel form, one launch: `in` is the f16 gradient on the
+     * Hin x Win = (2 Hout) x (2 Wout) grid, the output (and the mask) live on the Hout x Wout grid of the conv's low-resolution input;
+     * out[m][n] = sum over parities (py, px) and 2x2 taps (a, b) of Wp[2 py + px][2 a + b] . in[2 (m - py + a) + py][2 (n - px + b) + px], zero outside.
+     * `w`: 16 packed taps, 4 (2 py + px) + 2 a + b, each the sum of the transposed 3x3 taps that meet the same gradient pixel (dasr_pack_desc::tapmask).
+     * f16 tensors only (in_f32 0, prec 2, kh 3 / stride 1 / pad 1, a 16-bit output is f16, no split tensors).  Epilogue terms: `mask` with the constant
+     * `slope`, alpha / gamma, out_f32 and / or the f16 out_bf16 on the dense grid; bias, act, res1 / res2, slope_ptr, prelu_part and a strided output
+     * (out_stride, out_oy, out_ox, out_W) are DASR_EINVAL.  (A value of an existing field: the struct and DASR_ABI_VERSION are unchanged.) */
     const void* w;   int64_t w_lo_off;      /* packed bf16 weights (dasr_pack_weights); lo plane offset (elements) for prec 3 */
     const float* bias;                      /* [cout] or NULL */
     int32_t cout, Hout, Wout, N;
