@@ -836,6 +836,34 @@ int dasr_windows_down_u8(const uint8_t* src, int32_t H, int32_t W, const dasr_wi
 int dasr_imresize_up(const void* x, int32_t x_f64, int32_t N, int32_t C, int32_t h, int32_t w, int32_t s, const int32_t* idx_h, const double* w_h, const int32_t* idx_w,
                      const double* w_w, void* dst, int32_t mode, void* stream);
 
+/* ---- dataset corruption: JPEG round trip and rounded Gaussian noise on resident 8-bit images (csrc/corrupt.hip) -------------------------
+ * codes/DSN/add_corruptions.py on the device (dasr_amd/corrupt.py, `python -m dasr_amd.add_corruptions`).  Images are uint8 [N][H][W][3] interleaved RGB, any H, W >= 1.
+ * Integer arithmetic (int32) and plain vector loads and stores, no atomics, asynchronous on `stream`, nothing is synchronised, same inputs give the same bits.
+ *
+ * dasr_jpeg_blocks + dasr_jpeg_merge: what Image.save(f, 'JPEG', quality=q) followed by Image.open gives back with libjpeg-turbo, bit for bit, without the entropy
+ * coder: baseline, 4:2:0, the slow-integer DCT (jfdctint.c / jidctint.c), Annex K tables scaled as jpeg_set_quality does, h2v2 "fancy" up-sampling (plain replication
+ * when the chroma plane is at most 2 samples wide).  corrupt.jpeg_roundtrip_ref states every step.
+ * dasr_jpeg_blocks writes the DECODED planes of every image into `planes` (8-byte aligned), per image DASR_JPEG_PLANE_BYTES(H, W) bytes: Y [ceil8(H)][ceil8(W)], then
+ * Cb and Cr [ceil8(ceil(H / 2))][ceil16(W) / 2].  One 8 x 8 block per 8 lanes (DASR_JPEG_BLOCKS_PER_WG blocks per workgroup): RGB bytes -> YCbCr -> 2 x 2 chroma average
+ * -> forward DCT, quantise, dequantise, inverse DCT; coefficients stay in registers and LDS.  Edges: columns repeat the last column up to a multiple of 16 before the
+ * average; rows get at most one repeated row (odd H) before it, and the averaged chroma plane repeats its last row down to a multiple of 8; Y repeats its last row.
+ * Rows of 3 W bytes are read as aligned 4-byte words where src is 4-byte aligned and the run lies inside the row, byte by byte elsewhere.
+ * dasr_jpeg_merge reads those planes: chroma up-sampling, YCbCr -> RGB, clamp, interleaved bytes to dst [N][H][W][3].
+ *
+ * dasr_noise_u8: dst[n][e] = clip(src[n][e] + rint(std z), 0, 255), e < per (= H W 3), rint to nearest even.  z: Philox4x32-10 with key `seed` (low word, high word) and
+ * counter (g lo, g hi, index0 + n, 0) for the group g = e / 4; its outputs x0 .. x3 give z of e = 4 g .. 4 g + 3 as two Box-Muller pairs in fp64: u1 = (x0 + 1) 2^-32,
+ * u2 = x1 2^-32, sqrt(-2 ln u1) cos(2 pi u2) and ... sin(2 pi u2); x2, x3 likewise.  dst may be src.
+ *
+ * A null pointer, N outside 1 .. 65535, a side outside 1 .. 65535, quality outside 1 .. 100, planes not 8-byte aligned, planes equal to src / dst, per < 1 or above
+ * 2^36, std negative or not finite, index0 < 0 or index0 + N > 2^32: DASR_EINVAL, nothing is launched. */
+#define DASR_JPEG_BLOCKS_PER_WG 32
+#define DASR_JPEG_CEIL(v, m) (((v) + (m) - 1) / (m) * (m))
+#define DASR_JPEG_PLANE_BYTES(H, W) \
+    ((int64_t)DASR_JPEG_CEIL(H, 8) * DASR_JPEG_CEIL(W, 8) + 2 * (int64_t)DASR_JPEG_CEIL(((H) + 1) / 2, 8) * (DASR_JPEG_CEIL(W, 16) / 2))
+int dasr_jpeg_blocks(const uint8_t* src, int32_t N, int32_t H, int32_t W, int32_t quality, uint8_t* planes, void* stream);
+int dasr_jpeg_merge(const uint8_t* planes, int32_t N, int32_t H, int32_t W, uint8_t* dst, void* stream);
+int dasr_noise_u8(const uint8_t* src, uint8_t* dst, int32_t N, int64_t per, double std, int64_t seed, int64_t index0, void* stream);
+
 /* ---- profiling session (bench.py `roofline`) -----------------------------------------------------------
  * Between dasr_prof_begin and dasr_prof_end every kernel launch of the library (up to `capacity`) carries its own start/stop
  * events on its launch stream (hipExtLaunchKernel: the dispatch's begin/end timestamps, what rocprofv3 --kernel-trace prints).
