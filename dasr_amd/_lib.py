@@ -314,6 +314,10 @@ _SIGS = {
     'dasr_jpeg_blocks': [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp],
     'dasr_jpeg_merge': [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp],
     'dasr_noise_u8': [c_vp, c_vp, c_i32, c_i64, C.c_double, c_i64, c_i64, c_vp],
+    'dasr_png_filter': [c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp],
+    'dasr_png_codes': [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp],
+    'dasr_png_emit': [c_vp, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp],
+    'dasr_png_pack': [c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp],
     'dasr_prof_begin': [c_i32],
     'dasr_prof_end': [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp],
 }

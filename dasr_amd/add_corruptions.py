@@ -2,7 +2,7 @@
 
     python -m dasr_amd.add_corruptions [--noise_std_dev 8.0] [--blur_std_dev None] [--jpg_quality 30] [--artifacts gaussian] [--dataset df2k] [--resolution hr|lr]
                                        [--paths paths.yml | --input_dir IN --output_dir OUT [--input_dir IN2 --output_dir OUT2 ...]]
-                                       [--seed 0] [--num_workers 6] [--overwrite]
+                                       [--seed 0] [--num_workers 6] [--overwrite] [--device_png]
 
 The flags of the reference with its defaults; the literal None (any case) switches a stage off (the reference's README passes `--noise_std_dev None`, which its own
 type=float cannot parse).  The folders come from the yaml file as the reference reads it, [dataset]['clean'][resolution]['train' | 'valid'] ->
@@ -12,7 +12,9 @@ Every image file of an input folder is decoded on host threads (PIL, imgio.decod
 noise -> blur -> JPEG: corrupt.gaussian_noise (one launch; image index = position of the file in the sorted list of its folder, so a file does not depend on thread
 counts or on the other files) and corrupt.jpeg_roundtrip (two launches; equal, bit for bit, to PIL's save + open with libjpeg-turbo) on the device.  --blur_std_dev is
 PIL's own extended box blur (ImageFilter.GaussianBlur), run on the host exactly as the reference runs it: one read-back and re-upload for that file, logged once.  The
-result is read back once and written as PNG under the input's base name on the host threads.
+result is read back once and written as PNG under the input's base name on the host threads.  With --device_png the file is encoded on the device instead
+(png.write_batch: no read-back of the raw bytes, no PIL encode; the host threads add the container and the checksums); not together with --blur_std_dev, whose result
+is made on the host.
 
 The noise is NOT the reference's stream: utils.gaussian_noise draws from numpy's unseeded global generator, so its files differ from run to run; here they are a
 function of --seed (corrupt.gaussian_noise_ref).
@@ -54,6 +56,7 @@ def parse_args(argv=None):
     p.add_argument('--seed', default=0, type=int, help='64-bit key of the noise generator')
     p.add_argument('--num_workers', default=6, type=int, help='decode / encode threads (at most %d)' % imgio.MAX_DECODE_THREADS)
     p.add_argument('--overwrite', action='store_true', help='write into output folders that already hold files')
+    p.add_argument('--device_png', action='store_true', help='encode the PNG files on the device (png.write_batch) instead of with PIL on the host threads')
     return p.parse_args(argv)
 
 
@@ -84,6 +87,8 @@ def plan(o):
             raise ValueError('--jpg_quality must lie in 1 .. 100, got %r' % (o.jpg_quality,))
     if o.noise_std_dev is not None and not 0.0 <= o.noise_std_dev < float('inf'):
         raise ValueError('--noise_std_dev must be finite and not negative, got %r' % (o.noise_std_dev,))
+    if getattr(o, 'device_png', False) and o.blur_std_dev is not None:
+        raise ValueError('--device_png cannot be combined with --blur_std_dev: the blurred image is made by PIL on the host')
     if o.blur_std_dev is not None and not 0.0 <= o.blur_std_dev < float('inf'):
         raise ValueError('--blur_std_dev must be finite and not negative, got %r' % (o.blur_std_dev,))
     work = []
@@ -105,6 +110,8 @@ def plan(o):
                 raise ValueError('%s: mode %s, expected an 8-bit RGB image' % (path, mode))
             if H > 65535 or W > 65535:
                 raise ValueError('%s: %d x %d, a side above 65535' % (path, H, W))
+            if getattr(o, 'device_png', False) and W > 21844:
+                raise ValueError('%s: --device_png encodes rows of at most 21844 pixels, this file has %d (leave the flag out: PIL encodes on the host)' % (path, W))
             files.append((path, os.path.join(dst, name), index, H, W))
         work.append((dst, files))
     return work
@@ -128,16 +135,19 @@ def _blur_host(dev_img, std):
 
 def run(o, times=None):
     """main behind the argument parser.  `times`: a list that receives one dict of seconds per file ('decode' as the consumer waits for it, 'upload', 'kernels', 'blur',
-    'readback', 'submit' and 'encode_wait', the consumer's wait for the encoders); the device stages are then synchronised one by one, which an ordinary run does not do."""
+    'readback', 'submit' and 'encode_wait', the consumer's wait for the encoders; with --device_png 'device_png' in place of 'readback' and 'submit'); the device stages are then synchronised one by one, which an ordinary run does not do."""
     import torch
-    from . import corrupt
+    from . import corrupt, png
     work = plan(o)
+    device_png = getattr(o, 'device_png', False)
     device = imgio.device_of(None)
     for dst, _ in work:
         util.mkdir(dst)
     written = []
     threads = max(1, min(imgio.MAX_DECODE_THREADS, int(o.num_workers)))
     clock = time.perf_counter
+    if device_png:
+        print('--device_png: the PNG files are encoded on the device (filter, Huffman-only deflate), the host adds the container and the checksums')
     if o.blur_std_dev is not None:
         print('--blur_std_dev %g: PIL GaussianBlur on the host, one read-back and re-upload per file' % o.blur_std_dev)
 
@@ -177,10 +187,14 @@ def run(o, times=None):
                 if o.jpg_quality is not None:
                     x = corrupt.jpeg_roundtrip(x, o.jpg_quality)
                     t0 = tick(t, 'kernels', t0, True)
-                host = x.cpu().numpy()
-                t0 = tick(t, 'readback', t0)
-                pending.append(enc.submit(_save_png, host, out_path))
-                t0 = tick(t, 'submit', t0)
+                if device_png:
+                    pending.append(png.write_batch([x], [out_path], enc)[0])
+                    t0 = tick(t, 'device_png', t0)
+                else:
+                    host = x.cpu().numpy()
+                    t0 = tick(t, 'readback', t0)
+                    pending.append(enc.submit(_save_png, host, out_path))
+                    t0 = tick(t, 'submit', t0)
                 drain(2 * threads)
                 t0 = clock()
         drain(0)

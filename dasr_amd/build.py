@@ -9,7 +9,7 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libdasr_hip.so')
 SOURCES = ['conv.hip', 'resblock.hip', 'wgrad.hip', 'misc.hip', 'gan.hip', 'lpips.hip', 'metrics.hip', 'imgio.hip', 'rccl.hip']
 # translation units added after tests/test_evaluate_host.py pinned the list above; linked into the same library
-MORE_SOURCES = ['corrupt.hip']
+MORE_SOURCES = ['corrupt.hip', 'png.hip']
 
 
 def _stale():

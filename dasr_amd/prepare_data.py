@@ -2,14 +2,16 @@
 in one pass over the files, on the MI355X (codes/SRN/data/README.md:26-27: DIV2K800 -> DIV2K800_sub, DIV2K800_sub_bicLRx4).
 
     python -m dasr_amd.prepare_data --input_dir HR [--sub_dir D --crop_sz 480 --step 240 --thres_sz 48] [--mod_dir D] [--lr_dir D] [--bic_dir D] [--scale 4]
-                                    [--num_workers 6] [--overwrite]
+                                    [--num_workers 6] [--overwrite] [--device_png]
 
 Every PNG file of --input_dir is decoded once on host threads (PIL, imgio.decode_ahead) and its BYTES are uploaded once.  With --sub_dir the units are the sub-images of
 extract_subimgs_single.py:62-83 (window_grid; written to --sub_dir as name_s001.png, ... in row-major order), without it the whole images.  Every unit is mod-cropped to a
 multiple of --scale, then --mod_dir gets name.png (the mod-cropped bytes), --lr_dir name_bicLRx{s}.png (MATLAB's imresize(., 1 / s) of the unit, written as imwrite
 writes a double image) and --bic_dir name_bicx{s}.png (imresize(., s) of the DOUBLE LR image).  The sub and mod files are byte copies sliced on the host; the LR images of
 all units of a file are ONE dasr_windows_down_u8 launch, their Bic images ONE dasr_imresize_up launch (bicubic.py), one read-back per file and product; the PNG files
-are encoded on host threads (zlib level 3, as extract_subimgs_single.py:19 sets it: the pixels do not depend on it).  The mirror edge of the resampling
+are encoded on host threads (zlib level 3, as extract_subimgs_single.py:19 sets it: the pixels do not depend on it).  With --device_png all products of a file are
+encoded on the device in one png.write_batch (sub and mod as windows of the uploaded image): no read-back of raw bytes, no PIL encode; the host threads add the
+container and the checksums.  It needs --lr_dir or --bic_dir (without them no device is opened).  The mirror edge of the resampling
 is the unit's edge: a file of --lr_dir is what MATLAB makes of the file of --sub_dir, not a crop of the whole image's LR image.
 
 Accepted input is 8-bit RGB.  A grey, palette or alpha file, a file smaller than --crop_sz (the reference script raises IndexError there) or than --scale, no output
@@ -40,6 +42,7 @@ def parse_args(argv=None):
     p.add_argument('--scale', default=4, type=int, help='2, 3 or 4 (generate_mod_LR_bic.m: up_scale = mod_scale = 4)')
     p.add_argument('--num_workers', default=6, type=int, help='decode / encode threads (at most %d)' % imgio.MAX_DECODE_THREADS)
     p.add_argument('--overwrite', action='store_true', help='write into output folders that already hold files')
+    p.add_argument('--device_png', action='store_true', help='encode the PNG files on the device (png.write_batch) instead of with PIL on the host threads')
     return p.parse_args(argv)
 
 
@@ -67,6 +70,8 @@ def plan(o):
         raise ValueError('no output folder given: at least one of --sub_dir, --mod_dir, --lr_dir, --bic_dir')
     if o.scale not in SCALES:
         raise ValueError('--scale must be one of %s, got %d' % (SCALES, o.scale))
+    if getattr(o, 'device_png', False) and 'lr' not in dirs and 'bic' not in dirs:
+        raise ValueError('--device_png needs --lr_dir or --bic_dir: --sub_dir and --mod_dir alone are byte copies made on the host, no device is opened for them')
     if o.crop_sz < 1 or o.step < 1 or o.thres_sz < 0:
         raise ValueError('--crop_sz and --step must be positive and --thres_sz not negative, got %d, %d, %d' % (o.crop_sz, o.step, o.thres_sz))
     if 'sub' in dirs and o.crop_sz < o.scale:
@@ -94,6 +99,8 @@ def plan(o):
             if H < o.scale or W < o.scale:
                 raise ValueError('%s: image %d x %d is smaller than --scale %d' % (path, H, W, o.scale))
             origins, unit = [(0, 0)], (H, W)
+        if getattr(o, 'device_png', False) and unit[1] > 21844:
+            raise ValueError('%s: --device_png encodes rows of at most 21844 pixels, a unit here has %d (leave the flag out: PIL encodes on the host)' % (path, unit[1]))
         files.append((path, os.path.splitext(name)[0], H, W, origins, unit))
     return dirs, files
 
@@ -107,12 +114,15 @@ def _save_rgb(arr, path):
 
 def run(o, times=None):
     """main behind the argument parser.  `times`: a list that receives one dict of seconds per file ('decode' as the consumer waits for it, 'upload', 'down', 'up', 'readback',
-    'submit' and 'encode_wait', the consumer's wait for the encoders); the device stages are then synchronised one by one, which an ordinary run does not do."""
+    'submit' and 'encode_wait', the consumer's wait for the encoders; with --device_png 'device_png', the batch's tables, launches and read-backs, in place of 'readback'); the device stages are then synchronised one by one, which an ordinary run does not do."""
     import numpy as np
     import torch
-    from . import bicubic
+    from . import bicubic, png
     dirs, files = plan(o)
     s = o.scale
+    device_png = getattr(o, 'device_png', False)
+    if device_png:
+        print('--device_png: the PNG files are encoded on the device (filter, Huffman-only deflate), the host adds the container and the checksums')
     device = imgio.device_of(None) if ('lr' in dirs or 'bic' in dirs) else None
     for d in dirs.values():
         util.mkdir(d)
@@ -154,18 +164,33 @@ def run(o, times=None):
                 t0 = tick(t, 'down', t0, True)
                 bic_u8 = bicubic.upsample(lr_f64, s, out='u8') if 'bic' in dirs else None
                 t0 = tick(t, 'up', t0, True)
-                lr_host = lr_u8.cpu().numpy() if 'lr' in dirs else None
-                bic_host = bic_u8.cpu().numpy() if 'bic' in dirs else None
-                t0 = tick(t, 'readback', t0)
-            for k, (unit, (y0, x0)) in enumerate(zip(units, origins)):
-                if 'sub' in dirs:
-                    jobs.append(('sub', enc.submit(_save_rgb, np.ascontiguousarray(img[y0:y0 + uh, x0:x0 + uw]), os.path.join(dirs['sub'], unit + '.png'))))
-                if 'mod' in dirs:
-                    jobs.append(('mod', enc.submit(_save_rgb, np.ascontiguousarray(img[y0:y0 + hh, x0:x0 + ww]), os.path.join(dirs['mod'], unit + '.png'))))
-                if 'lr' in dirs:
-                    jobs.append(('lr', enc.submit(_save_rgb, lr_host[k], os.path.join(dirs['lr'], '%s_bicLRx%d.png' % (unit, s)))))
-                if 'bic' in dirs:
-                    jobs.append(('bic', enc.submit(_save_rgb, bic_host[k], os.path.join(dirs['bic'], '%s_bicx%d.png' % (unit, s)))))
+                if not device_png:
+                    lr_host = lr_u8.cpu().numpy() if 'lr' in dirs else None
+                    bic_host = bic_u8.cpu().numpy() if 'bic' in dirs else None
+                    t0 = tick(t, 'readback', t0)
+            if device_png:
+                # every product of the file in one batch, from the tensors that sit on the device: sub and mod are windows of the uploaded image (pitch descriptors)
+                keys, tensors, paths = [], [], []
+                for k, (unit, (y0, x0)) in enumerate(zip(units, origins)):
+                    for key, tensor, path in (('sub', dev_img[y0:y0 + uh, x0:x0 + uw], unit + '.png'), ('mod', dev_img[y0:y0 + hh, x0:x0 + ww], unit + '.png'),
+                                              ('lr', lr_u8[k] if 'lr' in dirs else None, '%s_bicLRx%d.png' % (unit, s)),
+                                              ('bic', bic_u8[k] if 'bic' in dirs else None, '%s_bicx%d.png' % (unit, s))):
+                        if key in dirs:
+                            keys.append(key)
+                            tensors.append(tensor)
+                            paths.append(os.path.join(dirs[key], path))
+                jobs = list(zip(keys, png.write_batch(tensors, paths, enc)))
+                t0 = tick(t, 'device_png', t0)
+            else:
+                for k, (unit, (y0, x0)) in enumerate(zip(units, origins)):
+                    if 'sub' in dirs:
+                        jobs.append(('sub', enc.submit(_save_rgb, np.ascontiguousarray(img[y0:y0 + uh, x0:x0 + uw]), os.path.join(dirs['sub'], unit + '.png'))))
+                    if 'mod' in dirs:
+                        jobs.append(('mod', enc.submit(_save_rgb, np.ascontiguousarray(img[y0:y0 + hh, x0:x0 + ww]), os.path.join(dirs['mod'], unit + '.png'))))
+                    if 'lr' in dirs:
+                        jobs.append(('lr', enc.submit(_save_rgb, lr_host[k], os.path.join(dirs['lr'], '%s_bicLRx%d.png' % (unit, s)))))
+                    if 'bic' in dirs:
+                        jobs.append(('bic', enc.submit(_save_rgb, bic_host[k], os.path.join(dirs['bic'], '%s_bicx%d.png' % (unit, s)))))
             pending.append(jobs)
             t0 = tick(t, 'submit', t0)
             drain(2)

@@ -864,6 +864,65 @@ int dasr_jpeg_blocks(const uint8_t* src, int32_t N, int32_t H, int32_t W, int32_
 int dasr_jpeg_merge(const uint8_t* planes, int32_t N, int32_t H, int32_t W, uint8_t* dst, void* stream);
 int dasr_noise_u8(const uint8_t* src, uint8_t* dst, int32_t N, int64_t per, double std, int64_t seed, int64_t index0, void* stream);
 
+/* ---- PNG files from resident 8-bit images (csrc/png.hip) ----------------------------------------------------------------------------
+ * `python -m dasr_amd.prepare_data --device_png`, `add_corruptions --device_png` (dasr_amd/png.py states the stream in numpy and pure Python).  The deflate stream of an
+ * image is the concatenation of independently coded STRIPS of whole rows (at most 65 535 filtered bytes each), without LZ77: per strip one dynamic-Huffman block (BFINAL 0)
+ * followed by an empty stored block that byte-aligns it (zlib's Z_SYNC_FLUSH), or one stored block where that is smaller.  The host adds 78 01 in front, 03 00 (an empty
+ * final fixed-Huffman block) and the Adler-32 behind, and the PNG container.  A batch of images is one call per stage.  Asynchronous on `stream`, nothing is synchronised,
+ * plain loads and stores and LDS atomics only, same inputs give the same bits.
+ *
+ * Tables: images [n_images] and strips [n_strips] in device memory, and the same arrays in HOST memory (the staging buffer they were uploaded from), which is what every
+ * call validates before it launches.  An image is interleaved RGB bytes, `pitch` bytes from row to row (a window of a larger image: src points at its first pixel); its
+ * strips are strips[first_strip .. first_strip + n_strips).  Strip s covers rows [row0, row0 + rows) of image `image`; n = rows (1 + 3 W) is its count of filtered bytes;
+ * they stand at filt + filt_off (a multiple of 16; the strip owns n rounded up to 16 bytes there) and its coded bytes at slots + slot_off (a multiple of 4; the slot is
+ * DASR_PNG_SLOT_BYTES(n) = n + 16 rounded up to 4 bytes).
+ *
+ * dasr_png_filter: per row the five PNG filter types with bpp 3 (None, Sub, Up, Average with floor((left + up) / 2), Paeth with tie order a, b, c; the row above an
+ * image's first row is zeros, the row above a strip's first row is the row above it in the image); cost of a type = sum of min(b, 256 - b) over the row's 3 W filtered
+ * bytes, the smallest wins, ties to the lowest type; the row is written as type byte + filtered bytes.  hist [n_strips][257]: counts of the strip's byte values (type
+ * bytes included) and end-of-block = 1.  adler [n_strips][2]: s1 = sum b_i mod 65521, s2 = sum (n - i) b_i mod 65521 over the strip's bytes b_0 .. b_(n-1) (Adler-32
+ * run from s1 = s2 = 0; the stream's checksum follows from (1, 0) by s2 += n s1 + strip.s2, s1 += strip.s1).
+ *
+ * dasr_png_codes: hist [n][257] (sum below 2^32; below 2^28 for hdr[1]) -> lens [n][257] (<= 15; 0 for an unused symbol), codes [n][257] (canonical, RFC 1951
+ * 3.2.2, as numbers: deflate packs them starting from the most significant bit) and hdr [n][DASR_PNG_HDR_WORDS]: [0] bits of the block header, [1] bits of the coded
+ * symbols sum hist lens, [2] HLIT | HDIST << 8 | HCLEN << 16 (0, 1, number of code-length codes - 4), [3] 0, [4 ..] the header's bits, LSB first: BFINAL 0, BTYPE 10,
+ * HLIT, HDIST, HCLEN, the lengths (<= 7) of the code-length code in the order 16, 17, 18, 0, 8, ..., then the 257 lengths and the two distance lengths (1, 1: what zlib's
+ * Z_HUFFMAN_ONLY streams declare) one by one in that code (no run symbols 16 - 18).  The code is complete (Kraft sum 1).  It is a Huffman code (two-queue construction on
+ * the symbols sorted by (count, symbol)) where that tree is no deeper than 15; a deeper tree has its counts per length repaired (one code leaves length 15, one moves a
+ * level down, until the Kraft sum is 1) and the lengths handed out again by count.  Fewer than two used symbols: two codes of one bit.
+ *
+ * dasr_png_emit: one workgroup per strip writes its block into its slot and its size into sizes [n_strips]: the header, the codes bit-reversed and LSB first at the bit
+ * offsets an exclusive scan of the code lengths gives, end-of-block, three zero bits, padding to a byte, 00 00 FF FF; a strip that would take more than n + 5 bytes is
+ * 00, LEN, ~LEN and its n bytes.  Bits are put together in LDS and stored as whole words; a word outside the slot is not stored and sets bit 0 of *status (device
+ * memory, 8 bytes, zeroed by the caller; meta[0] of dasr_png_pack).  lens above 15 are read as 15.
+ *
+ * dasr_png_pack: an exclusive scan of the sizes (ws: n_strips x 8 bytes of scratch), the strips gathered in order into out (4-byte aligned, out_bytes: the sum of the
+ * slots always suffices), and meta [n_images + 3]: [0] status (bit 1: a size above its slot, bit 2: a strip beyond out_bytes; such strips are left out), [1] total
+ * bytes, [2 + i] offset of image i's first strip, [2 + n_images] the total again.  Two launches, no host loop.
+ *
+ * DASR_EINVAL, nothing launched: a null pointer, n_images or n_strips < 1, an image with H or W < 1, W > 21 844 (a row above 65 535 filtered bytes) or pitch < 3 W, a
+ * strip outside its image, with n != rows (1 + 3 W) or n > 65 535, with a misaligned offset or beyond filt_bytes / slots_bytes, a misaligned buffer. */
+#define DASR_PNG_HDR_WORDS 64
+#define DASR_PNG_SLOT_BYTES(n) (((n) + 16 + 3) / 4 * 4)
+typedef struct {
+    const uint8_t* src;
+    int64_t pitch;                   /* bytes from row to row */
+    int32_t H, W;
+    int32_t first_strip, n_strips;
+} dasr_png_image;
+typedef struct {
+    int32_t image, row0, rows, n;    /* n = rows (1 + 3 W) filtered bytes */
+    int64_t filt_off, slot_off;
+} dasr_png_strip;
+int dasr_png_filter(const dasr_png_image* images_dev, const dasr_png_image* images_host, int32_t n_images, const dasr_png_strip* strips_dev,
+                    const dasr_png_strip* strips_host, int32_t n_strips, uint8_t* filt, int64_t filt_bytes, uint32_t* hist, uint32_t* adler, void* stream);
+int dasr_png_codes(const uint32_t* hist, int32_t n, uint8_t* lens, uint16_t* codes, uint32_t* hdr, void* stream);
+int dasr_png_emit(const dasr_png_strip* strips_dev, const dasr_png_strip* strips_host, int32_t n_strips, const uint8_t* filt, int64_t filt_bytes, const uint8_t* lens,
+                  const uint16_t* codes, const uint32_t* hdr, uint8_t* slots, int64_t slots_bytes, uint32_t* sizes, uint64_t* status, void* stream);
+int dasr_png_pack(const dasr_png_image* images_dev, const dasr_png_image* images_host, int32_t n_images, const dasr_png_strip* strips_dev,
+                  const dasr_png_strip* strips_host, int32_t n_strips, const uint32_t* sizes, const uint8_t* slots, int64_t slots_bytes, uint64_t* ws, uint8_t* out,
+                  int64_t out_bytes, uint64_t* meta, void* stream);
+
 /* ---- profiling session (bench.py `roofline`) -----------------------------------------------------------
  * Between dasr_prof_begin and dasr_prof_end every kernel launch of the library (up to `capacity`) carries its own start/stop
  * events on its launch stream (hipExtLaunchKernel: the dispatch's begin/end timestamps, what rocprofv3 --kernel-trace prints).
