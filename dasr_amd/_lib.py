@@ -318,6 +318,8 @@ _SIGS = {
     'dasr_png_codes': [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp],
     'dasr_png_emit': [c_vp, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp],
     'dasr_png_pack': [c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp],
+    'dasr_png_filter_fmt': [c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_i32, c_vp],
+    'dasr_png_pack_fmt': [c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i32, c_vp],
     'dasr_prof_begin': [c_i32],
     'dasr_prof_end': [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp],
 }

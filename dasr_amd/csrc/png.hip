@@ -1,4 +1,5 @@
-// PNG encoding of 8-bit RGB images resident in device memory, without LZ77 (dasr_amd/png.py states the same stream in numpy and pure Python):
+// PNG encoding of 8-bit images resident in device memory (interleaved RGB, interleaved BGR written as RGB, or one grey channel), without LZ77 (dasr_amd/png.py states the
+// same stream in numpy and pure Python):
 //  * png_filter_kernel: per row the PNG filter type with the smallest sum of min(b, 256 - b), the filtered bytes, and per strip of rows the histogram and the Adler-32 partials.
 //  * png_codes_kernel: per strip a length-limited Huffman code for its 257 symbols, the canonical codes and the bits of the dynamic block's header.
 //  * png_emit_kernel: per strip the deflate block (or a stored block where that is smaller) and the empty stored block that byte-aligns it, into the strip's slot.
@@ -11,7 +12,7 @@ namespace {
 
 constexpr int SYMS = 257;             // byte values and end-of-block
 constexpr int MAX_STRIP = 65535;
-constexpr int MAX_W = 21844;
+constexpr int max_w(int bpp) { return (MAX_STRIP - 1) / bpp; }   // 1 + bpp W <= 65 535: 21 844 for three bytes per pixel, 65 534 for one
 constexpr int ADLER_MOD = 65521;
 constexpr int HDR_WORDS = DASR_PNG_HDR_WORDS;
 
@@ -29,6 +30,15 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
 // ---- 1. filter ------------------------------------------------------------------------------------------------------------------------
 // grid (n_strips), 256 threads: wave w takes rows w, w + 4, ... of the strip, one byte per lane and step.  First sweep: the five costs of the row; second sweep: the bytes of the
 // winning type, the histogram (one copy per wave in LDS) and the two Adler sums (64-bit per lane: (n - i) b < 2^24 per byte, < 2^40 per strip).
+// BPP: bytes per pixel of source and file (3: colour type 2, 1: colour type 0).  REV (BPP 3): the source is BGR, byte j of a PNG row is source byte 3 (j / 3) + 2 - j % 3; its
+// left neighbour is the same channel of the pixel to the left, BPP source bytes back, so the output is that of the channel-reversed image.
+template <int BPP, bool REV>
+__device__ __forceinline__ int src_index(int j) {
+    if constexpr (REV) return j + 2 - 2 * (j % 3);
+    else return j;
+}
+
+template <int BPP, bool REV>
 __global__ __launch_bounds__(256) void png_filter_kernel(const dasr_png_image* __restrict__ images, const dasr_png_strip* __restrict__ strips, uint8_t* __restrict__ filt,
                                                          uint32_t* __restrict__ hist, uint32_t* __restrict__ adler) {
     __shared__ uint32_t h[4][SYMS];
@@ -38,7 +48,7 @@ __global__ __launch_bounds__(256) void png_filter_kernel(const dasr_png_image* _
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     for (int i = tid; i < 4 * SYMS; i += 256) (&h[0][0])[i] = 0u;
     __syncthreads();
-    const int rb = 3 * I.W, stride = rb + 1, n = S.rows * stride;
+    const int rb = BPP * I.W, stride = rb + 1, n = S.rows * stride;
     uint8_t* out = filt + S.filt_off;
     unsigned long long s1 = 0, s2 = 0;
     for (int r = wave; r < S.rows; r += 4) {
@@ -48,7 +58,8 @@ __global__ __launch_bounds__(256) void png_filter_kernel(const dasr_png_image* _
         const bool has_up = y > 0;
         uint32_t cost[5] = {0u, 0u, 0u, 0u, 0u};
         for (int j = lane; j < rb; j += 64) {
-            const int x = cur[j], a = j >= 3 ? cur[j - 3] : 0, b = has_up ? up[j] : 0, c = (has_up && j >= 3) ? up[j - 3] : 0;
+            const int q = src_index<BPP, REV>(j);
+            const int x = cur[q], a = j >= BPP ? cur[q - BPP] : 0, b = has_up ? up[q] : 0, c = (has_up && j >= BPP) ? up[q - BPP] : 0;
             const int v[5] = {x, (x - a) & 255, (x - b) & 255, (x - ((a + b) >> 1)) & 255, (x - paeth(a, b, c)) & 255};
 #pragma unroll
             for (int t = 0; t < 5; ++t) cost[t] += (uint32_t)min(v[t], 256 - v[t]);
@@ -70,7 +81,8 @@ __global__ __launch_bounds__(256) void png_filter_kernel(const dasr_png_image* _
             s2 += (unsigned long long)(n - pos0) * (unsigned)best;
         }
         for (int j = lane; j < rb; j += 64) {
-            const int x = cur[j], a = j >= 3 ? cur[j - 3] : 0, b = has_up ? up[j] : 0, c = (has_up && j >= 3) ? up[j - 3] : 0;
+            const int q = src_index<BPP, REV>(j);
+            const int x = cur[q], a = j >= BPP ? cur[q - BPP] : 0, b = has_up ? up[q] : 0, c = (has_up && j >= BPP) ? up[q - BPP] : 0;
             const int pred = best == 0 ? 0 : best == 1 ? a : best == 2 ? b : best == 3 ? ((a + b) >> 1) : paeth(a, b, c);
             const int v = (x - pred) & 255, pos = pos0 + 1 + j;
             out[pos] = (uint8_t)v;
@@ -488,18 +500,18 @@ __global__ __launch_bounds__(256) void png_gather_kernel(const dasr_png_strip* _
 }
 
 // ---- validation of the host copies of the tables ---------------------------------------------------------------------------------------
-bool images_ok(const dasr_png_image* im, int n_images, int n_strips) {
+bool images_ok(const dasr_png_image* im, int n_images, int n_strips, int bpp = 3) {
     if (!im || n_images < 1) return false;
     for (int i = 0; i < n_images; ++i) {
         const dasr_png_image& I = im[i];
-        if (!I.src || I.H < 1 || I.W < 1 || I.W > MAX_W || (I.H > 1 && I.pitch < 3 * (int64_t)I.W)) return false;
+        if (!I.src || I.H < 1 || I.W < 1 || I.W > max_w(bpp) || (I.H > 1 && I.pitch < bpp * (int64_t)I.W)) return false;
         if (I.first_strip < 0 || I.n_strips < 1 || (int64_t)I.first_strip + I.n_strips > n_strips) return false;
     }
     return true;
 }
 
 // filt_bytes / slots_bytes < 0: that buffer is not used by the call
-bool strips_ok(const dasr_png_strip* st, int n_strips, const dasr_png_image* im, int n_images, int64_t filt_bytes, int64_t slots_bytes) {
+bool strips_ok(const dasr_png_strip* st, int n_strips, const dasr_png_image* im, int n_images, int64_t filt_bytes, int64_t slots_bytes, int bpp = 3) {
     if (!st || n_strips < 1) return false;
     for (int s = 0; s < n_strips; ++s) {
         const dasr_png_strip& S = st[s];
@@ -507,7 +519,7 @@ bool strips_ok(const dasr_png_strip* st, int n_strips, const dasr_png_image* im,
         if (im) {
             if (S.image < 0 || S.image >= n_images) return false;
             const dasr_png_image& I = im[S.image];
-            if ((int64_t)S.row0 + S.rows > I.H || (int64_t)S.rows * (1 + 3 * (int64_t)I.W) != S.n) return false;
+            if ((int64_t)S.row0 + S.rows > I.H || (int64_t)S.rows * (1 + bpp * (int64_t)I.W) != S.n) return false;
         }
         if (filt_bytes >= 0 && (S.filt_off < 0 || (S.filt_off & 15) || S.filt_off + ((S.n + 15) & ~15) > filt_bytes)) return false;
         if (slots_bytes >= 0 && (S.slot_off < 0 || (S.slot_off & 3) || S.slot_off + ((S.n + 16 + 3) & ~3) > slots_bytes)) return false;
@@ -515,14 +527,27 @@ bool strips_ok(const dasr_png_strip* st, int n_strips, const dasr_png_image* im,
     return true;
 }
 
+// fmt of the _fmt entry points: 0 interleaved RGB, 1 interleaved BGR, 2 one channel; bytes per pixel, 0 for any other value
+int fmt_bpp(int32_t fmt) { return fmt == 0 || fmt == 1 ? 3 : fmt == 2 ? 1 : 0; }
+
 }  // namespace
+
+extern "C" int dasr_png_filter_fmt(const dasr_png_image* images_dev, const dasr_png_image* images_host, int32_t n_images, const dasr_png_strip* strips_dev,
+                                   const dasr_png_strip* strips_host, int32_t n_strips, uint8_t* filt, int64_t filt_bytes, uint32_t* hist, uint32_t* adler, int32_t fmt,
+                                   void* stream) {
+    const int bpp = fmt_bpp(fmt);
+    if (!bpp || !images_dev || !strips_dev || !filt || !hist || !adler || filt_bytes < 0 || ((uintptr_t)filt & 15)) return DASR_EINVAL;
+    if (!images_ok(images_host, n_images, n_strips, bpp) || !strips_ok(strips_host, n_strips, images_host, n_images, filt_bytes, -1, bpp)) return DASR_EINVAL;
+    const dim3 grid((unsigned)n_strips), block(256);
+    if (fmt == 0) { DASR_LAUNCH_TAG("png_filter_kernel", (png_filter_kernel<3, false>), grid, block, 0, as_stream(stream), images_dev, strips_dev, filt, hist, adler); }
+    else if (fmt == 1) { DASR_LAUNCH_TAG("png_filter_kernel<bgr>", (png_filter_kernel<3, true>), grid, block, 0, as_stream(stream), images_dev, strips_dev, filt, hist, adler); }
+    else { DASR_LAUNCH_TAG("png_filter_kernel<grey>", (png_filter_kernel<1, false>), grid, block, 0, as_stream(stream), images_dev, strips_dev, filt, hist, adler); }
+    return (int)hipGetLastError();
+}
 
 extern "C" int dasr_png_filter(const dasr_png_image* images_dev, const dasr_png_image* images_host, int32_t n_images, const dasr_png_strip* strips_dev,
                                const dasr_png_strip* strips_host, int32_t n_strips, uint8_t* filt, int64_t filt_bytes, uint32_t* hist, uint32_t* adler, void* stream) {
-    if (!images_dev || !strips_dev || !filt || !hist || !adler || filt_bytes < 0 || ((uintptr_t)filt & 15)) return DASR_EINVAL;
-    if (!images_ok(images_host, n_images, n_strips) || !strips_ok(strips_host, n_strips, images_host, n_images, filt_bytes, -1)) return DASR_EINVAL;
-    DASR_LAUNCH(png_filter_kernel, dim3((unsigned)n_strips), dim3(256), 0, as_stream(stream), images_dev, strips_dev, filt, hist, adler);
-    return (int)hipGetLastError();
+    return dasr_png_filter_fmt(images_dev, images_host, n_images, strips_dev, strips_host, n_strips, filt, filt_bytes, hist, adler, 0, stream);
 }
 
 extern "C" int dasr_png_codes(const uint32_t* hist, int32_t n, uint8_t* lens, uint16_t* codes, uint32_t* hdr, void* stream) {
@@ -541,15 +566,23 @@ extern "C" int dasr_png_emit(const dasr_png_strip* strips_dev, const dasr_png_st
     return (int)hipGetLastError();
 }
 
-extern "C" int dasr_png_pack(const dasr_png_image* images_dev, const dasr_png_image* images_host, int32_t n_images, const dasr_png_strip* strips_dev,
-                             const dasr_png_strip* strips_host, int32_t n_strips, const uint32_t* sizes, const uint8_t* slots, int64_t slots_bytes, uint64_t* ws, uint8_t* out,
-                             int64_t out_bytes, uint64_t* meta, void* stream) {
+extern "C" int dasr_png_pack_fmt(const dasr_png_image* images_dev, const dasr_png_image* images_host, int32_t n_images, const dasr_png_strip* strips_dev,
+                                 const dasr_png_strip* strips_host, int32_t n_strips, const uint32_t* sizes, const uint8_t* slots, int64_t slots_bytes, uint64_t* ws,
+                                 uint8_t* out, int64_t out_bytes, uint64_t* meta, int32_t fmt, void* stream) {
+    const int bpp = fmt_bpp(fmt);
+    if (!bpp) return DASR_EINVAL;
     if (!images_dev || !strips_dev || !sizes || !slots || !ws || !out || !meta || slots_bytes < 0 || out_bytes < 0) return DASR_EINVAL;
     if (((uintptr_t)slots & 3) || ((uintptr_t)out & 3) || ((uintptr_t)ws & 7) || ((uintptr_t)meta & 7)) return DASR_EINVAL;
-    if (!images_ok(images_host, n_images, n_strips) || !strips_ok(strips_host, n_strips, images_host, n_images, -1, slots_bytes)) return DASR_EINVAL;
+    if (!images_ok(images_host, n_images, n_strips, bpp) || !strips_ok(strips_host, n_strips, images_host, n_images, -1, slots_bytes, bpp)) return DASR_EINVAL;
     DASR_LAUNCH(png_scan_kernel, dim3(1), dim3(1024), 0, as_stream(stream), images_dev, n_images, strips_dev, n_strips, sizes, reinterpret_cast<unsigned long long*>(ws),
                 reinterpret_cast<unsigned long long*>(meta));
     DASR_LAUNCH(png_gather_kernel, dim3((unsigned)n_strips), dim3(256), 0, as_stream(stream), strips_dev, sizes, slots, reinterpret_cast<const unsigned long long*>(ws), out,
                 (unsigned long long)out_bytes, reinterpret_cast<unsigned long long*>(meta));
     return (int)hipGetLastError();
+}
+
+extern "C" int dasr_png_pack(const dasr_png_image* images_dev, const dasr_png_image* images_host, int32_t n_images, const dasr_png_strip* strips_dev,
+                             const dasr_png_strip* strips_host, int32_t n_strips, const uint32_t* sizes, const uint8_t* slots, int64_t slots_bytes, uint64_t* ws, uint8_t* out,
+                             int64_t out_bytes, uint64_t* meta, void* stream) {
+    return dasr_png_pack_fmt(images_dev, images_host, n_images, strips_dev, strips_host, n_strips, sizes, slots, slots_bytes, ws, out, out_bytes, meta, 0, stream);
 }

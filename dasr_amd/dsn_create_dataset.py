@@ -5,9 +5,11 @@ For every target-domain HR image: fake LR = G(img) saved as PNG under <out>/imgs
 (float64 .npy, shape [1,1,h,w]; h/2 x w/2 for the wavelet filter) under <out>/ddm_target; with --including_source_ddm the map of
 every source-domain LR image under <out>/ddm_source.  Same flags as the reference; its `../paths.yml` lookup is replaced by
 --target_dir / --source_dir (or --dataset synthetic for seeded random images).  Generator / discriminator run on the HIP kernels
-(dasr_amd.dsn_model.DSNModel.translate / .ddm_of); image IO is PIL on the host.
+(dasr_amd.dsn_model.DSNModel.translate / .ddm_of); image IO is PIL on the host.  With --device_png the fake LR images are quantised (metrics.tensor2img_device: the
+rounding of _save_png) and encoded on the device (png.DeviceWriter); the pixels of the files and the .npy maps are those of the default path.
 """
 import argparse
+import contextlib
 import os
 import shutil
 
@@ -43,6 +45,8 @@ def build_parser():
     p.add_argument('--paths', default='../paths.yml', type=str, help="yaml file with the dataset folders (the reference reads '../paths.yml', create_dataset_modified.py:49-50)")
     p.add_argument('--out_root', default='DSN_results', type=str)
     p.add_argument('--n_synthetic', default=4, type=int)
+    p.add_argument('--device_png', action='store_true', help='encode the fake LR images on the device (png.DeviceWriter) instead of with PIL on the main thread')
+    p.add_argument('--num_workers', default=4, type=int, help='host threads of --device_png: the container, the checksums and the file write (at most 16)')
     return p
 
 
@@ -110,12 +114,24 @@ def main(argv=None):
     shutil.copyfile(o.checkpoint, os.path.join(out, o.name + '.tar'))
     dev = m.device
     n = 0
-    for name, img in _images(o, 'target'):
-        H, W = img.shape[-2] // 4 * 4, img.shape[-1] // 4 * 4
-        fake, _, ddm = m.translate(img[..., :H, :W].to(dev))
-        _save_png(fake[0], os.path.join(dirs['imgs_from_target'], name.rsplit('.', 1)[0] + '.png'))
-        np.save(os.path.join(dirs['ddm_target'], name.split('.')[0]), ddm.double().cpu().numpy())
-        n += 1
+    if o.device_png:
+        from .metrics import tensor2img_device
+        from .png import DeviceWriter
+        print('--device_png: the PNG files are encoded on the device (filter, Huffman-only deflate), the host adds the container and the checksums')
+        sink = DeviceWriter(o.num_workers)
+    else:
+        sink = contextlib.nullcontext()
+    with sink as writer:   # (leaving the block waits for every file of the writer)
+        for name, img in _images(o, 'target'):
+            H, W = img.shape[-2] // 4 * 4, img.shape[-1] // 4 * 4
+            fake, _, ddm = m.translate(img[..., :H, :W].to(dev))
+            path = os.path.join(dirs['imgs_from_target'], name.rsplit('.', 1)[0] + '.png')
+            if writer is None:
+                _save_png(fake[0], path)
+            else:
+                writer.write(tensor2img_device(fake[0]), path, 'bgr')   # HWC BGR bytes of rint(clamp(x, 0, 1) 255): the file is their RGB image
+            np.save(os.path.join(dirs['ddm_target'], name.split('.')[0]), ddm.double().cpu().numpy())
+            n += 1
     if o.including_source_ddm:
         for name, img in _images(o, 'source'):
             _, ddm = m.ddm_of(img.to(dev))

@@ -54,6 +54,7 @@ def parse(opt_path, is_train=True):
         opt['path']['log'] = root
     opt['network_G']['scale'] = scale
     back_projection_iters(opt.get('back_projection'))   # (checked here, read by the models: a bad value stops the run before a network is built)
+    device_png_flag(opt.get('device_png'))
     # codes/SRN/options/options.py:68-71 exports CUDA_VISIBLE_DEVICES = gpu_ids for its single-process nn.DataParallel.  HIP honours
     # that variable too, so under one-process-per-GPU launch (torch.distributed.run sets WORLD_SIZE / LOCAL_RANK) it would hide every
     # device but the listed ones from EVERY rank (the shipped JSONs say gpu_ids [0]: rank 1's set_device(1) would fail).  Rule:
@@ -81,6 +82,15 @@ def back_projection_iters(value):
     if isinstance(value, int) and value >= 0:
         return value
     raise ValueError('back_projection: expected true, false or a number of iterations >= 0, got %r' % (value,))
+
+
+def device_png_flag(value):
+    """the top-level key `"device_png"`: true -> the drivers encode SR images on the device (dasr_amd/png.py), absent / false -> PIL on the host; anything else is a ValueError"""
+    if value is None or value is False:
+        return False
+    if value is True:
+        return True
+    raise ValueError('device_png: expected true or false, got %r' % (value,))
 
 
 class NoneDict(dict):

@@ -1,4 +1,4 @@
-"""PNG files from 8-bit RGB images that are resident on the device, without LZ77: the per-row filter, a dynamic-Huffman deflate block per strip of rows and the packing
+"""PNG files from 8-bit images that are resident on the device, without LZ77: the per-row filter, a dynamic-Huffman deflate block per strip of rows and the packing
 of the strips into one buffer run on the MI355X (csrc/png.hip); the host adds the container (signature, IHDR, IDAT, IEND), the combined Adler-32 and the chunk CRCs.
 
 The stream of one image (what every inflater reads, PIL bit for bit):
@@ -13,7 +13,13 @@ no strip is special.
 
 filter_ref / strip_stats_ref / encode_ref state all of this in numpy and pure Python and need no device (the tests pin the kernels to them: the filtered bytes,
 histograms and Adler partials bit for bit; the files by what they inflate and decode to, since two Huffman constructions may break ties differently).
-encode_batch / write_batch run it on uint8 device tensors: one descriptor upload, five launches, two read-backs per batch."""
+encode_batch / write_batch run it on uint8 device tensors: one descriptor upload, five launches, two read-backs per batch.
+
+`fmt` names what a batch holds: 'rgb' (the default) interleaved RGB [H, W, 3]; 'bgr' interleaved BGR [H, W, 3] as util.tensor2img / metrics.tensor2img_device return it, written as
+the RGB file of the channel-reversed image (the filter kernel reads the bytes in file order, nothing is permuted in memory); 'grey' one channel [H, W], colour type 0, one
+byte per pixel (rows of 1 + W filtered bytes, W <= 65 534).  DeviceWriter is the sink the drivers hand single images to: the device stages per image on the current stream,
+the container, the CRCs and the file write on its thread pool, a bounded number of files outstanding."""
+import collections
 import heapq
 import struct
 import zlib
@@ -30,11 +36,24 @@ HDR_WORDS = 64              # DASR_PNG_HDR_WORDS
 CL_ORDER = (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15)
 SIGNATURE = b'\x89PNG\r\n\x1a\n'
 HOST_PATH = "PIL's Image.save"
+FORMATS = {'rgb': (0, 3), 'bgr': (1, 3), 'grey': (2, 1)}   # fmt -> (DASR_PNG_RGB / _BGR / _GREY, bytes per pixel)
+MAX_WRITER_THREADS = 16
 
 
-def strip_rows(W):
+def _format(fmt):
+    if fmt not in FORMATS:
+        raise ValueError("fmt: expected 'rgb', 'bgr' or 'grey', got %r" % (fmt,))
+    return FORMATS[fmt]
+
+
+def max_width(fmt='rgb'):
+    """the widest image of a format: a row of 1 + bpp W filtered bytes fits one strip"""
+    return (MAX_STRIP_BYTES - 1) // _format(fmt)[1]
+
+
+def strip_rows(W, fmt='rgb'):
     """rows of a strip of an image W pixels wide"""
-    return max(1, STRIP_TARGET // (1 + 3 * int(W)))
+    return max(1, STRIP_TARGET // (1 + _format(fmt)[1] * int(W)))
 
 
 def photo(h, w, seed):
@@ -51,40 +70,45 @@ def photo(h, w, seed):
 
 
 # ---- the filter ----------------------------------------------------------------------------------------------------------------------
-def _check_image(img):
+def _check_image(img, fmt='rgb'):
     img = np.asarray(img)
-    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3 or img.shape[0] < 1 or img.shape[1] < 1:
-        raise ValueError('the image must be uint8 [H, W, 3], got %s %s' % (img.dtype, img.shape))
-    if img.shape[1] > MAX_WIDTH:
-        raise ValueError('an image %d pixels wide has rows above %d filtered bytes (W > %d): encode it on the host (%s)' % (img.shape[1], MAX_STRIP_BYTES, MAX_WIDTH, HOST_PATH))
+    bpp = _format(fmt)[1]
+    if img.dtype != np.uint8 or img.ndim != (3 if bpp == 3 else 2) or (bpp == 3 and img.shape[2] != 3) or img.shape[0] < 1 or img.shape[1] < 1:
+        raise ValueError('the image must be uint8 %s, got %s %s' % ('[H, W, 3]' if bpp == 3 else '[H, W]', img.dtype, img.shape))
+    if img.shape[1] > max_width(fmt):
+        raise ValueError('an image %d pixels wide has rows above %d filtered bytes (W > %d): encode it on the host (%s)' % (img.shape[1], MAX_STRIP_BYTES, max_width(fmt), HOST_PATH))
     return img
 
 
-def filter_ref(img):
-    """uint8 [H, W, 3] -> uint8 [H, 1 + 3 W]: the filter type of every row and its filtered bytes (its bytes in C order are the stream that is deflated)"""
-    img = _check_image(img)
+def filter_ref(img, fmt='rgb'):
+    """uint8 [H, W, 3] ('grey': [H, W]) -> uint8 [H, 1 + bpp W]: the filter type of every row and its filtered bytes (its bytes in C order are the stream that is deflated).
+    'bgr': the rows of the channel-reversed image"""
+    img = _check_image(img, fmt)
+    if fmt == 'bgr':
+        img = img[:, :, ::-1]
     H, W = img.shape[:2]
-    x = img.reshape(H, 3 * W).astype(np.int32)
-    a = np.concatenate([np.zeros((H, 3), np.int32), x[:, :-3]], axis=1)          # left
-    b = np.concatenate([np.zeros((1, 3 * W), np.int32), x[:-1]], axis=0)         # up: zeros above the first row
-    c = np.concatenate([np.zeros((H, 3), np.int32), b[:, :-3]], axis=1)          # up-left
+    bpp = _format(fmt)[1]
+    x = img.reshape(H, bpp * W).astype(np.int32)
+    a = np.concatenate([np.zeros((H, bpp), np.int32), x[:, :-bpp]], axis=1)      # left
+    b = np.concatenate([np.zeros((1, bpp * W), np.int32), x[:-1]], axis=0)       # up: zeros above the first row
+    c = np.concatenate([np.zeros((H, bpp), np.int32), b[:, :-bpp]], axis=1)      # up-left
     p = a + b - c
     pa, pb, pc = np.abs(p - a), np.abs(p - b), np.abs(p - c)
     paeth = np.where((pa <= pb) & (pa <= pc), a, np.where(pb <= pc, b, c))
-    cand = np.stack([x, x - a, x - b, x - ((a + b) >> 1), x - paeth]) & 255      # [5, H, 3 W]
+    cand = np.stack([x, x - a, x - b, x - ((a + b) >> 1), x - paeth]) & 255      # [5, H, bpp W]
     cost = np.minimum(cand, 256 - cand).sum(axis=2)                              # [5, H]
     types = np.argmin(cost, axis=0)                                              # (the first minimum: the lowest type)
-    out = np.empty((H, 1 + 3 * W), np.uint8)
+    out = np.empty((H, 1 + bpp * W), np.uint8)
     out[:, 0] = types
     out[:, 1:] = cand[types, np.arange(H)]
     return out
 
 
-def strip_stats_ref(filtered):
-    """filtered uint8 [H, 1 + 3 W] -> (histograms uint32 [n_strips, 257] with end-of-block = 1, Adler partials uint32 [n_strips, 2]): per strip of n bytes b_0 .. b_(n-1),
+def strip_stats_ref(filtered, fmt='rgb'):
+    """filtered uint8 [H, 1 + bpp W] -> (histograms uint32 [n_strips, 257] with end-of-block = 1, Adler partials uint32 [n_strips, 2]): per strip of n bytes b_0 .. b_(n-1),
     s1 = sum b_i mod 65521 and s2 = sum (n - i) b_i mod 65521 (Adler-32 run from s1 = s2 = 0)"""
     H, stride = filtered.shape
-    rows = strip_rows((stride - 1) // 3)
+    rows = strip_rows((stride - 1) // _format(fmt)[1], fmt)
     hist, adler = [], []
     for r0 in range(0, H, rows):
         b = filtered[r0:r0 + rows].reshape(-1).astype(np.int64)
@@ -231,20 +255,20 @@ def _chunk_parts(kind, parts):
     return [struct.pack('>I', sum(len(p) for p in parts)), kind] + list(parts) + [struct.pack('>I', crc)]
 
 
-def file_parts(H, W, strips, adler):
-    """the pieces of the PNG file of an H x W image whose packed strips are `strips` (bytes-like) and whose combined Adler-32 is `adler`"""
-    ihdr = struct.pack('>IIBBBBB', W, H, 8, 2, 0, 0, 0)
+def file_parts(H, W, strips, adler, fmt='rgb'):
+    """the pieces of the PNG file of an H x W image whose packed strips are `strips` (bytes-like) and whose combined Adler-32 is `adler`: colour type 2 (RGB), for 'grey' 0"""
+    ihdr = struct.pack('>IIBBBBB', W, H, 8, 2 if _format(fmt)[1] == 3 else 0, 0, 0, 0)
     return [SIGNATURE] + _chunk_parts(b'IHDR', [ihdr]) + _chunk_parts(b'IDAT', [b'\x78\x01', strips, b'\x03\x00', struct.pack('>I', adler)]) + _chunk_parts(b'IEND', [])
 
 
-def encode_ref(img):
-    """uint8 [H, W, 3] -> the bytes of its PNG file, on the host"""
-    f = filter_ref(img)
-    H, W = f.shape[0], (f.shape[1] - 1) // 3
-    rows = strip_rows(W)
+def encode_ref(img, fmt='rgb'):
+    """uint8 [H, W, 3] ('grey': [H, W]) -> the bytes of its PNG file, on the host"""
+    f = filter_ref(img, fmt)
+    H, W = f.shape[0], (f.shape[1] - 1) // _format(fmt)[1]
+    rows = strip_rows(W, fmt)
     strips = [f[r0:r0 + rows].reshape(-1) for r0 in range(0, H, rows)]
-    _, adler = strip_stats_ref(f)
-    return b''.join(file_parts(H, W, b''.join(deflate_strip_ref(s) for s in strips), adler_combine(adler, [s.size for s in strips])))
+    _, adler = strip_stats_ref(f, fmt)
+    return b''.join(file_parts(H, W, b''.join(deflate_strip_ref(s) for s in strips), adler_combine(adler, [s.size for s in strips]), fmt))
 
 
 # ---- the device path (csrc/png.hip) ------------------------------------------------------------------------------------------------------
@@ -252,16 +276,33 @@ IMAGE_DESC = np.dtype([('src', '<u8'), ('pitch', '<i8'), ('H', '<i4'), ('W', '<i
 STRIP_DESC = np.dtype([('image', '<i4'), ('row0', '<i4'), ('rows', '<i4'), ('n', '<i4'), ('filt_off', '<i8'), ('slot_off', '<i8')])  # dasr_png_strip
 
 
-def _check_tensor(k, t):
+def _check_grey_tensor(k, t):
     import torch
     what = 'images[%d]' % k
     if not torch.is_tensor(t):
+        raise ValueError('%s: expected a uint8 device tensor [H, W], got %s' % (what, type(t).__name__))
+    if t.device.type != 'cuda' or t.dtype != torch.uint8 or t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError('%s: expected a uint8 device tensor [H, W] (8-bit grey), got %s %s on %s' % (what, t.dtype, tuple(t.shape), t.device))
+    H, W = int(t.shape[0]), int(t.shape[1])
+    if (W > 1 and t.stride(1) != 1) or (H > 1 and t.stride(0) < W):   # (the stride of a dimension of size 1 says nothing)
+        raise ValueError('%s: pixels must be consecutive bytes (stride(1) == 1, rows that do not overlap), got strides %s' % (what, tuple(t.stride())))
+    if W > max_width('grey'):
+        raise ValueError('%s: %d pixels wide, rows above %d filtered bytes (W > %d): encode it on the host (%s)' % (what, W, MAX_STRIP_BYTES, max_width('grey'), HOST_PATH))
+    return H, W
+
+
+def _check_tensor(k, t, fmt='rgb'):
+    import torch
+    if _format(fmt)[1] == 1:
+        return _check_grey_tensor(k, t)
+    what, order = 'images[%d]' % k, fmt.upper()
+    if not torch.is_tensor(t):
         raise ValueError('%s: expected a uint8 device tensor [H, W, 3], got %s' % (what, type(t).__name__))
     if t.device.type != 'cuda' or t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
-        raise ValueError('%s: expected a uint8 device tensor [H, W, 3] (8-bit RGB), got %s %s on %s' % (what, t.dtype, tuple(t.shape), t.device))
+        raise ValueError('%s: expected a uint8 device tensor [H, W, 3] (8-bit %s), got %s %s on %s' % (what, order, t.dtype, tuple(t.shape), t.device))
     H, W = int(t.shape[0]), int(t.shape[1])
     if t.stride(2) != 1 or t.stride(1) != 3 or (H > 1 and t.stride(0) < 3 * W):
-        raise ValueError('%s: pixels must be interleaved RGB bytes (stride(1) == 3, stride(2) == 1, rows that do not overlap), got strides %s' % (what, tuple(t.stride())))
+        raise ValueError('%s: pixels must be interleaved %s bytes (stride(1) == 3, stride(2) == 1, rows that do not overlap), got strides %s' % (what, order, tuple(t.stride())))
     if W > MAX_WIDTH:
         raise ValueError('%s: %d pixels wide, rows above %d filtered bytes (W > %d): encode it on the host (%s)' % (what, W, MAX_STRIP_BYTES, MAX_WIDTH, HOST_PATH))
     return H, W
@@ -270,9 +311,11 @@ def _check_tensor(k, t):
 class Plan:
     """the descriptors of one batch: host arrays, their one upload, and the sizes of the work buffers"""
 
-    def __init__(self, images):
+    def __init__(self, images, fmt='rgb'):
         import torch
-        sizes = [_check_tensor(k, t) for k, t in enumerate(images)]
+        self.fmt = fmt
+        self.fmt_code, bpp = _format(fmt)
+        sizes = [_check_tensor(k, t, fmt) for k, t in enumerate(images)]
         if any(t.device != images[0].device for t in images):
             raise ValueError('images: all tensors of a batch must be on one device')
         self.device = images[0].device
@@ -280,14 +323,14 @@ class Plan:
         strips, self.images = [], np.zeros(len(images), IMAGE_DESC)
         filt_off = slot_off = 0
         for k, (t, (H, W)) in enumerate(zip(images, sizes)):
-            rows, stride = strip_rows(W), 1 + 3 * W
+            rows, stride = strip_rows(W, fmt), 1 + bpp * W
             first = len(strips)
             for r0 in range(0, H, rows):
                 r = min(rows, H - r0)
                 strips.append((k, r0, r, r * stride, filt_off, slot_off))
                 filt_off += -(-r * stride // 16) * 16
                 slot_off += -(-(r * stride + 16) // 4) * 4
-            self.images[k] = (t.data_ptr(), t.stride(0) if H > 1 else 3 * W, H, W, first, len(strips) - first)
+            self.images[k] = (t.data_ptr(), t.stride(0) if H > 1 else bpp * W, H, W, first, len(strips) - first)
         self.strips = np.array(strips, dtype=STRIP_DESC)
         self.filt_bytes, self.slot_bytes = filt_off, slot_off
         blob = np.concatenate([self.images.view(np.uint8), self.strips.view(np.uint8)])
@@ -299,20 +342,20 @@ class Plan:
         return self.images.ctypes.data, self.strips.ctypes.data
 
 
-def filter_batch(images, plan=None):
-    """stage 1 (dasr_png_filter) on the current stream -> (plan, filtered bytes uint8 [plan.filt_bytes]: strip s at plan.strips['filt_off'][s], histograms uint32
+def filter_batch(images, plan=None, fmt='rgb'):
+    """stage 1 (dasr_png_filter_fmt; `fmt` of a given plan is the plan's) on the current stream -> (plan, filtered bytes uint8 [plan.filt_bytes]: strip s at plan.strips['filt_off'][s], histograms uint32
     [n_strips, 257], meta).  meta is the int64 buffer of the batch's first read-back: status, total bytes, n_images + 1 offsets, then the Adler partials as uint32 pairs."""
     import torch
     from . import _lib
     from .engine import _stream
-    plan = plan or Plan(images)
+    plan = plan or Plan(images, fmt)
     dev = plan.device
     filt = torch.empty(plan.filt_bytes, dtype=torch.uint8, device=dev)
     hist = torch.empty((plan.n_strips, N_SYMS), dtype=torch.int32, device=dev)
     meta = torch.zeros(plan.n_images + 3 + plan.n_strips, dtype=torch.int64, device=dev)
     ih, sh = plan.host()
-    _lib.check(_lib.lib().dasr_png_filter(plan.images_dev, ih, plan.n_images, plan.strips_dev, sh, plan.n_strips, filt.data_ptr(), plan.filt_bytes, hist.data_ptr(),
-                                          meta.data_ptr() + 8 * (plan.n_images + 3), _stream()), 'dasr_png_filter')
+    _lib.check(_lib.lib().dasr_png_filter_fmt(plan.images_dev, ih, plan.n_images, plan.strips_dev, sh, plan.n_strips, filt.data_ptr(), plan.filt_bytes, hist.data_ptr(),
+                                              meta.data_ptr() + 8 * (plan.n_images + 3), plan.fmt_code, _stream()), 'dasr_png_filter_fmt')
     return plan, filt, hist, meta
 
 
@@ -332,7 +375,7 @@ def codes_batch(hist):
     return lens, codes, hdr
 
 
-def _encode_device(images, times=None):
+def _encode_device(images, times=None, fmt='rgb'):
     """stages 1-4 and the two read-backs -> (plan, meta int64 host array, packed bytes uint8 host array).  `times`: a dict that receives the seconds of 'plan' (the tables
     and their upload), 'kernels', 'readback_meta' and 'readback_bytes'; the stream is then synchronised in between, which an ordinary call does not do."""
     import time
@@ -347,7 +390,7 @@ def _encode_device(images, times=None):
             times[key] = times.get(key, 0.0) + time.perf_counter() - t0
         return time.perf_counter()
     t0 = time.perf_counter()
-    plan = Plan(images)
+    plan = Plan(images, fmt)
     t0 = tick('plan', t0)
     plan, filt, hist, meta = filter_batch(images, plan)
     lens, codes, hdr = codes_batch(hist)
@@ -359,8 +402,8 @@ def _encode_device(images, times=None):
     ih, sh = plan.host()
     _lib.check(L.dasr_png_emit(plan.strips_dev, sh, plan.n_strips, filt.data_ptr(), plan.filt_bytes, lens.data_ptr(), codes.data_ptr(), hdr.data_ptr(), slots.data_ptr(),
                                plan.slot_bytes, sizes.data_ptr(), meta.data_ptr(), _stream()), 'dasr_png_emit')
-    _lib.check(L.dasr_png_pack(plan.images_dev, ih, plan.n_images, plan.strips_dev, sh, plan.n_strips, sizes.data_ptr(), slots.data_ptr(), plan.slot_bytes, ws.data_ptr(),
-                               out.data_ptr(), plan.slot_bytes, meta.data_ptr(), _stream()), 'dasr_png_pack')
+    _lib.check(L.dasr_png_pack_fmt(plan.images_dev, ih, plan.n_images, plan.strips_dev, sh, plan.n_strips, sizes.data_ptr(), slots.data_ptr(), plan.slot_bytes, ws.data_ptr(),
+                                   out.data_ptr(), plan.slot_bytes, meta.data_ptr(), plan.fmt_code, _stream()), 'dasr_png_pack_fmt')
     t0 = tick('kernels', t0)
     m = meta.cpu().numpy()                                                       # read-back 1: status, sizes and offsets, Adler partials
     if m[0] != 0:
@@ -376,16 +419,16 @@ def _assemble(plan, m, packed, k):
     H, W = plan.sizes[k]
     first, cnt = int(plan.images['first_strip'][k]), int(plan.images['n_strips'][k])
     adler = m[plan.n_images + 3:].view(np.uint32).reshape(-1, 2)[first:first + cnt]
-    return file_parts(H, W, memoryview(packed[int(m[2 + k]):int(m[3 + k])]), adler_combine(adler, plan.strips['n'][first:first + cnt]))
+    return file_parts(H, W, memoryview(packed[int(m[2 + k]):int(m[3 + k])]), adler_combine(adler, plan.strips['n'][first:first + cnt]), plan.fmt)
 
 
-def encode_batch(images, times=None):
-    """uint8 device tensors [H, W, 3] (views with any row stride; stride(1) == 3 and stride(2) == 1) -> the bytes of their PNG files.  Stages 1-4 run on the current
+def encode_batch(images, times=None, fmt='rgb'):
+    """uint8 device tensors [H, W, 3] (views with any row stride; stride(1) == 3 and stride(2) == 1; 'grey': [H, W], stride(1) == 1) -> the bytes of their PNG files.  Stages 1-4 run on the current
     stream for the whole batch; the container, the Adler-32 and the chunk CRCs are made on the host.  `times`: see _encode_device."""
     images = list(images)
     if not images:
         return []
-    plan, m, packed = _encode_device(images, times)
+    plan, m, packed = _encode_device(images, times, fmt)
     return [b''.join(_assemble(plan, m, packed, k)) for k in range(len(images))]
 
 
@@ -395,7 +438,7 @@ def _write(plan, m, packed, k, path):
     return path
 
 
-def write_batch(images, paths, pool, times=None):
+def write_batch(images, paths, pool, times=None, fmt='rgb'):
     """encode_batch straight into files: returns one future per image (its result is the path); the container, the CRCs (zlib.crc32 releases the GIL) and the write of
     every file run on `pool`"""
     images, paths = list(images), list(paths)
@@ -403,5 +446,57 @@ def write_batch(images, paths, pool, times=None):
         raise ValueError('paths: %d paths for %d images' % (len(paths), len(images)))
     if not images:
         return []
-    plan, m, packed = _encode_device(images, times)
+    plan, m, packed = _encode_device(images, times, fmt)
     return [pool.submit(_write, plan, m, packed, k, p) for k, p in enumerate(paths)]
+
+
+class DeviceWriter:
+    """the sink of the drivers that write one image at a time: `with DeviceWriter(threads) as w: w.write(u8_device_tensor, path, fmt)`.  write() runs write_batch for that
+    image on the current stream and returns once its two read-backs are done (until then the call holds the tensor; afterwards the caller may reuse it); the container, the
+    CRCs and the file write run on the writer's own pool of at most 16 threads.  At most 2 x threads files are outstanding: beyond that write() waits for the oldest.  close()
+    (or leaving the block) waits for all of them and raises the first failure, so a driver cannot return before its files are complete."""
+
+    def __init__(self, threads=4):
+        from concurrent.futures import ThreadPoolExecutor
+        self.threads = max(1, min(int(threads), MAX_WRITER_THREADS))
+        self.max_pending = 2 * self.threads
+        self._pool = ThreadPoolExecutor(max_workers=self.threads)
+        self._pending = collections.deque()
+        self._error = None
+
+    def _wait_oldest(self):
+        try:
+            self._pending.popleft().result()
+        except Exception as e:
+            if self._error is None:
+                self._error = e
+
+    def write(self, image, path, fmt='rgb'):
+        if self._pool is None:
+            raise ValueError('DeviceWriter.write after close()')
+        self._pending.append(write_batch([image], [path], self._pool, fmt=fmt)[0])
+        while len(self._pending) > self.max_pending:
+            self._wait_oldest()
+
+    def close(self):
+        if self._pool is None:
+            return
+        while self._pending:
+            self._wait_oldest()
+        self._pool.shutdown(wait=True)
+        self._pool = None
+        if self._error is not None:
+            raise self._error
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.close()
+            return False
+        try:                                                        # the block failed: finish what was handed over, its own failure is the one that is raised
+            self.close()
+        except Exception:
+            pass
+        return False

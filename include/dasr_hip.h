@@ -922,6 +922,22 @@ int dasr_png_emit(const dasr_png_strip* strips_dev, const dasr_png_strip* strips
 int dasr_png_pack(const dasr_png_image* images_dev, const dasr_png_image* images_host, int32_t n_images, const dasr_png_strip* strips_dev,
                   const dasr_png_strip* strips_host, int32_t n_strips, const uint32_t* sizes, const uint8_t* slots, int64_t slots_bytes, uint64_t* ws, uint8_t* out,
                   int64_t out_bytes, uint64_t* meta, void* stream);
+/* The same two stages for the other pixel layouts the drivers hold (`"device_png": true` of the SRN option files, `back_projection --device_png`,
+ * `dsn_create_dataset --device_png`); one batch has one fmt, with bpp bytes per pixel in source and file:
+ *   DASR_PNG_RGB  interleaved RGB, bpp 3: the bits of dasr_png_filter / dasr_png_pack.
+ *   DASR_PNG_BGR  interleaved BGR (util.tensor2img's order), bpp 3: byte j of a PNG row is source byte 3 (j / 3) + 2 - j % 3, its left and upper-left neighbours the same
+ *                 channel of the pixel to the left: the output of DASR_PNG_RGB on the channel-reversed image (the file is colour type 2, RGB).
+ *   DASR_PNG_GREY one channel [H, W], bpp 1, PNG colour type 0: a row has W bytes, the left neighbour is the byte before.
+ * Everything above holds with bpp in place of 3: n = rows (1 + bpp W), pitch >= bpp W, W <= (65 535 - 1) / bpp (21 844 or 65 534).  Any other fmt is DASR_EINVAL.
+ * dasr_png_codes and dasr_png_emit see filtered bytes and strip sizes only and serve every fmt. */
+#define DASR_PNG_RGB 0
+#define DASR_PNG_BGR 1
+#define DASR_PNG_GREY 2
+int dasr_png_filter_fmt(const dasr_png_image* images_dev, const dasr_png_image* images_host, int32_t n_images, const dasr_png_strip* strips_dev,
+                        const dasr_png_strip* strips_host, int32_t n_strips, uint8_t* filt, int64_t filt_bytes, uint32_t* hist, uint32_t* adler, int32_t fmt, void* stream);
+int dasr_png_pack_fmt(const dasr_png_image* images_dev, const dasr_png_image* images_host, int32_t n_images, const dasr_png_strip* strips_dev,
+                      const dasr_png_strip* strips_host, int32_t n_strips, const uint32_t* sizes, const uint8_t* slots, int64_t slots_bytes, uint64_t* ws, uint8_t* out,
+                      int64_t out_bytes, uint64_t* meta, int32_t fmt, void* stream);
 
 /* ---- profiling session (bench.py `roofline`) -----------------------------------------------------------
  * Between dasr_prof_begin and dasr_prof_end every kernel launch of the library (up to `capacity`) carries its own start/stop
