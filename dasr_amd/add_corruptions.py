@@ -12,8 +12,8 @@ Every image file of an input folder is decoded on host threads (PIL, imgio.decod
 noise -> blur -> JPEG: corrupt.gaussian_noise (one launch; image index = position of the file in the sorted list of its folder, so a file does not depend on thread
 counts or on the other files) and corrupt.jpeg_roundtrip (two launches; equal, bit for bit, to PIL's save + open with libjpeg-turbo) on the device.  --blur_std_dev is
 PIL's own extended box blur (ImageFilter.GaussianBlur), run on the host exactly as the reference runs it: one read-back and re-upload for that file, logged once.  The
-result is read back once and written as PNG under the input's base name on the host threads.  With --device_png the file is encoded on the device instead
-(png.write_batch: no read-back of the raw bytes, no PIL encode; the host threads add the container and the checksums); not together with --blur_std_dev, whose result
+result is read back once and written as PNG under the input's base name on the host threads of a png.FileWriter (PIL, level 6).  With --device_png the file is encoded
+on the device instead (the writer's device mode, png.write_batch: no read-back of the raw bytes, no PIL encode; the host threads add the container and the checksums); not together with --blur_std_dev, whose result
 is made on the host.
 
 The noise is NOT the reference's stream: utils.gaussian_noise draws from numpy's unseeded global generator, so its files differ from run to run; here they are a
@@ -25,8 +25,6 @@ anything is decoded or written."""
 import argparse
 import os
 import time
-from collections import deque
-from concurrent.futures import ThreadPoolExecutor
 
 from . import imgio, util
 from .dsn_data import is_image_file
@@ -97,31 +95,18 @@ def plan(o):
             raise ValueError('input folder %s does not exist' % src)
         if os.path.abspath(src) == os.path.abspath(dst):
             raise ValueError('output folder %s is its own input folder' % dst)
-        if not o.overwrite and os.path.isdir(dst) and os.listdir(dst):
-            raise ValueError('output folder %s already holds files (pass --overwrite to write into it)' % dst)
+        if not o.overwrite:
+            util.refuse_filled_folder(dst, 'output folder')
         names = sorted(x for x in os.listdir(src) if is_image_file(x))
         if not names:
             raise ValueError('input folder %s holds no image files' % src)
         files = []
         for index, name in enumerate(names):
             path = os.path.join(src, name)
-            H, W, mode = imgio.image_header(path)
-            if mode != 'RGB':
-                raise ValueError('%s: mode %s, expected an 8-bit RGB image' % (path, mode))
-            if H > 65535 or W > 65535:
-                raise ValueError('%s: %d x %d, a side above 65535' % (path, H, W))
-            if getattr(o, 'device_png', False) and W > 21844:
-                raise ValueError('%s: --device_png encodes rows of at most 21844 pixels, this file has %d (leave the flag out: PIL encodes on the host)' % (path, W))
+            H, W = imgio.rgb8_header(path, getattr(o, 'device_png', False))
             files.append((path, os.path.join(dst, name), index, H, W))
         work.append((dst, files))
     return work
-
-
-def _save_png(arr, path):
-    """RGB bytes [h, w, 3] -> a PNG file at `path`, whatever its extension (the reference writes 'PNG' under the input's base name)"""
-    from PIL import Image
-    Image.fromarray(arr).save(path, 'PNG', compress_level=PNG_COMPRESSION)
-    return path
 
 
 def _blur_host(dev_img, std):
@@ -135,7 +120,7 @@ def _blur_host(dev_img, std):
 
 def run(o, times=None):
     """main behind the argument parser.  `times`: a list that receives one dict of seconds per file ('decode' as the consumer waits for it, 'upload', 'kernels', 'blur',
-    'readback', 'submit' and 'encode_wait', the consumer's wait for the encoders; with --device_png 'device_png' in place of 'readback' and 'submit'); the device stages are then synchronised one by one, which an ordinary run does not do."""
+    'readback', 'submit' and 'encode_wait', the consumer's wait for the encoders, both from the writer; with --device_png 'device_png' in place of 'readback' and 'submit'); the device stages are then synchronised one by one, which an ordinary run does not do."""
     import torch
     from . import corrupt, png
     work = plan(o)
@@ -143,37 +128,20 @@ def run(o, times=None):
     device = imgio.device_of(None)
     for dst, _ in work:
         util.mkdir(dst)
-    written = []
     threads = max(1, min(imgio.MAX_DECODE_THREADS, int(o.num_workers)))
-    clock = time.perf_counter
-    if device_png:
-        print('--device_png: the PNG files are encoded on the device (filter, Huffman-only deflate), the host adds the container and the checksums')
+    clock, tick = time.perf_counter, imgio.tick
     if o.blur_std_dev is not None:
         print('--blur_std_dev %g: PIL GaussianBlur on the host, one read-back and re-upload per file' % o.blur_std_dev)
-
-    def tick(t, key, t0, sync=False):
-        if times is not None:
-            if sync:
-                torch.cuda.synchronize()
-            t[key] = t.get(key, 0.0) + clock() - t0
-        return clock()
-
-    with ThreadPoolExecutor(max_workers=threads) as enc:
-        pending = deque()   # the encode jobs in flight: at most 2 x threads results wait encoded or to be encoded next to the one in hand
-
-        def drain(keep):
-            while len(pending) > keep:
-                t0 = clock()
-                written.append(pending.popleft().result())
-                if times is not None:
-                    times[-1]['encode_wait'] = times[-1].get('encode_wait', 0.0) + clock() - t0
+    # at most 2 x threads results wait encoded or to be encoded next to the one in hand
+    with png.FileWriter(device_png, threads, compress_level=PNG_COMPRESSION) as writer:
         for dst, files in work:
             print('\nComputing images from directory ' + os.path.dirname(files[0][0]))
             decoded = imgio.decode_ahead(imgio.decode_u8, [(f[0],) for f in files], threads)
             t0 = clock()
             for img, (path, out_path, index, H, W) in zip(decoded, files):
-                t = {'file': path}
+                t = None
                 if times is not None:
+                    t = writer.times = {'file': path}   # (the writer adds 'device_png' or 'submit', and 'encode_wait')
                     times.append(t)
                 t0 = tick(t, 'decode', t0)
                 x = torch.from_numpy(img).to(device)
@@ -187,18 +155,12 @@ def run(o, times=None):
                 if o.jpg_quality is not None:
                     x = corrupt.jpeg_roundtrip(x, o.jpg_quality)
                     t0 = tick(t, 'kernels', t0, True)
-                if device_png:
-                    pending.append(png.write_batch([x], [out_path], enc)[0])
-                    t0 = tick(t, 'device_png', t0)
-                else:
-                    host = x.cpu().numpy()
+                if not device_png:
+                    x = x.cpu().numpy()
                     t0 = tick(t, 'readback', t0)
-                    pending.append(enc.submit(_save_png, host, out_path))
-                    t0 = tick(t, 'submit', t0)
-                drain(2 * threads)
+                writer.write(x, out_path)   # PNG bytes under the input's base name, whatever its extension (the reference writes 'PNG' there)
                 t0 = clock()
-        drain(0)
-    return written
+    return writer.paths
 
 
 def main(argv=None):

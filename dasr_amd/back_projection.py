@@ -5,15 +5,14 @@
 Every PNG file of --sr_dir is paired with the file of the same name in --lr_dir (main_bp.m:14-16).  The files are decoded on host threads (PIL, imgio.decode_ahead), the BYTES are
 uploaded, and everything per pixel runs on the device: byte / 255 as planar fp32 (imgio.planar_f32: dasr_u8_to_planar, MATLAB's im2double), `iters` iterations of
 backprojection.m (backproject.back_project), the clamp and rounding to bytes (metrics.tensor2img_device, MATLAB's imwrite of a double image).  The result is
-written as PNG under the same name in --out_dir.  Accepted input is 8-bit RGB; a missing partner or an SR size that is not 2, 3 or 4 times the LR size is a
-ValueError naming both files.  With --device_png the bytes are not read back: the device encodes the file (png.DeviceWriter, fmt 'bgr'; --num_workers host threads add
+written as PNG under the same name in --out_dir (png.FileWriter: by default the bytes are read back and PIL encodes them on the main thread).  Accepted input is 8-bit RGB; a missing partner or an SR size that is not 2, 3 or 4 times the LR size is a
+ValueError naming both files.  With --device_png the bytes are not read back: the device encodes the file (png.FileWriter in device mode, fmt 'bgr'; --num_workers host threads add
 the container and the checksums), the pixels are those of the default path.  With --reverse_filter the iterations are those of main_reverse_filter.m:18-22 (backproject.reverse_filter) instead, everything else
 as above."""
 import argparse
-import contextlib
 import os
 
-from . import imgio, util
+from . import imgio, png, util
 from .backproject import DEFAULT_ITERS, SCALES, back_project, reverse_filter
 
 
@@ -25,7 +24,7 @@ def parse_args(argv=None):
     p.add_argument('--iters', default=DEFAULT_ITERS, type=int, help='iterations (main_bp.m: 20)')
     p.add_argument('--num_workers', default=6, type=int, help='decode threads (at most %d)' % imgio.MAX_DECODE_THREADS)
     p.add_argument('--reverse_filter', action='store_true', help='run the reverse filter (main_reverse_filter.m) in place of the back-projection')
-    p.add_argument('--device_png', action='store_true', help='encode the PNG files on the device (png.DeviceWriter) instead of with PIL on the main thread')
+    p.add_argument('--device_png', action='store_true', help='encode the PNG files on the device (png.FileWriter in device mode) instead of with PIL on the main thread')
     return p.parse_args(argv)
 
 
@@ -59,29 +58,17 @@ def main(argv=None):
     pairs = list_pairs(o.sr_dir, o.lr_dir)
     device = imgio.device_of(None)
     util.mkdir(o.out_dir)
-    written = []
     project = reverse_filter if o.reverse_filter else back_project
 
     def load(sr_file, lr_file, _s):
         return imgio.decode_u8(sr_file), imgio.decode_u8(lr_file)
-    if o.device_png:
-        from .png import DeviceWriter
-        print('--device_png: the PNG files are encoded on the device (filter, Huffman-only deflate), the host adds the container and the checksums')
-        sink = DeviceWriter(o.num_workers)
-    else:
-        sink = contextlib.nullcontext()
-    with sink as writer:   # (leaving the block waits for every file of the writer)
+    # without --device_png the bytes are read back and encoded by PIL on this thread, inside write()
+    with png.FileWriter(o.device_png, o.num_workers if o.device_png else 0) as writer:
         for (sr_u8, lr_u8), (sr_file, _lr_file, _s) in zip(imgio.decode_ahead(load, pairs, o.num_workers), pairs):
             out = project(imgio.planar_f32(sr_u8, device, batch=True), imgio.planar_f32(lr_u8, device, batch=True), o.iters)
-            img = metrics.tensor2img_device(out)   # HWC BGR bytes, as util.tensor2img gives them
-            path = os.path.join(o.out_dir, os.path.basename(sr_file))
-            if writer is None:
-                util.save_img(img.cpu().numpy(), path)
-            else:
-                writer.write(img, path, 'bgr')
-            written.append(path)
+            writer.write(metrics.tensor2img_device(out), os.path.join(o.out_dir, os.path.basename(sr_file)), 'bgr')   # HWC BGR bytes, as util.tensor2img gives them
             print(os.path.basename(sr_file))
-    return written
+    return writer.paths
 
 
 if __name__ == '__main__':

@@ -5,21 +5,22 @@ For every target-domain HR image: fake LR = G(img) saved as PNG under <out>/imgs
 (float64 .npy, shape [1,1,h,w]; h/2 x w/2 for the wavelet filter) under <out>/ddm_target; with --including_source_ddm the map of
 every source-domain LR image under <out>/ddm_source.  Same flags as the reference; its `../paths.yml` lookup is replaced by
 --target_dir / --source_dir (or --dataset synthetic for seeded random images).  Generator / discriminator run on the HIP kernels
-(dasr_amd.dsn_model.DSNModel.translate / .ddm_of); image IO is PIL on the host.  With --device_png the fake LR images are quantised (metrics.tensor2img_device: the
-rounding of _save_png) and encoded on the device (png.DeviceWriter); the pixels of the files and the .npy maps are those of the default path.
+(dasr_amd.dsn_model.DSNModel.translate / .ddm_of); image IO is PIL on the host: a fake LR image is
+quantised as TF.to_pil_image does (clamp, x 255, round), read back and encoded on the main thread (png.FileWriter).  With --device_png it is quantised by
+metrics.tensor2img_device (the same rounding) and encoded on the device (the writer's device mode); the pixels of the files and the .npy maps are those of the default path.
 """
 import argparse
-import contextlib
 import os
 import shutil
 
 import numpy as np
 import torch
 
+from . import png
+from .dsn_data import is_image_file
 from .dsn_model import DSNModel
 from .imgio import decode_u8, u8_to_chw
-
-IMG_EXT = ('.png', '.jpg', '.jpeg', '.JPG', '.JPEG', '.PNG')
+from .metrics import tensor2img_device
 
 
 def build_parser():
@@ -45,19 +46,13 @@ def build_parser():
     p.add_argument('--paths', default='../paths.yml', type=str, help="yaml file with the dataset folders (the reference reads '../paths.yml', create_dataset_modified.py:49-50)")
     p.add_argument('--out_root', default='DSN_results', type=str)
     p.add_argument('--n_synthetic', default=4, type=int)
-    p.add_argument('--device_png', action='store_true', help='encode the fake LR images on the device (png.DeviceWriter) instead of with PIL on the main thread')
+    p.add_argument('--device_png', action='store_true', help='encode the fake LR images on the device (png.FileWriter in device mode) instead of with PIL on the main thread')
     p.add_argument('--num_workers', default=4, type=int, help='host threads of --device_png: the container, the checksums and the file write (at most 16)')
     return p
 
 
 def _load(path):
     return u8_to_chw(decode_u8(path)).unsqueeze(0).contiguous()
-
-
-def _save_png(t, path):
-    from PIL import Image
-    a = (t.clamp(0, 1) * 255.0).round().byte().permute(1, 2, 0).cpu().numpy()  # TF.to_pil_image: mul(255).byte() after clamp
-    Image.fromarray(a).save(path)
 
 
 # --dataset name -> (first key, second key) of paths.yml (codes/DSN/create_dataset_modified.py:52-81)
@@ -81,7 +76,7 @@ def _images(o, which):
     d = (o.target_dir if which == 'target' else o.source_dir) or _named_dir(o, which)
     if d:
         for f in sorted(os.listdir(d)):
-            if f.endswith(IMG_EXT):
+            if is_image_file(f):
                 yield f, _load(os.path.join(d, f))
     elif o.dataset == 'synthetic':
         g = torch.Generator().manual_seed(7 if which == 'target' else 8)
@@ -114,22 +109,16 @@ def main(argv=None):
     shutil.copyfile(o.checkpoint, os.path.join(out, o.name + '.tar'))
     dev = m.device
     n = 0
-    if o.device_png:
-        from .metrics import tensor2img_device
-        from .png import DeviceWriter
-        print('--device_png: the PNG files are encoded on the device (filter, Huffman-only deflate), the host adds the container and the checksums')
-        sink = DeviceWriter(o.num_workers)
-    else:
-        sink = contextlib.nullcontext()
-    with sink as writer:   # (leaving the block waits for every file of the writer)
+    # without --device_png the image is quantised by torch ops, read back and encoded by PIL on this thread, inside write()
+    with png.FileWriter(o.device_png, o.num_workers if o.device_png else 0) as writer:
         for name, img in _images(o, 'target'):
             H, W = img.shape[-2] // 4 * 4, img.shape[-1] // 4 * 4
             fake, _, ddm = m.translate(img[..., :H, :W].to(dev))
             path = os.path.join(dirs['imgs_from_target'], name.rsplit('.', 1)[0] + '.png')
-            if writer is None:
-                _save_png(fake[0], path)
-            else:
+            if o.device_png:
                 writer.write(tensor2img_device(fake[0]), path, 'bgr')   # HWC BGR bytes of rint(clamp(x, 0, 1) 255): the file is their RGB image
+            else:
+                writer.write((fake[0].clamp(0, 1) * 255.0).round().byte().permute(1, 2, 0), path)   # TF.to_pil_image: mul(255).byte() after clamp
             np.save(os.path.join(dirs['ddm_target'], name.split('.')[0]), ddm.double().cpu().numpy())
             n += 1
     if o.including_source_ddm:

@@ -4,6 +4,7 @@ device cache, and the descriptor upload in front of the batch-assembly launches.
 import ctypes as C
 import itertools
 import math
+import time
 from collections import deque
 from concurrent.futures import ThreadPoolExecutor
 
@@ -25,6 +26,31 @@ def image_header(path):
 
 def image_size(path):
     return image_header(path)[:2]
+
+
+def rgb8_header(path, device_png=False, unit_width=None):
+    """(H, W) of a file the folder CLIs accept, from its header: ValueError naming the file for a mode other than RGB, a side above 65535 or, with `device_png`, rows
+    wider than the device encoder takes (png.max_width('rgb')); `unit_width`: the width of what is encoded when that is not the whole file (prepare_data's sub-images)"""
+    from .png import max_width
+    H, W, mode = image_header(path)
+    if mode != 'RGB':
+        raise ValueError('%s: mode %s, expected an 8-bit RGB image' % (path, mode))
+    if H > 65535 or W > 65535:
+        raise ValueError('%s: %d x %d, a side above 65535' % (path, H, W))
+    if device_png and (unit_width or W) > max_width('rgb'):
+        raise ValueError('%s: --device_png encodes rows of at most %d pixels, %s has %d (leave the flag out: PIL encodes on the host)' % (
+            path, max_width('rgb'), 'this file' if unit_width is None else 'a unit here', unit_width or W))
+    return H, W
+
+
+def tick(times, key, t0, sync=False):
+    """THE stage clock: adds the seconds since t0 to times[key] and returns the new t0.  `times` None: nothing is measured and nothing synchronised; `sync`: the device is
+    synchronised first, so the stage's launches are in the number (which an ordinary run does not do)"""
+    if times is not None:
+        if sync:
+            torch.cuda.synchronize()
+        times[key] = times.get(key, 0.0) + time.perf_counter() - t0
+    return time.perf_counter()
 
 
 def decode_u8(path, box=None):

@@ -17,11 +17,15 @@ encode_batch / write_batch run it on uint8 device tensors: one descriptor upload
 
 `fmt` names what a batch holds: 'rgb' (the default) interleaved RGB [H, W, 3]; 'bgr' interleaved BGR [H, W, 3] as util.tensor2img / metrics.tensor2img_device return it, written as
 the RGB file of the channel-reversed image (the filter kernel reads the bytes in file order, nothing is permuted in memory); 'grey' one channel [H, W], colour type 0, one
-byte per pixel (rows of 1 + W filtered bytes, W <= 65 534).  DeviceWriter is the sink the drivers hand single images to: the device stages per image on the current stream,
-the container, the CRCs and the file write on its thread pool, a bounded number of files outstanding."""
+byte per pixel (rows of 1 + W filtered bytes, W <= 65 534).
+
+FileWriter is the sink every driver hands its images to, one at a time or all products of a file at once.  Device mode: the device stages per call on the current stream,
+the container, the CRCs and the file write on its thread pool.  Host mode: save_host (PIL) on the pool or, without threads, on the caller's thread.  Either way a bounded
+number of calls is outstanding and close() waits for every file."""
 import collections
 import heapq
 import struct
+import time
 import zlib
 
 import numpy as np
@@ -38,6 +42,7 @@ SIGNATURE = b'\x89PNG\r\n\x1a\n'
 HOST_PATH = "PIL's Image.save"
 FORMATS = {'rgb': (0, 3), 'bgr': (1, 3), 'grey': (2, 1)}   # fmt -> (DASR_PNG_RGB / _BGR / _GREY, bytes per pixel)
 MAX_WRITER_THREADS = 16
+DEVICE_NOTE = '--device_png: the PNG files are encoded on the device (filter, Huffman-only deflate), the host adds the container and the checksums'
 
 
 def _format(fmt):
@@ -378,20 +383,14 @@ def codes_batch(hist):
 def _encode_device(images, times=None, fmt='rgb'):
     """stages 1-4 and the two read-backs -> (plan, meta int64 host array, packed bytes uint8 host array).  `times`: a dict that receives the seconds of 'plan' (the tables
     and their upload), 'kernels', 'readback_meta' and 'readback_bytes'; the stream is then synchronised in between, which an ordinary call does not do."""
-    import time
     import torch
     from . import _lib
     from .engine import _stream
+    from .imgio import tick
     L = _lib.lib()
-
-    def tick(key, t0):
-        if times is not None:
-            torch.cuda.synchronize()
-            times[key] = times.get(key, 0.0) + time.perf_counter() - t0
-        return time.perf_counter()
     t0 = time.perf_counter()
     plan = Plan(images, fmt)
-    t0 = tick('plan', t0)
+    t0 = tick(times, 'plan', t0, True)
     plan, filt, hist, meta = filter_batch(images, plan)
     lens, codes, hdr = codes_batch(hist)
     dev = plan.device
@@ -404,13 +403,13 @@ def _encode_device(images, times=None, fmt='rgb'):
                                plan.slot_bytes, sizes.data_ptr(), meta.data_ptr(), _stream()), 'dasr_png_emit')
     _lib.check(L.dasr_png_pack_fmt(plan.images_dev, ih, plan.n_images, plan.strips_dev, sh, plan.n_strips, sizes.data_ptr(), slots.data_ptr(), plan.slot_bytes, ws.data_ptr(),
                                    out.data_ptr(), plan.slot_bytes, meta.data_ptr(), plan.fmt_code, _stream()), 'dasr_png_pack_fmt')
-    t0 = tick('kernels', t0)
+    t0 = tick(times, 'kernels', t0, True)
     m = meta.cpu().numpy()                                                       # read-back 1: status, sizes and offsets, Adler partials
     if m[0] != 0:
         raise _lib.DasrHipError('the device PNG encoder reported status %d: a strip did not fit its slot' % m[0])
-    t0 = tick('readback_meta', t0)
+    t0 = tick(times, 'readback_meta', t0, True)
     packed = out[:int(m[1])].cpu().numpy()                                       # read-back 2: the bytes
-    tick('readback_bytes', t0)
+    tick(times, 'readback_bytes', t0, True)
     return plan, m, packed
 
 
@@ -450,41 +449,90 @@ def write_batch(images, paths, pool, times=None, fmt='rgb'):
     return [pool.submit(_write, plan, m, packed, k, p) for k, p in enumerate(paths)]
 
 
-class DeviceWriter:
-    """the sink of the drivers that write one image at a time: `with DeviceWriter(threads) as w: w.write(u8_device_tensor, path, fmt)`.  write() runs write_batch for that
-    image on the current stream and returns once its two read-backs are done (until then the call holds the tensor; afterwards the caller may reuse it); the container, the
-    CRCs and the file write run on the writer's own pool of at most 16 threads.  At most 2 x threads files are outstanding: beyond that write() waits for the oldest.  close()
-    (or leaving the block) waits for all of them and raises the first failure, so a driver cannot return before its files are complete."""
+def save_host(array, path, fmt='rgb', compress_level=6):
+    """THE host saver: uint8 [H, W, 3] ('grey': [H, W]) -> a PNG file at `path`, whatever its extension, through PIL at zlib level `compress_level` (6 is PIL's default; the
+    pixels do not depend on it).  'bgr': the RGB file of the channel-reversed image, as encode_batch writes it.  Returns the path."""
+    from PIL import Image
+    array = np.asarray(array)
+    if array.dtype != np.uint8 or array.ndim != (3 if _format(fmt)[1] == 3 else 2):
+        raise ValueError("the image must be uint8 %s for fmt %r, got %s %s" % ('[H, W, 3]' if fmt != 'grey' else '[H, W]', fmt, array.dtype, array.shape))
+    array = np.ascontiguousarray(array[:, :, ::-1] if fmt == 'bgr' else array)   # (a slice of a larger image is copied here, on the thread that encodes it)
+    Image.fromarray(array).save(path, 'PNG', compress_level=compress_level)
+    return path
 
-    def __init__(self, threads=4):
+
+class FileWriter:
+    """the sink every driver hands its 8-bit images to: `with FileWriter(device, threads) as w: w.write(image, path, fmt)`.
+    device=True: `image` is a uint8 device tensor; a call is ONE write_batch on the current stream and returns once its two read-backs are done (until then the call holds
+    the tensors; afterwards the caller may reuse them); the container, the CRCs and the file write run on the writer's own pool of at most 16 threads.
+    device=False: `image` is a host uint8 array, or a device tensor that is read back here, on the caller's thread; every image is one save_host job at `compress_level` on
+    the pool -- with threads=0 on the caller's thread, before write() returns.
+    At most `max_pending` (default 2 x threads) CALLS are outstanding: beyond that a call waits for the oldest.  close() (or leaving the block) waits for all of them and
+    raises the first failure, so a driver cannot return before its files are complete.  `paths`: every path handed over, in submission order.  `waited`: the seconds the
+    caller has spent waiting for the pool.  `times`: a dict the caller may set (per file, say) that receives the seconds of the hand-over ('device_png': the batch's tables,
+    launches and read-backs; 'submit' in host mode) and 'encode_wait'.  `note`: printed once by a device-mode writer (None: the driver logs its own line)."""
+
+    def __init__(self, device, threads=4, max_pending=None, compress_level=6, note=DEVICE_NOTE, save=save_host):
         from concurrent.futures import ThreadPoolExecutor
-        self.threads = max(1, min(int(threads), MAX_WRITER_THREADS))
-        self.max_pending = 2 * self.threads
-        self._pool = ThreadPoolExecutor(max_workers=self.threads)
-        self._pending = collections.deque()
-        self._error = None
+        self.device = bool(device)
+        self.threads = 0 if int(threads) <= 0 and not self.device else max(1, min(int(threads), MAX_WRITER_THREADS))
+        self.max_pending = 2 * self.threads if max_pending is None else int(max_pending)
+        self.compress_level, self._save = compress_level, save
+        self._pool = ThreadPoolExecutor(max_workers=self.threads) if self.threads else None
+        self._pending = collections.deque()                         # the futures of one call each
+        self._error, self._closed = None, False
+        self.paths, self.waited, self.times = [], 0.0, None
+        if self.device and note:
+            print(note)
 
-    def _wait_oldest(self):
-        try:
-            self._pending.popleft().result()
-        except Exception as e:
-            if self._error is None:
-                self._error = e
+    def _add(self, key, seconds):
+        if self.times is not None:
+            self.times[key] = self.times.get(key, 0.0) + seconds
+        return seconds
+
+    def _wait_until(self, keep):
+        while len(self._pending) > keep:
+            t0 = time.perf_counter()
+            for fut in self._pending.popleft():
+                try:
+                    fut.result()
+                except Exception as e:
+                    if self._error is None:
+                        self._error = e
+            self.waited += self._add('encode_wait', time.perf_counter() - t0)
+
+    def write_many(self, images, paths, fmt='rgb'):
+        if self._closed:
+            raise ValueError('FileWriter.write after close()')
+        images, paths = list(images), list(paths)
+        if len(images) != len(paths):
+            raise ValueError('paths: %d paths for %d images' % (len(paths), len(images)))
+        t0, jobs = time.perf_counter(), []
+        if self.device:
+            jobs = write_batch(images, paths, self._pool, fmt=fmt)
+        else:
+            for a, p in zip(images, paths):
+                a = a.cpu().numpy() if hasattr(a, 'cpu') else a
+                if self._pool is None:
+                    self._save(a, p, fmt, self.compress_level)
+                else:
+                    jobs.append(self._pool.submit(self._save, a, p, fmt, self.compress_level))
+        self.paths += paths
+        self._add('device_png' if self.device else 'submit', time.perf_counter() - t0)
+        if jobs:
+            self._pending.append(jobs)
+            self._wait_until(self.max_pending)
 
     def write(self, image, path, fmt='rgb'):
-        if self._pool is None:
-            raise ValueError('DeviceWriter.write after close()')
-        self._pending.append(write_batch([image], [path], self._pool, fmt=fmt)[0])
-        while len(self._pending) > self.max_pending:
-            self._wait_oldest()
+        self.write_many([image], [path], fmt)
 
     def close(self):
-        if self._pool is None:
+        if self._closed:
             return
-        while self._pending:
-            self._wait_oldest()
-        self._pool.shutdown(wait=True)
-        self._pool = None
+        self._closed = True
+        self._wait_until(0)
+        if self._pool is not None:
+            self._pool.shutdown(wait=True)
         if self._error is not None:
             raise self._error
 
@@ -500,3 +548,8 @@ class DeviceWriter:
         except Exception:
             pass
         return False
+
+
+def DeviceWriter(threads=4):
+    """FileWriter in device mode without the note: what the option-file drivers and the tests of the device path construct"""
+    return FileWriter(True, threads, note=None)

@@ -5,7 +5,7 @@ For every dataset of the option file: feed_data -> train.run_inference -> train.
 Y channel, per image and averaged (same log lines as the reference).  `device_metrics: true` quantises the images and evaluates the four numbers on the
 GPU (dasr_amd/metrics.py) instead of with util.host_scores on get_current_visuals; absent, the host path is unchanged.  `chop: true` runs the quadrant inference.  `self_ensemble: true` replaces test() by test_x8(), the x8 geometric self-ensemble (SR_model.py:102-140), everything downstream unchanged.  `back_projection: true | N` back-projects every SR image onto its LR image (20 | N iterations, dasr_amd/backproject.py) before it is saved and scored.  `val_lpips: true` adds the
 LPIPS(alex) distance of the 8-bit images (test.py:88-128; weights from `path.lpips_alexnet` / `path.lpips_lin`, seeded when absent).
-`device_png: true` hands the quantised SR image to the device PNG encoder (dasr_amd/png.py) instead of reading it back for PIL; the pixels of the files are the same.
+Every SR image goes to one png.FileWriter per dataset: PIL on this thread, or, under `device_png: true`, the quantised image stays on the device and the device PNG encoder writes it (dasr_amd/png.py); the pixels of the files are the same.
 `save_RealorFake` needs the discriminator visual, not available here: NotImplementedError.  Datasets: `mode: "LRHR"` (HR folder, LR folder or LR made by bicubic down-sampling) and `mode: "LR"` read image folders through data.EvalFolderDataset; `mode: "synthetic"` ships
 seeded LR/HR pairs; any iterable of the reference's batch dicts works through `main(loaders=...)`.
 """
@@ -16,13 +16,14 @@ import time
 from collections import OrderedDict
 
 from . import options as option
-from . import util
+from . import png, util
 from .models import create_model
-from .train import BACK_PROJECTION_NOTE, DEVICE_PNG_NOTE, SELF_ENSEMBLE_NOTE, create_dataset, run_inference, save_sr, setup_logger, sr_and_scores, sr_writer
+from .train import BACK_PROJECTION_NOTE, DEVICE_PNG_NOTE, DEVICE_PNG_THREADS, SELF_ENSEMBLE_NOTE, create_dataset, run_inference, setup_logger, sr_and_scores
 
 
 def evaluate(model, loader, opt, dataset_dir, logger, scale):
-    with sr_writer(opt) as writer:   # `device_png`: the files of this dataset are complete when the block is left
+    # `device_png`: the device encoder; else PIL on this thread, inside write().  The files of this dataset are complete when the block is left
+    with png.FileWriter(opt['device_png'], DEVICE_PNG_THREADS if opt['device_png'] else 0, note=None) as writer:
         return _evaluate(model, loader, opt, dataset_dir, logger, scale, writer)
 
 
@@ -35,7 +36,7 @@ def _evaluate(model, loader, opt, dataset_dir, logger, scale, writer):
         run_inference(model, opt)
         sr_img, m, lpips = sr_and_scores(model, opt, need_HR, scale)   # `device_metrics`: quantised and scored on the GPU, the same bytes and numbers
         suffix = opt['suffix']
-        save_sr(writer, sr_img, os.path.join(dataset_dir, img_name + (suffix or '') + '.png'))
+        writer.write(sr_img, os.path.join(dataset_dir, img_name + (suffix or '') + '.png'), 'bgr' if sr_img.ndim == 3 else 'grey')
         if not need_HR:
             logger.info(img_name)
             continue

@@ -9,7 +9,6 @@ synthetic dataset (`datasets.train.mode: "synthetic"`) used by the benchmark and
 torch.distributed.run every rank takes its shard of each batch (dasr_amd.dist.shard_minibatch).
 """
 import argparse
-import contextlib
 import logging
 import math
 import os
@@ -20,7 +19,7 @@ import numpy as np
 import torch
 
 from . import options as option
-from . import util
+from . import png, util
 from .dist import DataParallelGroup, shard_minibatch
 from .models import create_model
 
@@ -100,7 +99,7 @@ def create_dataset(ds_opt, opt):
 SELF_ENSEMBLE_NOTE = 'self_ensemble: x8 self-ensemble inference is on (test_x8: the generator on the eight flips / transposes of every LR image, their SR images averaged)'
 BACK_PROJECTION_NOTE = 'back_projection: every SR image is back-projected onto its LR image, {:d} iterations on the GPU (csrc/imgio.hip), before it is saved and scored'
 DEVICE_PNG_NOTE = 'device_png: SR images are encoded on the device (csrc/png.hip)'
-DEVICE_PNG_THREADS = 4   # host threads of a driver's png.DeviceWriter: the container, the CRCs and the file write
+DEVICE_PNG_THREADS = 4   # host threads of a driver's png.FileWriter under `device_png`: the container, the CRCs and the file write
 
 
 def run_inference(model, opt):
@@ -115,7 +114,7 @@ def sr_and_scores(model, opt, need_HR, crop, ssim=True, y=True):
     """what the drivers take from the trainer after run_inference: (the SR image as uint8 HWC BGR / HW, the util.host_scores dict against the ground truth or None
     without HR, LPIPS or None without `val_lpips`).  `device_metrics`: the image is quantised and the four numbers are formed on the GPU (BaseModel.current_sr_u8 /
     current_metrics, dasr_amd/metrics.py, imported only then); absent: get_current_visuals and util.host_scores (`ssim`, `y`: what the host path evaluates).
-    `device_png`: the SR image stays a uint8 DEVICE tensor of the same bytes (metrics.tensor2img_device, made once) for save_sr; without `device_metrics` it is read back once
+    `device_png`: the SR image stays a uint8 DEVICE tensor of the same bytes (metrics.tensor2img_device, made once) for the writer; without `device_metrics` it is read back once
     for util.host_scores."""
     if opt['device_png']:
         from .metrics import tensor2img_device
@@ -139,26 +138,10 @@ def sr_and_scores(model, opt, need_HR, crop, ssim=True, y=True):
     return sr_img, scores, (visuals['LPIPS'] if opt['val_lpips'] else None)
 
 
-def sr_writer(opt):
-    """context manager of a driver's pass over a dataset: a png.DeviceWriter under `device_png` (leaving the block waits for every file and raises the first failure),
-    else None: save_sr then writes with util.save_img as before"""
-    if opt['device_png']:
-        from .png import DeviceWriter
-        return DeviceWriter(DEVICE_PNG_THREADS)
-    return contextlib.nullcontext()
-
-
-def save_sr(writer, sr_img, path):
-    """the SR image of sr_and_scores to `path`: host bytes through util.save_img, or (a writer) the device tensor, HWC BGR or HW, through the device encoder"""
-    if writer is None:
-        util.save_img(sr_img, path)
-    else:
-        writer.write(sr_img, path, 'bgr' if sr_img.dim() == 3 else 'grey')
-
-
 def validate(model, val_set, opt, current_step, logger):
     """validation pass of codes/SRN/train.py:174-235: test() per image, SR image saved, PSNR on the `scale`-pixel-cropped uint8 images"""
-    with sr_writer(opt) as writer:
+    # `device_png`: the device encoder, leaving the block waits for every file; else PIL on this thread, inside write() (DEVICE_PNG_NOTE is logged once per run, not per pass)
+    with png.FileWriter(opt['device_png'], DEVICE_PNG_THREADS if opt['device_png'] else 0, note=None) as writer:
         return _validate(model, val_set, opt, current_step, logger, writer)
 
 
@@ -178,7 +161,7 @@ def _validate(model, val_set, opt, current_step, logger, writer):
             avg_lpips += float(lpips)
             log_info += '         {}:{:.3f}'.format(model.lpips_label, float(lpips))
         logger.info(log_info)
-        save_sr(writer, sr_img, os.path.join(img_dir, '{:s}_{:d}.png'.format(img_name, current_step)))
+        writer.write(sr_img, os.path.join(img_dir, '{:s}_{:d}.png'.format(img_name, current_step)), 'bgr' if sr_img.ndim == 3 else 'grey')
         if scores is not None:
             avg_psnr += scores['psnr']
     avg_psnr = avg_psnr / max(idx, 1)

@@ -12,7 +12,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, png
 from .engine import _stream
 
 
@@ -58,11 +58,15 @@ def tensor2img(tensor, out_type=np.uint8, min_max=(0, 1)):
     return img.astype(out_type)
 
 
+def refuse_filled_folder(path, what):
+    """ValueError if the output folder `path` already holds files; `what` names it in the message ('--lr_dir', 'output folder').  The CLIs call it unless --overwrite is given"""
+    if os.path.isdir(path) and os.listdir(path):
+        raise ValueError('%s %s already holds files (pass --overwrite to write into it)' % (what, path))
+
+
 def save_img(img, img_path, mode='RGB'):
     """BGR (or gray) uint8 array -> PNG (the reference writes through cv2.imwrite)"""
-    from PIL import Image
-    arr = img[:, :, ::-1] if img.ndim == 3 else img
-    Image.fromarray(np.ascontiguousarray(arr)).save(img_path)
+    png.save_host(img, img_path, 'bgr' if img.ndim == 3 else 'grey')
 
 
 def bgr2ycbcr(img, only_y=True):

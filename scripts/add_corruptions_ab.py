@@ -78,7 +78,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit('needs the GPU: a timing taken anywhere else says nothing about it')
     from PIL import Image
-    from dasr_amd import add_corruptions, corrupt, imgio
+    from dasr_amd import add_corruptions, corrupt, imgio, png
     dev = torch.device('cuda')
     lines = ['# scripts/add_corruptions_ab.py --files %d --workers %d --reps %d: %s, torch %s, PIL %s' % (
         args.files, args.workers, args.reps, torch.cuda.get_device_name(0), torch.__version__, Image.__version__)]
@@ -153,7 +153,7 @@ def main():
         t_dec = time.perf_counter() - t0
         res = np.array(Image.open(os.path.join(out, '0001.png')))
         t0 = time.perf_counter()
-        add_corruptions._save_png(res, os.path.join(root, 'enc.png'))
+        png.save_host(res, os.path.join(root, 'enc.png'), 'rgb', add_corruptions.PNG_COMPRESSION)
         t_enc = time.perf_counter() - t0
         t0 = time.perf_counter()
         noisy = np.clip(a + np.rint(np.random.normal(loc=0.0, scale=8.0, size=a.shape)), 0, 255).astype(np.uint8)   # utils.gaussian_noise

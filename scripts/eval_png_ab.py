@@ -1,4 +1,4 @@
-"""A/B of the option key `"device_png": true` (SR images encoded by csrc/png.hip through png.DeviceWriter) against the default path (util.save_img: PIL, compress_level 6,
+"""A/B of the option key `"device_png": true` (SR images encoded by csrc/png.hip through png.FileWriter) against the default path (png.save_host on the main thread: PIL, compress_level 6,
 on the main thread) in the drivers that write SR images, in ONE process, the two variants alternating:
 
   1. `python -m dasr_amd.test` (test.main) on a folder of --pairs LR/HR PNG pairs, RRDB_net nf 64 nb 23, `chop`, `device_metrics: true`, at every --sizes entry
@@ -31,7 +31,7 @@ if ROOT not in sys.path:
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-STAGES = ('run_inference', 'sr_and_scores', 'save_sr')
+STAGES = ('run_inference', 'sr_and_scores', 'write')   # (write: png.FileWriter.write, the one place both paths save an image)
 
 
 def write_pairs(lr_dir, hr_dir, n, h, w):
@@ -79,8 +79,8 @@ class Clock:
     def __init__(self, module, outer):
         self.module, self.outer, self.t, self.wall, self.saved = module, outer, {}, 0.0, {}
 
-    def _wrap(self, name, is_outer):
-        fn = getattr(self.module, name)
+    def _wrap(self, owner, name, is_outer):
+        fn = getattr(owner, name)
 
         def timed(*a, **k):
             torch.cuda.synchronize()
@@ -93,18 +93,19 @@ class Clock:
             else:
                 self.t[name] = self.t.get(name, 0.0) + dt
             return r
-        self.saved[name] = fn
-        setattr(self.module, name, timed)
+        self.saved[(owner, name)] = fn
+        setattr(owner, name, timed)
 
     def __enter__(self):
+        from dasr_amd import png
         for name in STAGES:
-            self._wrap(name, False)
-        self._wrap(self.outer, True)
+            self._wrap(png.FileWriter if name == 'write' else self.module, name, False)
+        self._wrap(self.module, self.outer, True)
         return self
 
     def __exit__(self, *exc):
-        for name, fn in self.saved.items():
-            setattr(self.module, name, fn)
+        for (owner, name), fn in self.saved.items():
+            setattr(owner, name, fn)
         return False
 
 
@@ -151,8 +152,8 @@ def main():
     from dasr_amd import back_projection, options, test as dtest, train
     from dasr_amd.models import create_model
     sizes = [tuple(int(v) for v in s.split('x')) for s in a.sizes.split(',')]
-    lines = ['SR images written by the device PNG encoder (`"device_png": true`, `--device_png`; png.DeviceWriter, %d host threads in the option-file drivers) against '
-             "the default path (util.save_img: PIL's Image.save, compress_level 6, main thread)" % train.DEVICE_PNG_THREADS,
+    lines = ['SR images written by the device PNG encoder (`"device_png": true`, `--device_png`; png.FileWriter, %d host threads in the option-file drivers) against '
+             "the default path (png.save_host: PIL's Image.save, compress_level 6, main thread)" % train.DEVICE_PNG_THREADS,
              'device: %s; host: %d CPUs available to the process, torch %s, numpy %s' % (torch.cuda.get_device_name(0), len(os.sched_getaffinity(0)), torch.__version__,
                                                                                        np.__version__),
              '%d pairs per folder (a smooth field plus noise of deviation 0.02), RRDB_net nf 64 nb 23 with the weights of write_generator (the SR image is the '

@@ -7,6 +7,9 @@ bicubic) and then runs each main(argv) --runs times in-process; one line per CLI
 network's code objects and is the warm-up).  Folders: 5 pairs of 1356 x 2040 with 6 decode threads, 40 pairs of 340 x 512 with 2.  The hand-off: 100 calls between
 two device synchronisations on one 1356 x 2040 image, --runs times.
 
+The drivers that write PNG files (`png ...` reports, on the 5-file folders only; `--only png` selects them): prepare_data --sub_dir --lr_dir --bic_dir and
+add_corruptions (noise 8, JPEG 30) over the 1356 x 2040 ground-truth files, each with and without --device_png, and back_projection --device_png; ms per file.
+
 The lines go to stdout and are appended to --out.  Nothing here is asserted by a test.
 
     python scripts/folder_cli_ab.py [--tree PATH] [--label NAME] [--runs 7] [--only TEXT] [--out profiles/eval_refactor_raw.txt]
@@ -37,7 +40,7 @@ def main():
     import numpy as np
     import torch
     from PIL import Image
-    from dasr_amd import back_projection as B, dsn_evaluate as E, imgio, metrics   # (first: evaluate_ab puts its own checkout in front of sys.path)
+    from dasr_amd import add_corruptions as A, back_projection as B, dsn_evaluate as E, imgio, metrics, prepare_data as P   # (first: evaluate_ab puts its own checkout in front of sys.path)
     from evaluate_ab import write_pair
     if not os.path.abspath(E.__file__).startswith(root + os.sep):
         raise SystemExit('dasr_amd was imported from %s, not from --tree %s' % (E.__file__, root))
@@ -74,6 +77,17 @@ def main():
                 ['--dir', res, '--gt_dir', gt, '--border_crop', '4', '--allow_random_perceptual', '--num_workers', str(workers)]), n)
             report('back_projection.main', name, 'ms per pair', lambda: B.main(
                 ['--lr_dir', lr, '--sr_dir', res, '--out_dir', out, '--num_workers', str(workers)]), n)
+            if k:
+                continue
+            for flag in ([], ['--device_png']):
+                tag, sub = ' '.join(flag), os.path.join(out, 'png' + ''.join(flag))
+                report(('png prepare_data ' + tag).strip(), name, 'ms per file', lambda: P.main(
+                    ['--input_dir', gt, '--sub_dir', os.path.join(sub, 'sub'), '--lr_dir', os.path.join(sub, 'lr'), '--bic_dir', os.path.join(sub, 'bic'), '--overwrite',
+                     '--num_workers', str(workers)] + flag), n)
+                report(('png add_corruptions ' + tag).strip(), name, 'ms per file', lambda: A.main(
+                    ['--input_dir', gt, '--output_dir', os.path.join(sub, 'noisy'), '--overwrite', '--num_workers', str(workers)] + flag), n)
+            report('png back_projection --device_png', name, 'ms per file', lambda: B.main(
+                ['--lr_dir', lr, '--sr_dir', res, '--out_dir', os.path.join(out, 'png_bp'), '--num_workers', str(workers), '--device_png']), n)
     dev = imgio.device_of(None)
     img = np.random.RandomState(0).randint(0, 256, size=(1356, 2040, 3)).astype(np.uint8)
     on_dev = torch.from_numpy(img).to(dev)

@@ -106,7 +106,7 @@ def main():
             with ThreadPoolExecutor(max_workers=threads) as pool:
                 for _ in range(max(2, args.reps // 3) + 1):
                     t0 = time.perf_counter()
-                    list(pool.map(prepare_data._save_rgb, arrays, paths))
+                    list(pool.map(lambda arr, path: png.save_host(arr, path, 'rgb', prepare_data.PNG_COMPRESSION), arrays, paths))
                     ts.append(time.perf_counter() - t0)
             t_pil[threads] = ts[1:]
             lines.append('pil     %2d thread(s), zlib level %d, %d products into files: %s' % (threads, prepare_data.PNG_COMPRESSION, len(arrays), med_ms(ts[1:])))

@@ -83,7 +83,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit('needs the GPU: a timing taken anywhere else says nothing about it')
     from PIL import Image
-    from dasr_amd import backproject, bicubic, imgio, prepare_data
+    from dasr_amd import backproject, bicubic, imgio, png, prepare_data
     from dasr_amd.data import imresize_matlab
     dev = torch.device('cuda')
     torch.set_num_threads(16)
@@ -125,7 +125,7 @@ def main():
         arrays = [np.array(Image.open(p)) for p in products]
         t0 = time.perf_counter()
         for a, p in zip(arrays, products):
-            prepare_data._save_rgb(a, p)
+            png.save_host(a, p, 'rgb', prepare_data.PNG_COMPRESSION)
         t_enc = time.perf_counter() - t0
         lines.append('codec   one thread: decode of one file %.0f ms, PNG encoding of its %d products at zlib level %d %.0f ms; upload + launches + read-back %.1f ms per file (median), %.2f %% of'
                      ' decode + encode' % (1e3 * t_dec, len(products), prepare_data.PNG_COMPRESSION, 1e3 * t_enc, dev_ms, 100 * dev_ms / (1e3 * (t_dec + t_enc))))

@@ -215,3 +215,49 @@ def test_dsn_create_dataset_cli(tmp_path):
         assert len(files) == n and files == sorted(os.listdir(str(tmp_path / 'res' / 'dev' / sub)))
         for f in files:
             assert (tmp_path / 'res' / 'host' / sub / f).read_bytes() == (tmp_path / 'res' / 'dev' / sub / f).read_bytes(), f
+
+
+def test_file_writer_device_and_host_mode(tmp_path):
+    """7 x 5 x 3, a 39 x 27 window of a 64 x 64 x 3 tensor (row pitch 192 bytes for rows of 81) and 20 x 12 grey: the device mode writes the files of png.encode_batch,
+    through write_many (one batch) and through three write calls; the host mode reads the tensors back and writes the same pixels"""
+    _gpu()
+    from dasr_amd import png
+    dev = torch.device('cuda')
+    big = torch.from_numpy(png.photo(64, 64, 2)).to(dev)
+    colour = [torch.from_numpy(png.photo(7, 5, 1)).to(dev), big[11:50, 20:47]]
+    grey = torch.from_numpy(np.ascontiguousarray(png.photo(20, 12, 3)[:, :, 1])).to(dev)
+    assert colour[1].stride(0) == 192 and tuple(colour[1].shape) == (39, 27, 3)
+    want = png.encode_batch(colour) + png.encode_batch([grey], fmt='grey')
+    names = ['a.png', 'window.png', 'grey.png']
+
+    def run(folder, device, many):
+        folder.mkdir()
+        paths = [str(folder / n) for n in names]
+        with png.FileWriter(device, 2, note=None) as w:
+            if many:
+                w.write_many(colour, paths[:2])
+            else:
+                w.write(colour[0], paths[0])
+                w.write(colour[1], paths[1])
+            w.write(grey, paths[2], 'grey')
+        assert w.paths == paths
+        return [open(p, 'rb').read() for p in paths]
+    assert run(tmp_path / 'many', True, True) == want
+    assert run(tmp_path / 'single', True, False) == want
+    from PIL import Image
+
+    def decoded(folder):
+        out = []
+        for n in names:
+            with Image.open(str(folder / n)) as im:
+                assert im.format == 'PNG'
+                out.append((im.mode, np.array(im)))
+        return out
+    dev_files = decoded(tmp_path / 'many')
+    assert [(m, a.shape) for m, a in dev_files] == [('RGB', (7, 5, 3)), ('RGB', (39, 27, 3)), ('L', (20, 12))]
+    for (_, a), t in zip(dev_files, colour + [grey]):
+        assert np.array_equal(a, t.cpu().numpy())
+    for many in (True, False):
+        run(tmp_path / ('host%d' % many), False, many)
+        for (m, a), (hm, ha) in zip(dev_files, decoded(tmp_path / ('host%d' % many))):
+            assert m == hm and np.array_equal(a, ha)

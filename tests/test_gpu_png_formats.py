@@ -1,4 +1,4 @@
-"""GPU: the pixel formats of the device PNG encoder (`fmt='bgr'` / `'grey'` of dasr_amd/png.py; dasr_png_filter_fmt / dasr_png_pack_fmt of csrc/png.hip) and png.DeviceWriter.
+"""GPU: the pixel formats of the device PNG encoder (`fmt='bgr'` / `'grey'` of dasr_amd/png.py; dasr_png_filter_fmt / dasr_png_pack_fmt of csrc/png.hip) and the device mode of png.FileWriter (png.DeviceWriter).
 The filter stage bit for bit against png.filter_ref (types, bytes, histograms, Adler partials, the combined Adler-32 against zlib's), fmt 0 against dasr_png_filter, what the
 two entry points refuse, whole batches by what the files decode and inflate to, and the writer against encode_batch.
 
