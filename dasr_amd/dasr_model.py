@@ -19,8 +19,8 @@ import torch
 
 from . import _lib
 from ._lib import make_op
-from .engine import BTensor, OpList, NULL_T, Tensor, _stream, set_reduce_scale
-from .gan_nets import (NLayerDiscriminatorHIP, DiscriminatorVGG128HIP, VGGFeatureHIP, VGG_MEAN, VGG_STD, nlayer_d_spec, vgg128_spec,
+from .engine import BTensor, OpList, NULL_T, _stream, set_reduce_scale, dp_world
+from .gan_nets import (NLayerDiscriminatorHIP, DiscriminatorVGG128HIP, VGGFeatureHIP, FreqSplit, VGG_MEAN, VGG_STD, nlayer_d_spec, vgg128_spec,
                        vgg128_init_state_dict)
 from .init import kaiming_state_dict
 from .lpips import load_lpips
@@ -31,21 +31,6 @@ logger = logging.getLogger('base')
 A_PIX, A_LL, A_FEA, A_GAN, A_DREAL, A_DFAKE, A_SREAL, A_SFAKE = range(8)
 A_GAN_SRC, A_DREAL_SRC, A_DFAKE_SRC, A_SREAL_SRC, A_SFAKE_SRC = range(8, 13)   # source-domain discriminator (gan_H_source > 0)
 N_ACC = 16
-
-
-def _nview(bt, n0):
-    """view of images [n0:] of a blocked tensor"""
-    v = bt.view()
-    return Tensor(v.p + n0 * v.n_stride * bt.esz, v.n_stride, v.cb_stride)
-
-
-def gaussian_kernel2d(k):
-    """GaussianFilter weights (architecture.py:1177-1199)"""
-    mean, var = (k - 1) / 2.0, (k / 6.0) ** 2.0
-    ax = torch.arange(k, dtype=torch.float32)
-    xx = ax.repeat(k).view(k, k)
-    g = torch.exp(-((xx - mean) ** 2 + (xx.t() - mean) ** 2) / (2 * var))
-    return g / g.sum()
 
 
 def vgg_random_state_dict(spec, seed):
@@ -110,14 +95,7 @@ class DASR_Model(BaseModel):
         self.load()
         self.norm = bool(t['norm'])
         self.fs = t['fs']
-        if self.fs == 'wavelet':
-            pass
-        elif self.fs in ('gau', 'avgpool'):
-            k = t['fs_kernel_size']
-            w = gaussian_kernel2d(k) if self.fs == 'gau' else torch.full((k, k), 1.0 / (k * k))  # count_include_pad=True
-            self.fs_k, self.fs_w = k, w.contiguous().to(self.device)
-        else:
-            raise NotImplementedError('FS type [{:s}] not recognized.'.format(str(self.fs)))
+        self.freq = FreqSplit.srn(self.fs, t['fs_kernel_size'], self.norm, self.device)
         if self.is_train:
             self.l_pix_w = t['pixel_weight'] or 0
             if self.l_pix_w > 0 and t['pixel_criterion'] not in ('l1', 'l2'):   # nn.L1Loss / nn.MSELoss (DASR_model.py:76-82)
@@ -317,19 +295,13 @@ class DASR_Model(BaseModel):
         """self.filter_high of the reference (DASR_model.py:58,61-66: FilterHigh(kernel_size=fs_kernel_size, gaussian = fs is not 'avgpool'),
         architecture.py:1228-1243): 0.5 + 0.5 * (x - lowpass(x)), k x k depthwise filter with zero padding, on the device (dasr_lowpass).
         x: NCHW fp32 CUDA tensor -> NCHW fp32 CUDA tensor.  Used by the training-sample visuals (train.py:123-172)."""
-        from .engine import BTensor
         N, C_, H, W = x.shape
-        k = int(self.opt['train']['fs_kernel_size'] or 5)
-        key = ('fh', k, self.fs == 'avgpool')
-        if getattr(self, '_fh_w', (None,))[0] != key:
-            w = torch.full((k, k), 1.0 / (k * k)) if self.fs == 'avgpool' else gaussian_kernel2d(k)
-            self._fh_w = (key, w.contiguous().to(self.device))
         xb, hb = BTensor(N, 16, H, W, True, self.device), BTensor(N, 16, H, W, True, self.device)
         out = torch.empty((N, C_, H, W), dtype=torch.float32, device=self.device)
         L = _lib.lib()
         st = _stream()
         _lib.check(L.dasr_nchw_to_blocked(x.contiguous().data_ptr(), N, C_, H, W, xb.view(), NULL_T, st), 'nchw_to_blocked')
-        _lib.check(L.dasr_lowpass(xb.view(), NULL_T, self._fh_w[1].data_ptr(), k, N, C_, H, W, 0, 0.5, 0.5, NULL_T, hb.view(), 0, st), 'lowpass')
+        _lib.check(L.dasr_lowpass(xb.view(), NULL_T, self.freq.w.data_ptr(), self.freq.k, N, C_, H, W, 0, 0.5, 0.5, NULL_T, hb.view(), 0, st), 'lowpass')
         _lib.check(L.dasr_blocked_to_nchw(hb.view(), N, C_, H, W, out.data_ptr(), st), 'blocked_to_nchw')
         return out
 
@@ -392,8 +364,8 @@ class _StepPlan:
         self.fake_w = torch.zeros((n, 1, h, w), dtype=torch.float32, device=dev)
         self.wmap = torch.zeros((n, 1, H, W), dtype=torch.float32, device=dev)
         acc = m.acc.data_ptr()
-        wavelet = m.fs == 'wavelet'
-        Hd, Wd = (H // 2, W // 2) if wavelet else (H, W)
+        fs = m.freq
+        Hd, Wd = fs.out_size(H, W)
         fwd, gl = OpList(), OpList()
 
         # ---- forward -------------------------------------------------------------------------------------------
@@ -421,7 +393,7 @@ class _StepPlan:
         self.real_low = BTensor(n, 16, Hd, Wd, True, dev)
         self.g_low = BTensor(n, 16, Hd, Wd, True, dev)
         dx_fake = d.x.view() if d is not None else NULL_T
-        dx_real = _nview(d.x, n) if d is not None else NULL_T
+        dx_real = d.x.view(n0=n) if d is not None else NULL_T
         Ds = m.netD_source                     # source-domain discriminator on the high frequencies of [fake_s ; real_s] (DASR_model.py:250-259)
         if isinstance(Ds, DiscriminatorVGG128HIP) and (Hd, Wd) != (128, 128):
             raise ValueError('Discriminator_VGG_128 needs 128 x 128 inputs (Linear(512 * 4 * 4, 100)), got %d x %d' % (Hd, Wd))
@@ -439,22 +411,10 @@ class _StepPlan:
             self.ds_run_d.extend(ds.running_ops(1))
             self.ds_run_d.extend(ds.running_ops(0))
         sx_fake = ds.x.view() if ds is not None else NULL_T
-        sx_real = _nview(ds.x, n) if ds is not None else NULL_T
-        if wavelet:
-            for src, n0, ll, hc in ((g.sr, 0, self.fake_low.view(), sx_fake), (g.sr, n, NULL_T, dx_fake),
-                                    (self.hr_b, 0, self.real_low.view(), sx_real), (self.hr_b, n, NULL_T, dx_real)):
-                if ll.p is None and hc.p is None:
-                    continue
-                fwd.add(make_op(_lib.OP_DWT_FWD, x=_nview(src, n0), N=n, C=3, H2=Hd, W2=Wd, norm=int(m.norm), ll=ll, hc=hc))
-        else:
-            a_h, b_h = (0.25, 0.75) if m.norm else (0.5, 0.5)  # FilterHigh normalises, filter_func normalises again (App. C-11)
-            self.ab = (a_h, b_h)
-            for src, n0, lo, hi in ((g.sr, 0, self.fake_low.view(), sx_fake), (g.sr, n, NULL_T, dx_fake),
-                                    (self.hr_b, 0, self.real_low.view(), sx_real), (self.hr_b, n, NULL_T, dx_real)):
-                if lo.p is None and hi.p is None:
-                    continue
-                fwd.add(make_op(_lib.OP_LOWPASS, x=_nview(src, n0), w=m.fs_w.data_ptr(), k=m.fs_k, N=n, C=3, H=H, W=W, a_h=a_h, b_h=b_h, out_low=lo,
-                                out_high=hi))
+        sx_real = ds.x.view(n0=n) if ds is not None else NULL_T
+        for src, n0, lo, hi in ((g.sr, 0, self.fake_low.view(), sx_fake), (g.sr, n, NULL_T, dx_fake),
+                                (self.hr_b, 0, self.real_low.view(), sx_real), (self.hr_b, n, NULL_T, dx_real)):
+            fwd.add_all(fs.split(src.view(n0=n0), n, H, W, low=lo, high=hi))
         # LL loss (source half)
         if m.sup_LL:
             cnt = float(n * 3 * Hd * Wd)
@@ -475,28 +435,24 @@ class _StepPlan:
             v = self.v
             sc = [1.0 / s for s in VGG_STD] + [0.0]
             sh = [-mu / s for mu, s in zip(VGG_MEAN, VGG_STD)] + [0.0]
-            for src, dst in ((g.sr.view(), v.x.view()), (self.hr_b.view(), _nview(v.x, n))):
+            for src, dst in ((g.sr.view(), v.x.view()), (self.hr_b.view(), v.x.view(n0=n))):
                 fwd.add(make_op(_lib.OP_AFFINE4, x=src, N=n, C=3, H=H, W=W, y=dst, y_f32=v.x_flag, scale4=sc, shift4=sh))
             fwd.extend(v.fwd)
             f = v.feat
             cnt = float(n * f.C * f.H * f.W)
-            fwd.add(make_op(_lib.OP_L1DIFF, a=f.view(), b=_nview(f, n), is_f32=1 | (2 if m.l_fea_type == 'l2' else 0), N=n, C=f.C, H=f.H, W=f.W,
+            fwd.add(make_op(_lib.OP_L1DIFF, a=f.view(), b=f.view(n0=n), is_f32=1 | (2 if m.l_fea_type == 'l2' else 0), N=n, C=f.C, H=f.H, W=f.W,
                             coef=1.0 / cnt, gcoef=float(m.l_fea_w) / cnt, loss_acc=acc + 4 * A_FEA, ga=v.g_feat.view()))
         # discriminator forward on [fake_t; real_t] and the generator's GAN loss
-        if d is not None:
-            fwd.extend(d.fwd)
-            lg = d.logits
+        # (l_g_gan_source_Hf = w_src * BCE(D_s(fake_s), 1): value logged WITH the weight, DASR_model.py:258,316)
+        for D_, w_log, w_grad, slot in ((d, 1.0, m.l_gan_H_target_w, A_GAN), (ds, m.l_gan_H_source_w, m.l_gan_H_source_w, A_GAN_SRC)):
+            if D_ is None:
+                continue
+            fwd.extend(D_.fwd)
+            lg = D_.logits
             cnt = float(n * 1 * lg.H * lg.W)
             if not m.ragan:
-                fwd.add(make_op(_lib.OP_BCE, x=lg.view(), N=n, C=1, H=lg.H, W=lg.W, gan_type=m.gan_mode, target=1.0, coef=1.0 / cnt,
-                                gcoef=float(m.l_gan_H_target_w) / cnt, loss_acc=acc + 4 * A_GAN, grad=d.g_logits.view()))
-        if ds is not None:   # l_g_gan_source_Hf = w_src * BCE(D_s(fake_s), 1): value logged WITH the weight (DASR_model.py:258,316)
-            fwd.extend(ds.fwd)
-            lg = ds.logits
-            cnt = float(n * 1 * lg.H * lg.W)
-            if not m.ragan:
-                fwd.add(make_op(_lib.OP_BCE, x=lg.view(), N=n, C=1, H=lg.H, W=lg.W, gan_type=m.gan_mode, target=1.0, coef=float(m.l_gan_H_source_w) / cnt,
-                                gcoef=float(m.l_gan_H_source_w) / cnt, loss_acc=acc + 4 * A_GAN_SRC, grad=ds.g_logits.view()))
+                fwd.add(make_op(_lib.OP_BCE, x=lg.view(), N=n, C=1, H=lg.H, W=lg.W, gan_type=m.gan_mode, target=1.0, coef=float(w_log) / cnt,
+                                gcoef=float(w_grad) / cnt, loss_acc=acc + 4 * slot, grad=D_.g_logits.view()))
         # relativistic average form (`ragan`, DASR_model.py:240-244,252-256): three stages per loss, the per-pixel batch sums are all-reduced between
         # them under data parallelism (DASR_Model._run_ragan).  Weights: target w * (..)/2 enters the total times w AGAIN (w^2 on the gradient, w on
         # the logged value); source w * (..)/2 is added as is.
@@ -505,7 +461,7 @@ class _StepPlan:
         self.rs = [OpList(), OpList(), OpList()]
         self.r_bufs = []
         if m.ragan:
-            world = m.dp.world if (getattr(m, 'dp', None) is not None and m.dp.active) else 1
+            world = dp_world(m)
             for D_, slot_g, w_log, w_grad, lists_d, slots_d in (
                     (d, A_GAN, m.l_gan_H_target_w, m.l_gan_H_target_w * m.l_gan_H_target_w, self.rd, (A_DREAL, A_SREAL, A_SFAKE)),
                     (ds, A_GAN_SRC, m.l_gan_H_source_w, m.l_gan_H_source_w, self.rs, (A_DREAL_SRC, A_SREAL_SRC, A_SFAKE_SRC))):
@@ -516,8 +472,8 @@ class _StepPlan:
                 cnt = float(n * hw)
                 sums, part = torch.zeros(2 * hw, dtype=torch.float32, device=dev), torch.zeros(2 * hw, dtype=torch.float32, device=dev)
                 self.r_bufs.append((sums, part))
-                fake, real = lg.view(), _nview(lg, n)
-                g_fake, g_real = D_.g_logits.view(), _nview(D_.g_logits, n)
+                fake, real = lg.view(), lg.view(n0=n)
+                g_fake, g_real = D_.g_logits.view(), D_.g_logits.view(n0=n)
                 # generator: a = fake (target 1, gradient), b = real (target 0, detached)
                 _ragan_ops(self.rg, fake, real, n, lg.H, lg.W, n * world, 1.0, 0.0, 0.5 * float(w_log) / cnt, 0.5 * float(w_grad) / cnt, sums, part,
                            acc + 4 * slot_g, None, None, 0.0, g_fake, None, form=(0, 2, 3)[m.gan_mode])
@@ -543,40 +499,26 @@ class _StepPlan:
         g_hi_t = d.gx.view() if d is not None else NULL_T
         g_hi_s = ds.gx.view() if ds is not None else NULL_T
         g_lo_s = self.g_low.view() if m.sup_LL else NULL_T
-        if wavelet:
-            for n0, gll, ghc in ((0, g_lo_s, g_hi_s), (n, NULL_T, g_hi_t)):
-                if gll.p is None and ghc.p is None:
-                    continue
-                gl.add(make_op(_lib.OP_DWT_BWD, gll=gll, ghc=ghc, N=n, C=3, H2=Hd, W2=Wd, norm=int(m.norm), gx=_nview(g.g_sr, n0), accumulate=1))
-        else:
-            for n0, glo, ghi in ((0, g_lo_s, g_hi_s), (n, NULL_T, g_hi_t)):
-                if glo.p is None and ghi.p is None:
-                    continue
-                gl.add(make_op(_lib.OP_LOWPASS, x=glo, x2=ghi, w=m.fs_w.data_ptr(), k=m.fs_k, N=n, C=3, H=H, W=W, mode=1, a_h=self.ab[0],
-                               out_low=_nview(g.g_sr, n0), accumulate=1))
+        for n0, glo, ghi in ((0, g_lo_s, g_hi_s), (n, NULL_T, g_hi_t)):
+            gl.add_all(fs.adjoint(g.g_sr.view(n0=n0), n, H, W, g_low=glo, g_high=ghi))
         self.g_loss_bwd = gl
 
         # ---- discriminator step: BCE(real, 1), BCE(fake, 0), backward with weight gradients -----------------------------------
-        dstep = OpList()
-        if d is not None:
-            lg = d.logits
-            cnt = float(n * lg.H * lg.W)
-            for n0, target, a_loss, a_score in (() if m.ragan else ((n, 1.0, A_DREAL, A_SREAL), (0, 0.0, A_DFAKE, A_SFAKE))):
-                dstep.add(make_op(_lib.OP_BCE, x=_nview(lg, n0), N=n, C=1, H=lg.H, W=lg.W, gan_type=m.gan_mode, target=target, coef=0.5 / cnt,
-                                  gcoef=0.5 / cnt, loss_acc=acc + 4 * a_loss, score_acc=acc + 4 * a_score, score_coef=1.0 / cnt, grad=_nview(d.g_logits, n0)))
-            dstep.extend(d.bwd_full)
-        self.d_step = dstep
-        # ---- source-domain discriminator step (DASR_model.py:287-303): the same on [fake_s ; real_s] ------------------------------------
-        sstep = OpList()
-        if self.ds is not None:
-            lg = self.ds.logits
-            cnt = float(n * lg.H * lg.W)
-            for n0, target, a_loss, a_score in (() if m.ragan else ((n, 1.0, A_DREAL_SRC, A_SREAL_SRC), (0, 0.0, A_DFAKE_SRC, A_SFAKE_SRC))):
-                sstep.add(make_op(_lib.OP_BCE, x=_nview(lg, n0), N=n, C=1, H=lg.H, W=lg.W, gan_type=m.gan_mode, target=target, coef=0.5 / cnt,
-                                  gcoef=0.5 / cnt, loss_acc=acc + 4 * a_loss, score_acc=acc + 4 * a_score, score_coef=1.0 / cnt,
-                                  grad=_nview(self.ds.g_logits, n0)))
-            sstep.extend(self.ds.bwd_full)
-        self.ds_step = sstep
+        def d_step(D_, real_slots, fake_slots):
+            step = OpList()
+            if D_ is not None:
+                lg = D_.logits
+                cnt = float(n * lg.H * lg.W)
+                for n0, target, (a_loss, a_score) in (() if m.ragan else ((n, 1.0, real_slots), (0, 0.0, fake_slots))):
+                    step.add(make_op(_lib.OP_BCE, x=lg.view(n0=n0), N=n, C=1, H=lg.H, W=lg.W, gan_type=m.gan_mode, target=target, coef=0.5 / cnt,
+                                     gcoef=0.5 / cnt, loss_acc=acc + 4 * a_loss, score_acc=acc + 4 * a_score, score_coef=1.0 / cnt,
+                                     grad=D_.g_logits.view(n0=n0)))
+                step.extend(D_.bwd_full)
+            return step
+
+        self.d_step = d_step(d, (A_DREAL, A_SREAL), (A_DFAKE, A_SFAKE))
+        # source-domain discriminator step (DASR_model.py:287-303): the same on [fake_s ; real_s]
+        self.ds_step = d_step(ds, (A_DREAL_SRC, A_SREAL_SRC), (A_DFAKE_SRC, A_SFAKE_SRC))
 
     def set_d_grad_scale(self, scale):
         """(the BatchNorm backward ops of these lists come from bwd_full: every one writes dgamma / dbeta and takes the scale)"""

@@ -18,7 +18,6 @@ power of two; the 16 data-gradient convs then are ONE f16 pass of the LDS-DMA de
 register-staged one) and the 16 weight gradients run on the 12-wave LDS-DMA kernel.  The rounding of a gradient to 11 bits enters the
 weight gradients like noise (nothing downstream is decided by it -- the PReLU masks come from the forward activations).
 """
-import ctypes as C
 import logging
 import os
 from collections import OrderedDict
@@ -27,11 +26,12 @@ import torch
 
 from . import _lib
 from ._lib import make_op
-from .engine import (BTensor, ParamStore, PackRegistry, OpList, WgradGroup, WgradGroup3, Workspace, conv_op, ceil_div, Tensor,
-                     ensure_runtime_ready, _stream, patch, set_reduce_scale)
-from .gan_nets import NLayerDiscriminatorHIP, BatchNormDiscriminatorHIP, VGGFeatureHIP, VGG16_CFG, fsd_spec, dsn_nld_spec, fold_batchnorm_fsd
+from .engine import (BTensor, ParamStore, PackRegistry, OpList, WgradGroup, WgradGroup3, Workspace, conv_op, ceil_div, ensure_runtime_ready, _stream,
+                     patch, set_reduce_scale, dp_world)
+from .gan_nets import (NLayerDiscriminatorHIP, BatchNormDiscriminatorHIP, VGGFeatureHIP, FreqSplit, VGG16_CFG, fsd_spec, dsn_nld_spec, fold_batchnorm_fsd,
+                       gaussian_kernel2d)
 from .models import AdamHIP
-from .dasr_model import gaussian_kernel2d, vgg_random_state_dict, _nview, _ragan_ops
+from .dasr_model import vgg_random_state_dict, _ragan_ops
 
 logger = logging.getLogger('base')
 EPS = 1e-8
@@ -470,10 +470,10 @@ class DSNModel:
         # gradient penalty sees D(sample) alone.  So the combination is the --wgan plan with the discriminator's Wasserstein gradients doubled and the
         # logged terms recombined (get_current_log); `rel` = the three-stage sigmoid form of --ragan alone
         self.rel = self.ragan and not self.wgan
-        self.filter = o['filter'].lower()
-        if self.filter not in ('gau', 'avg_pool', 'wavelet'):
-            raise NotImplementedError('Frequency Separation type [{:s}] not recognized'.format(o['filter']))
-        self.k = o['kernel_size']
+        # frequency separation: --filter, --kernel_size and the wavelet bands of the discriminator input, --cat_or_sum: 'cat' (9 channels) or
+        # 'sum' = (LH + HL + HH) / 3 (model.py:108-118)
+        self.filter, self.k, self.cs = o['filter'].lower(), o['kernel_size'], str(o['cat_or_sum']).lower()
+        self.freq = FreqSplit.dsn(self.filter, self.k, self.cs, self.device)
         if o['generator'].lower() not in ('deresnet', 'dsgan'):   # codes/DSN/train.py:124-129
             raise NotImplementedError('Generator model [{:s}] not recognized'.format(o['generator']))
         self.netG = DeResnetHIP(o['n_res_blocks'], device=self.device, scale=4 if o['generator'].lower() == 'deresnet' else 1)
@@ -481,11 +481,7 @@ class DSNModel:
         # generator-loss evaluation in the reference's order; only PerceptualLoss (= per_type LPIPS) has it, the VGG16 term ignores the flag
         self.lpips_rot_flip = bool(o['lpips_rot_flip']) and o['per_type'] == 'LPIPS' and o['w_per'] > 0
         self.netG.loss_weight = max(float(o['w_col']), float(o['w_tex']), float(o['w_per']))   # sizes the f16 pre-scale of the 16-bit backward (_GPlan.gscale)
-        self.cs = str(o['cat_or_sum']).lower()   # wavelet bands of the discriminator input: 'cat' (9 channels) or 'sum' = (LH + HL + HH) / 3 (model.py:108-118)
-        if self.cs not in ('cat', 'sum'):
-            raise NotImplementedError('Wavelet format [{:s}] not recognized'.format(str(o['cat_or_sum'])))
-        self.dwt_norm = 1 | (2 if self.cs == 'sum' else 0)   # dasr_dwt_fwd / _bwd `norm` flags of the discriminator front end
-        nc = 9 if (self.filter == 'wavelet' and self.cs == 'cat') else 3
+        nc = self.freq.in_nc
         gk = self.k if self.filter == 'gau' else None
         self.netD_eval = None
         if self.d_arch == 'fsd':
@@ -505,9 +501,6 @@ class DSNModel:
         else:
             self.netD = NLayerDiscriminatorHIP(nc, device=self.device, spec_layers=spec_layers)
             self.netD.load_state_dict(default_init_state(self.netD.spec))
-        if self.filter != 'wavelet':
-            w = gaussian_kernel2d(self.k) if self.filter == 'gau' else torch.full((self.k, self.k), 1.0 / (self.k * self.k))
-            self.fw = w.contiguous().to(self.device)
         self.opt_g = AdamHIP(self.netG.params, o['learning_rate'], (o['adam_beta_1'], 0.999), 0.0)
         self.opt_d = AdamHIP(self.netD.params, o['learning_rate'], (o['adam_beta_1'], 0.999), 0.0)
         self.epoch, self.iteration_count = 0, 0
@@ -532,8 +525,7 @@ class DSNModel:
 
     def _plan(self, N, H, W):
         # the relativistic ops bake the data-parallel world size into their batch-mean divisor: a plan is valid for ONE world size
-        world = self.dp.world if (self.dp is not None and self.dp.active) else 1
-        k = (N, H, W, world if (self.rel or self.wgan) else 0)
+        k = (N, H, W, dp_world(self) if (self.rel or self.wgan) else 0)
         if k not in self._plans:
             self._plans[k] = _DSNPlan(self, N, H, W)
         return self._plans[k]
@@ -683,7 +675,7 @@ class DSNModel:
         if self.filter == 'wavelet':   # DWTForward(J=1, 'haar', mode='reflect'): an odd side is extended by one mirrored sample; LL * 0.5 = 2x2 mean
             x = F.pad(x, (0, x.shape[3] % 2, 0, x.shape[2] % 2), mode='reflect')
             return F.avg_pool2d(x, 2)
-        return F.conv2d(x, self.fw.view(1, 1, self.k, self.k).expand(3, 1, self.k, self.k), groups=3)
+        return F.conv2d(x, self.freq.w.view(1, 1, self.k, self.k).expand(3, 1, self.k, self.k), groups=3)
 
     def perceptual_distance(self, x, y):
         """g_loss_module.perceptual_loss(x, y) without gradient: LPIPS(alex)(x, y, normalize=True).mean() or MSE of the VGG16 features (loss.py:108-130)
@@ -742,7 +734,7 @@ class DSNModel:
         import torch.nn.functional as F
         k, p = self.k, (self.k - 1) // 2
         if self.filter == 'gau':
-            return F.conv2d(x, self.fw.view(1, 1, k, k).expand(3, 1, k, k), padding=p, groups=3)
+            return F.conv2d(x, self.freq.w.view(1, 1, k, k).expand(3, 1, k, k), padding=p, groups=3)
         return F.avg_pool2d(x, k, stride=1, padding=p, count_include_pad=False)
 
     def filter_high(self, x):
@@ -809,9 +801,6 @@ class _GradPenaltyPlan:
         nl = len(net.layers)
         nc = net.layers[0]['cin']
         P, pack = net.params, net.pack
-        wav = m.filter == 'wavelet'
-        k = m.k
-        norm_valid = 2 if m.filter == 'avg_pool' else 0
         B = lambda t: BTensor(N, t.C, t.H, t.W, True, dev)
         self.g_img, self.t0 = BTensor(N, 16, h, w, True, dev), BTensor(N, 16, hd, wd, True, dev)
         self.part, self.out3 = torch.zeros(256, dtype=torch.float32, device=dev), torch.zeros(4, dtype=torch.float32, device=dev)
@@ -821,7 +810,7 @@ class _GradPenaltyPlan:
         ops = OpList()
         # ---- sample (already behind the linear front end: F(r real + (1 - r) fake) = r F(real) + (1 - r) F(fake), the + 0.5 of the normalisation included)
         self.mix_op = len(ops.ops)   # a = r (real half), b = 1 - r (fake half): set_mix()
-        ops.add(make_op(_lib.OP_AXPBY, x=_nview(d.x, N), a=0.5, z=d.x.view(), b=0.5, N=N, C=nc, H=hd, W=wd, out_f32=dg.x.view(), gamma=1.0))
+        ops.add(make_op(_lib.OP_AXPBY, x=d.x.view(n0=N), a=0.5, z=d.x.view(), b=0.5, N=N, C=nc, H=hd, W=wd, out_f32=dg.x.view(), gamma=1.0))
         ops.extend(dg.fwd)
         if m.bn:
             ops.extend(dg.running_ops(0))
@@ -831,25 +820,17 @@ class _GradPenaltyPlan:
         ops.add(make_op(_lib.OP_FILL_SCALED, x=dg.g_logits.view(), N=N, C=1, H=lg.H, W=lg.W, scalar=self.one.data_ptr(), factor=1.0 / cnt))
         ops.extend(dg.bwd_data_ops(N))                # -> dg.gx = d mean D / d (front-end output)
         ops.add(make_op(_lib.OP_FILL, p=self.g_img.t.data_ptr(), n=self.g_img.t.numel(), value=0.0))
-        if wav:                                       # adjoint of the front end -> g = d mean D / d sample (image space)
-            ops.add(make_op(_lib.OP_DWT_BWD, ghc=dg.gx.view(), N=N, C=3, H2=hd, W2=wd, norm=m.dwt_norm, gx=self.g_img.view(), accumulate=1))
-        else:
-            ops.add(make_op(_lib.OP_LOWPASS, x2=dg.gx.view(), w=m.fw.data_ptr(), k=k, N=N, C=3, H=h, W=w, mode=1 | norm_valid, accumulate=1, a_h=0.5,
-                            out_low=self.g_img.view()))
+        ops.add_all(m.freq.adjoint(self.g_img.view(), N, h, w, g_high=dg.gx.view()))   # adjoint of the front end -> g = d mean D / d sample (image space)
         # out3 = {||g||, 10 (||g|| - 1)^2, 20 (||g|| - 1) / ||g||}; acc[slot] += the penalty.  Data parallel: two stages around the all-reduce of the ranks'
         # sums of squares (dasr_grad_penalty; DSNModel.iteration runs ops[:cut], all-reduces out3[3], runs ops[cut:])
-        self.world = m.dp.world if (getattr(m, 'dp', None) is not None and m.dp.active) else 1
+        self.world = dp_world(m)
         for stage in ((0,) if self.world == 1 else (1, 2)):
             ops.add(make_op(_lib.OP_GRAD_PENALTY, g=self.g_img.view(), N=N, C=3, H=h, W=w, weight=10.0, part256=self.part.data_ptr(), out3=self.out3.data_ptr(),
                             loss_acc=m.acc.data_ptr() + 4 * acc_slot, stage=stage, world=self.world))
             if stage == 1:
                 self.cut = len(ops.ops)
         # ---- tangent pass along u = g: t0 = (linear part of the front end)(g)
-        if wav:
-            ops.add(make_op(_lib.OP_DWT_FWD, x=self.g_img.view(), N=N, C=3, H2=hd, W2=wd, norm=m.dwt_norm | 4, hc=self.t0.view()))
-        else:
-            ops.add(make_op(_lib.OP_LOWPASS, x=self.g_img.view(), w=m.fw.data_ptr(), k=k, N=N, C=3, H=h, W=w, mode=0 | norm_valid, a_h=0.5,
-                            out_high=self.t0.view()))
+        ops.add_all(m.freq.tangent(self.g_img.view(), N, h, w, self.t0.view()))
         keep = []
         adot, zdot = [None] * nl, [None] * nl        # tangents of the layer outputs (after norm + lrelu) / of the conv outputs in front of a norm
         src = self.t0
@@ -859,12 +840,7 @@ class _GradPenaltyPlan:
                 zdot[i] = B(dg.zs[i])
                 adot[i] = B(dg.acts[i])
                 ops.add(conv_op(pack, L['fwd'], src.view(), True, L['cin_pad'], hi, wi, ho, wo, N, kh=L['kh'], stride=L['stride'], pad=L['pad'], out_f32=zdot[i].view()))
-                if L['norm'] == 'batch':
-                    ops.add(make_op(_lib.OP_BNORM_JVP, x=dg.zs[i].view(), t=zdot[i].view(), N=N, C=L['cout'], H=ho, W=wo, group=dg.group, slope=D_SLOPE,
-                                    gamma=P.ptr(L['bn'] + 'weight'), beta=P.ptr(L['bn'] + 'bias'), stats=dg.stats[i].data_ptr(), out=adot[i].view()))
-                else:
-                    ops.add(make_op(_lib.OP_INORM_JVP, a=dg.acts[i].view(), t=zdot[i].view(), N=N, C=L['cout'], H=ho, W=wo, slope=D_SLOPE,
-                                    stats=dg.stats[i].data_ptr(), out=adot[i].view()))
+                ops.add(dg.norm_op(i, 'jvp', N, t=zdot[i].view(), out=adot[i].view()))
             else:   # conv + lrelu: adot = lrelu'(a) * conv(tangent) (the mask multiplies the conv output in the epilogue; no bias on a tangent)
                 adot[i] = B(dg.acts[i])
                 ops.add(conv_op(pack, L['fwd'], src.view(), True, L['cin_pad'], hi, wi, ho, wo, N, kh=L['kh'], stride=L['stride'], pad=L['pad'],
@@ -894,32 +870,21 @@ class _GradPenaltyPlan:
             L = net.layers[i]
             inp_a = dg.x if i == 0 else dg.acts[i - 1]
             inp_adot = self.t0 if i == 0 else adot[i - 1]
-            if L['norm'] == 'batch':
-                # BatchNorm: the first-order backward on both adjoints (the primal one also gives d pen / d gamma, d beta of a = lrelu(gamma xhat + beta)), then the
-                # dependence of J on z and the tangent output's own factor gamma (dasr_bnorm_second; += on top of the primal terms when there are any)
+            if L['norm']:
+                # the first-order backward of the norm on both adjoints: J (lrelu'(a) ga).  BatchNorm: the primal one also gives d pen / d gamma, d beta of
+                # a = lrelu(gamma xhat + beta)
                 g_zdot, g_z = B(dg.zs[i]), B(dg.zs[i])
-                (ho, wo) = dg.dims[i + 1]
-                gdst = (self.grad.data_ptr() + 4 * P.off(L['bn'] + 'weight'), self.grad.data_ptr() + 4 * P.off(L['bn'] + 'bias'))
+                gdst = (None, None)
+                if L['norm'] == 'batch':
+                    gdst = (self.grad.data_ptr() + 4 * P.off(L['bn'] + 'weight'), self.grad.data_ptr() + 4 * P.off(L['bn'] + 'bias'))
                 for ga_, out_, prim in ((g_adot, g_zdot, False),) + (((g_a, g_z, True),) if g_a is not None else ()):
-                    ops.add(make_op(_lib.OP_BNORM_BWD, x=dg.zs[i].view(), ga=ga_.view(), N=N, C=L['cout'], H=ho, W=wo, group=dg.group, slope=D_SLOPE,
-                                    gamma=P.ptr(L['bn'] + 'weight'), beta=P.ptr(L['bn'] + 'bias'), stats=dg.stats[i].data_ptr(), gx=out_.view(),
-                                    dgamma=gdst[0] if prim else None, dbeta=gdst[1] if prim else None, pscale=1.0))
-                ops.add(make_op(_lib.OP_BNORM_SECOND, x=dg.zs[i].view(), t=zdot[i].view(), ga=g_adot.view(), N=N, C=L['cout'], H=ho, W=wo, group=dg.group,
-                                slope=D_SLOPE, gamma=P.ptr(L['bn'] + 'weight'), beta=P.ptr(L['bn'] + 'bias'), stats=dg.stats[i].data_ptr(), out=g_z.view(),
-                                accumulate=1 if g_a is not None else 0, dgamma=gdst[0], pscale=1.0))
-                mask = None
-            elif L['norm']:
-                g_zdot, g_z = B(dg.zs[i]), B(dg.zs[i])
-                for ga_, out_ in ((g_adot, g_zdot),) + (((g_a, g_z),) if g_a is not None else ()):   # J (lrelu'(a) ga): the first-order InstanceNorm backward on both adjoints
-                    ops.add(make_op(_lib.OP_INORM_BWD, a=dg.acts[i].view(), ga=ga_.view(), N=N, C=L['cout'], H=dg.dims[i + 1][0], W=dg.dims[i + 1][1],
-                                    slope=D_SLOPE, stats=dg.stats[i].data_ptr(), gx=out_.view()))
-                # + the dependence of J on z: tangent zdot, upstream lrelu'(a) * g_adot
-                ops.add(make_op(_lib.OP_INORM_SECOND, a=dg.acts[i].view(), t=zdot[i].view(), ga=g_adot.view(), N=N, C=L['cout'], H=dg.dims[i + 1][0],
-                                W=dg.dims[i + 1][1], slope=D_SLOPE, stats=dg.stats[i].data_ptr(), out=g_z.view(), accumulate=1 if g_a is not None else 0))
-                mask = None
+                    ops.add(dg.norm_op(i, 'bwd', N, ga=ga_.view(), gx=out_.view(), dgamma=gdst[0] if prim else None, dbeta=gdst[1] if prim else None))
+                # + the dependence of J on z: tangent zdot, upstream lrelu'(a) * g_adot; BatchNorm: and the tangent output's own factor gamma
+                # (dasr_inorm_second / dasr_bnorm_second; += on top of the primal terms when there are any)
+                ops.add(dg.norm_op(i, 'second', N, t=zdot[i].view(), ga=g_adot.view(), out=g_z.view(), accumulate=1 if g_a is not None else 0,
+                                   dgamma=gdst[0]))
             else:   # conv + lrelu: the adjoints pass through lrelu'(a) (applied as the mask of the data-gradient convs of the layer ABOVE, see below)
                 g_zdot, g_z = g_adot, g_a
-                mask = None
             wgrad(i, [(g_z, inp_a), (g_zdot, inp_adot)] if g_z is not None else [(g_zdot, inp_adot)], bias=g_z is not None)
             if i > 0:
                 below = net.layers[i - 1]
@@ -947,15 +912,14 @@ class _DSNPlan:
         # De_resnet maps the HR crop to LR size; the DSGAN Generator maps the bicubic LR image to an LR image (codes/DSN/train.py:213-217)
         self.g = m.netG.plan(N, H, W) if m.netG.scale == 4 else m.netG.plan(N, h, w)
         g = self.g
-        wav = m.filter == 'wavelet'
-        hd, wd = (h // 2, w // 2) if wav else (h, w)
+        fs = m.freq
+        hd, wd = fs.out_size(h, w)
         self.d = m.netD.plan(2 * N, hd, wd)   # [fake; real]
         d = self.d
         self.bic_nchw = torch.zeros((N, 3, h, w), dtype=torch.float32, device=dev)
         self.real_nchw = torch.zeros((N, 3, h, w), dtype=torch.float32, device=dev)
         self.bic_b, self.real_b = BTensor(N, 16, h, w, True, dev), BTensor(N, 16, h, w, True, dev)
-        k = m.k
-        hc, wc = (hd, wd) if wav else (h - k + 1, w - k + 1)
+        hc, wc = fs.colour_size(h, w)
         self.col_f, self.col_b, self.g_col = (BTensor(N, 16, hc, wc, True, dev) for _ in range(3))
         acc = m.acc.data_ptr()
         o_ = m.opt
@@ -965,13 +929,8 @@ class _DSNPlan:
         for src, dst in ((self.bic_nchw, self.bic_b), (self.real_nchw, self.real_b)):
             f.add(make_op(_lib.OP_NCHW2B, src=src.data_ptr(), N=N, C=3, H=h, W=w, dst_f32=dst.view()))
         # discriminator front end on fake -> d.x[:N], real -> d.x[N:]
-        norm_valid = 2 if m.filter == 'avg_pool' else 0
         for src, n0 in ((g.fake, 0), (self.real_b, N)):
-            if wav:
-                f.add(make_op(_lib.OP_DWT_FWD, x=src.view(), N=N, C=3, H2=hd, W2=wd, norm=m.dwt_norm, hc=_nview(d.x, n0)))
-            else:
-                f.add(make_op(_lib.OP_LOWPASS, x=src.view(), w=m.fw.data_ptr(), k=k, N=N, C=3, H=h, W=w, mode=0 | norm_valid, a_h=0.5, b_h=0.5,
-                              out_high=_nview(d.x, n0)))
+            f.add_all(fs.split(src.view(), N, h, w, high=d.x.view(n0=n0)))
         f.extend(d.fwd)
         # BatchNorm discriminator: the reference calls D(real) then D(fake) (with --ragan: net(real), net(fake), net(fake), net(real)); every call
         # in training mode moves the running statistics once, with that call's batch statistics (group 0 = fake half, 1 = real half)
@@ -990,10 +949,9 @@ class _DSNPlan:
             rl = [OpList(), OpList(), OpList()]
             # data parallel: the batch means are means over the GLOBAL batch (n_glob = N * world); iteration() all-reduces the per-pixel sums
             # between the stages, as the SRN trainer does (dasr_model.py::_run_ragan), so the lists are cut at the stage boundaries
-            world = m.dp.world if (getattr(m, 'dp', None) is not None and m.dp.active) else 1
-            self.ragan_world = world
-            _ragan_ops(rl, _nview(lg, N), lg.view(), N, lg.H, lg.W, N * world, 1.0, 0.0, 1.0 / cnt, 1.0 / cnt, self.r_sums, self.r_part, acc, acc + 4 * 4,
-                       acc + 4 * 5, 1.0 / cnt, _nview(d.g_logits, N), d.g_logits.view(), form=1, eps=EPS)
+            self.ragan_world = dp_world(m)
+            _ragan_ops(rl, lg.view(n0=N), lg.view(), N, lg.H, lg.W, N * self.ragan_world, 1.0, 0.0, 1.0 / cnt, 1.0 / cnt, self.r_sums, self.r_part, acc, acc + 4 * 4,
+                       acc + 4 * 5, 1.0 / cnt, d.g_logits.view(n0=N), d.g_logits.view(), form=1, eps=EPS)
             self.ragan_cuts_fwd = []
             for l_ in rl:
                 f.extend(l_)
@@ -1001,18 +959,15 @@ class _DSNPlan:
         # discriminator loss: -log(real) - log(1 - fake)   (acc[0], acc[1]); scores acc[4] (real), acc[5] (fake)
         for n0, target, a_loss, a_score in (((N, 1.0, 0, 4), (0, 0.0, 1, 5)) if m.wgan else ()):   # --wgan: -mean(real) + mean(fake) on the raw map (loss.py:33-36)
             # (--ragan: both relativistic terms carry every logit once)
-            f.add(make_op(_lib.OP_BCE, x=_nview(lg, n0), N=N, C=1, H=lg.H, W=lg.W, gan_type=2, target=target, coef=1.0 / cnt,
+            f.add(make_op(_lib.OP_BCE, x=lg.view(n0=n0), N=N, C=1, H=lg.H, W=lg.W, gan_type=2, target=target, coef=1.0 / cnt,
                           gcoef=(2.0 if m.ragan else 1.0) / cnt, loss_acc=acc + 4 * a_loss, score_acc=acc + 4 * a_score, score_coef=1.0 / cnt,
-                          grad=_nview(d.g_logits, n0)))
+                          grad=d.g_logits.view(n0=n0)))
         for n0, mode, a_loss, a_score in (() if (m.rel or m.wgan) else ((N, 0, 0, 4), (0, 1, 1, 5))):
-            f.add(make_op(_lib.OP_LOGLOSS, x=_nview(lg, n0), N=N, H=lg.H, W=lg.W, mode=mode, eps=EPS, coef=1.0 / cnt, gcoef=1.0 / cnt, score_coef=1.0 / cnt,
-                          loss_acc=acc + 4 * a_loss, score_acc=acc + 4 * a_score, grad=_nview(d.g_logits, n0)))
+            f.add(make_op(_lib.OP_LOGLOSS, x=lg.view(n0=n0), N=N, H=lg.H, W=lg.W, mode=mode, eps=EPS, coef=1.0 / cnt, gcoef=1.0 / cnt, score_coef=1.0 / cnt,
+                          loss_acc=acc + 4 * a_loss, score_acc=acc + 4 * a_score, grad=d.g_logits.view(n0=n0)))
         # colour loss: L1 between the low-pass of fake and of the bicubic LR (acc[3])
         for src, dst in ((g.fake, self.col_f), (self.bic_b, self.col_b)):
-            if wav:
-                f.add(make_op(_lib.OP_DWT_FWD, x=src.view(), N=N, C=3, H2=hd, W2=wd, norm=1, ll=dst.view()))
-            else:
-                f.add(make_op(_lib.OP_LOWPASS_VALID, x=src.view(), w=m.fw.data_ptr(), k=k, N=N, C=3, H=h, W=w, out=dst.view()))
+            f.add_all(fs.colour(src.view(), N, h, w, dst.view()))
         ccnt = float(N * 3 * hc * wc)
         f.add(make_op(_lib.OP_L1DIFF, a=self.col_f.view(), b=self.col_b.view(), is_f32=1, N=N, C=3, H=hc, W=wc, coef=1.0 / ccnt,
                       gcoef=float(o_['w_col']) / ccnt, loss_acc=acc + 4 * 3, ga=self.g_col.view()))
@@ -1034,7 +989,7 @@ class _DSNPlan:
             f.extend(v.fwd)
             ft = v.feat
             fcnt = float(N * ft.C * ft.H * ft.W)
-            f.add(make_op(_lib.OP_L1DIFF, a=ft.view(), b=_nview(ft, N), is_f32=1 | 2, N=N, C=ft.C, H=ft.H, W=ft.W, coef=1.0 / fcnt,
+            f.add(make_op(_lib.OP_L1DIFF, a=ft.view(), b=ft.view(n0=N), is_f32=1 | 2, N=N, C=ft.C, H=ft.H, W=ft.W, coef=1.0 / fcnt,
                           gcoef=float(o_['w_per']) / fcnt, loss_acc=acc + 4 * 6, ga=v.g_feat.view()))
         self.fwd = f
         # D weight gradients from the pre-update graph
@@ -1044,7 +999,7 @@ class _DSNPlan:
         gb = OpList()
         if m.rel:   # -log(sigmoid(fake - mean_n(real)) + eps): stage 0's sums are still valid, the real term is absent (t < 0), real carries no gradient
             rl = [OpList(), OpList(), OpList()]
-            _ragan_ops(rl, _nview(lg, N), lg.view(), N, lg.H, lg.W, N * self.ragan_world, -1.0, 1.0, 1.0 / cnt, float(o_['w_tex']) / cnt, self.r_sums, self.r_part,
+            _ragan_ops(rl, lg.view(n0=N), lg.view(), N, lg.H, lg.W, N * self.ragan_world, -1.0, 1.0, 1.0 / cnt, float(o_['w_tex']) / cnt, self.r_sums, self.r_part,
                        acc + 4 * 2, None, None, 0.0, None, d.g_logits.view(), form=1, eps=EPS, stages=(1, 2))
             gb.extend(rl[1])
             self.ragan_cut_gbwd = len(gb.ops)
@@ -1057,14 +1012,7 @@ class _DSNPlan:
                            grad=d.g_logits.view()))
         gb.extend(d.bwd_data_ops(N))
         gb.add(make_op(_lib.OP_FILL, p=g.g_fake.t.data_ptr(), n=g.g_fake.t.numel(), value=0.0))
-        if wav:
-            gb.add(make_op(_lib.OP_DWT_BWD, gll=self.g_col.view(), ghc=d.gx.view(), N=N, C=3, H2=hd, W2=wd, norm=m.dwt_norm, gx=g.g_fake.view(),
-                           accumulate=1))
-        else:   # adjoint of the high-pass front end
-            gb.add(make_op(_lib.OP_LOWPASS, x2=d.gx.view(), w=m.fw.data_ptr(), k=k, N=N, C=3, H=h, W=w, mode=1 | norm_valid, accumulate=1, a_h=0.5,
-                           out_low=g.g_fake.view()))
-            gb.add(make_op(_lib.OP_LOWPASS_VALID, x=self.g_col.view(), w=m.fw.data_ptr(), k=k, N=N, C=3, H=h, W=w, mode=1, out=g.g_fake.view(),
-                           accumulate=1))
+        gb.add_all(fs.adjoint(g.g_fake.view(), N, h, w, g_high=d.gx.view(), g_colour=self.g_col.view()))   # adjoint of the high-pass front end and of the colour filter
         if lpips:
             gb.extend(self.v.bwd)
             self.sym_ops.append((gb, len(gb.ops), 1))
@@ -1111,9 +1059,8 @@ class _InferPlan:
         dev = m.device
         # De_resnet maps the image to 1/4 size; the DSGAN Generator keeps the size (create_dataset_modified.py:99-103 applies either to the image as is)
         h, w = (H // 4, W // 4) if (with_g and m.netG.scale == 4) else (H, W)
-        wav = m.filter == 'wavelet'
-        assert not wav or (h % 2 == 0 and w % 2 == 0), 'wavelet front end: even image size (ddm_of crops; translate expects it)'
-        hd, wd = (h // 2, w // 2) if wav else (h, w)
+        assert not m.freq.wavelet or (h % 2 == 0 and w % 2 == 0), 'wavelet front end: even image size (ddm_of crops; translate expects it)'
+        hd, wd = m.freq.out_size(h, w)
         self.d = m.inference_discriminator().plan(N, hd, wd)
         d = self.d
         nh, nw = d.logits.H, d.logits.W          # FSD keeps the map size; the nld discriminators shrink it
@@ -1129,11 +1076,7 @@ class _InferPlan:
             src = BTensor(N, 16, h, w, True, dev)
             ops.add(make_op(_lib.OP_NCHW2B, src=self.lr_nchw.data_ptr(), N=N, C=3, H=h, W=w, dst_f32=src.view()))
             self.src = src
-        if wav:
-            ops.add(make_op(_lib.OP_DWT_FWD, x=src.view(), N=N, C=3, H2=hd, W2=wd, norm=m.dwt_norm, hc=d.x.view()))
-        else:
-            ops.add(make_op(_lib.OP_LOWPASS, x=src.view(), w=m.fw.data_ptr(), k=m.k, N=N, C=3, H=h, W=w, mode=0 | (2 if m.filter == 'avg_pool' else 0),
-                            a_h=0.5, b_h=0.5, out_high=d.x.view()))
+        ops.add_all(m.freq.split(src.view(), N, h, w, high=d.x.view()))
         ops.extend(d.fwd)
         if m.wgan:   # --wgan (model.py:104-105): the discriminator map is the raw logit map
             ops.add(make_op(_lib.OP_AXPBY, x=d.logits.view(), a=1.0, N=N, C=1, H=nh, W=nw, out_f32=self.dout.view(), gamma=1.0))

@@ -28,6 +28,12 @@ def ceil_div(a, b):
     return (a + b - 1) // b
 
 
+def dp_world(m):
+    """number of data-parallel ranks a model's plans are recorded for (1 without an active process group)"""
+    dp = getattr(m, 'dp', None)
+    return dp.world if (dp is not None and dp.active) else 1
+
+
 # --------------------------------------------------------------------------------------------------
 class BTensor:
     """Blocked activation tensor T[n][cb][y][x][16] (bf16 or f32) living in a torch CUDA tensor."""
@@ -48,11 +54,12 @@ class BTensor:
         b.planes, b.t, b.esz = t.shape[1], t, 4 if f32 else 2
         return b
 
-    def view(self, c0=0):
-        """dasr_tensor starting at channel c0 (multiple of 16)."""
+    def view(self, c0=0, n0=0):
+        """dasr_tensor starting at channel c0 (multiple of 16) and image n0: images [n0:] of the tensor, strides unchanged."""
         assert c0 % 16 == 0 and c0 // 16 < self.planes, (c0, self.planes)
+        assert 0 <= n0 < self.N, (n0, self.N)
         cbs = self.H * self.W * 16
-        return Tensor(self.t.data_ptr() + (c0 // 16) * cbs * self.esz, self.planes * cbs, cbs)
+        return Tensor(self.t.data_ptr() + ((c0 // 16) * cbs + n0 * self.planes * cbs) * self.esz, self.planes * cbs, cbs)
 
     def nchw(self, C_=None):
         """Debug/IO helper: gather to a torch NCHW float tensor (torch indexing only, no arithmetic)."""
@@ -228,6 +235,11 @@ class OpList:
     def add(self, o):
         self.ops.append(o)
         self._arr = None
+
+    def add_all(self, ops):
+        """add the ops of a plain list (what a recorder such as gan_nets.FreqSplit returns)"""
+        for o in ops:
+            self.add(o)
 
     def extend(self, other):
         self.ops.extend(other.ops)

@@ -6,13 +6,11 @@ VGGFeatureHIP          : codes/SRN/models/modules/architecture.py:1060-1088 (vgg
 Both run in split-bf16 (prec 3, ~fp32) on fp32 activations: together they are <10 % of the step's FLOPs and they sit
 between the losses and the generator gradient, where the 1e-2 gradient tolerance is decided.
 """
-import ctypes as C
-
 import torch
 
 from . import _lib
 from .engine import (BTensor, ParamStore, PackRegistry, OpList, WgradGroup, Workspace, conv_op, ceil_div)
-from ._lib import Tensor, make_op
+from ._lib import make_op
 
 SLOPE = 0.2
 IN_EPS = 1e-5
@@ -264,6 +262,107 @@ def vgg128_init_state_dict(spec, seed):
     return sd
 
 
+def gaussian_kernel2d(k):
+    """GaussianFilter weights (architecture.py:1177-1199)"""
+    mean, var = (k - 1) / 2.0, (k / 6.0) ** 2.0
+    ax = torch.arange(k, dtype=torch.float32)
+    xx = ax.repeat(k).view(k, k)
+    g = torch.exp(-((xx - mean) ** 2 + (xx.t() - mean) ** 2) / (2 * var))
+    return g / g.sum()
+
+
+def _null(t):
+    return t is None or t.p is None
+
+
+class FreqSplit:
+    """The frequency-separation front end of the GAN trainers: Haar wavelet (dasr_dwt_fwd / _bwd) or a k x k low-pass (dasr_lowpass / _valid) with
+    the high band 0.5 + 0.5 (x - low(x)).  A model builds it once from its options (srn / dsn); the plans ask it for the ops to add, so the
+    kernel, the filter weights and the flag words are chosen here and nowhere else.  x, the outputs and the gradients are dasr_tensor views of N
+    three-channel images, (H, W) is the size of the image itself; an absent output or gradient is None (or NULL_T)."""
+
+    def __init__(self, wavelet, gaussian, k, device, a_h=0.5, b_h=0.5, dwt_norm=1, valid_bit=0):
+        self.wavelet, self.k = bool(wavelet), int(k)
+        w = gaussian_kernel2d(self.k) if gaussian else torch.full((self.k, self.k), 1.0 / (self.k * self.k))
+        self.w = w.contiguous().to(device)       # the k x k filter (a wavelet model has it for its image views: DASR_Model.filter_high)
+        self.a_h, self.b_h = a_h, b_h            # a_h / b_h of dasr_lowpass: scale and offset of the high band
+        self.valid_bit = valid_bit               # `mode` bit 1 (value 2) of dasr_lowpass: the box average counts only the pixels inside the image
+        self.dwt_norm = dwt_norm                 # `norm` of dasr_dwt_fwd / _bwd: 1 = bands normalised to [0, 1], 2 = 'sum' format (LH + HL + HH) / 3
+        self.in_nc = 9 if (self.wavelet and not dwt_norm & 2) else 3   # channels the discriminator sees
+
+    @classmethod
+    def srn(cls, fs, k, norm, device):
+        """train options fs ('wavelet', 'gau', 'avgpool': count_include_pad=True), fs_kernel_size, norm of the SRN trainer"""
+        if fs not in ('wavelet', 'gau', 'avgpool'):
+            raise NotImplementedError('FS type [{:s}] not recognized.'.format(str(fs)))
+        a_h, b_h = (0.25, 0.75) if norm else (0.5, 0.5)   # FilterHigh normalises, filter_func normalises again (App. C-11)
+        return cls(fs == 'wavelet', fs != 'avgpool', k or 5, device, a_h, b_h, dwt_norm=int(bool(norm)))
+
+    @classmethod
+    def dsn(cls, filter, k, cat_or_sum, device):
+        """--filter ('gau', 'avg_pool': count_include_pad=False, 'wavelet'), --kernel_size, --cat_or_sum of the DSN trainer"""
+        if filter not in ('gau', 'avg_pool', 'wavelet'):
+            raise NotImplementedError('Frequency Separation type [{:s}] not recognized'.format(filter))
+        if cat_or_sum not in ('cat', 'sum'):
+            raise NotImplementedError('Wavelet format [{:s}] not recognized'.format(str(cat_or_sum)))
+        return cls(filter == 'wavelet', filter != 'avg_pool', k, device, dwt_norm=1 | (2 if cat_or_sum == 'sum' else 0),
+                   valid_bit=2 if filter == 'avg_pool' else 0)
+
+    def out_size(self, h, w):
+        """size of the bands of an h x w image"""
+        return (h // 2, w // 2) if self.wavelet else (h, w)
+
+    def colour_size(self, h, w):
+        """size of colour() of an h x w image"""
+        return (h // 2, w // 2) if self.wavelet else (h - self.k + 1, w - self.k + 1)
+
+    def _dwt(self, kind, N, H, W, **args):
+        return make_op(kind, N=N, C=3, H2=H // 2, W2=W // 2, **args)
+
+    def _lowpass(self, kind, N, H, W, **args):
+        return make_op(kind, w=self.w.data_ptr(), k=self.k, N=N, C=3, H=H, W=W, **args)
+
+    def split(self, x, N, H, W, low=None, high=None):
+        """x -> the low band and / or the high band(s); no op when neither is wanted"""
+        if _null(low) and _null(high):
+            return []
+        if self.wavelet:
+            return [self._dwt(_lib.OP_DWT_FWD, N, H, W, x=x, norm=self.dwt_norm, ll=low, hc=high)]
+        return [self._lowpass(_lib.OP_LOWPASS, N, H, W, x=x, mode=self.valid_bit, a_h=self.a_h, b_h=self.b_h, out_low=low, out_high=high)]
+
+    def tangent(self, x, N, H, W, out):
+        """the linear part of the high band (no offset) of x"""
+        if self.wavelet:
+            return [self._dwt(_lib.OP_DWT_FWD, N, H, W, x=x, norm=self.dwt_norm | 4, hc=out)]
+        return [self._lowpass(_lib.OP_LOWPASS, N, H, W, x=x, mode=self.valid_bit, a_h=self.a_h, out_high=out)]
+
+    def colour(self, x, N, H, W, out):
+        """the DSN colour filter (loss.py:50-58,103-107): low-pass without padding, or Haar LL * 0.5"""
+        if self.wavelet:
+            return [self._dwt(_lib.OP_DWT_FWD, N, H, W, x=x, norm=1, ll=out)]
+        return [self._lowpass(_lib.OP_LOWPASS_VALID, N, H, W, x=x, out=out)]
+
+    def adjoint(self, dst, N, H, W, g_low=None, g_high=None, g_colour=None):
+        """dst += adjoint of split() on (g_low, g_high) and of colour() on g_colour.  The wavelet takes them in ONE op (g_colour in the place of
+        g_low: a plan has one or the other); the low-pass records one op for the bands and one for the colour filter."""
+        assert _null(g_low) or _null(g_colour)
+        if self.wavelet:
+            gll = g_colour if _null(g_low) else g_low
+            if _null(gll) and _null(g_high):
+                return []
+            return [self._dwt(_lib.OP_DWT_BWD, N, H, W, gll=gll, ghc=g_high, norm=self.dwt_norm, gx=dst, accumulate=1)]
+        ops = []
+        if not (_null(g_low) and _null(g_high)):
+            ops.append(self._lowpass(_lib.OP_LOWPASS, N, H, W, x=g_low, x2=g_high, mode=1 | self.valid_bit, a_h=self.a_h, out_low=dst, accumulate=1))
+        if not _null(g_colour):
+            ops.append(self._lowpass(_lib.OP_LOWPASS_VALID, N, H, W, x=g_colour, mode=1, out=dst, accumulate=1))
+        return ops
+
+    def colour_adjoint(self, g, dst, N, H, W):
+        """dst += adjoint of colour() on g"""
+        return self.adjoint(dst, N, H, W, g_colour=g)
+
+
 class _DPlan:
     """Forward on N images; data-gradient of the first `n_g` images (generator step, no weight gradients);
     full backward with weight gradients on all N images (discriminator step)."""
@@ -299,9 +398,28 @@ class _DPlan:
         self.bwd_data = {}
         self.ws.finalize()
 
-    def view_n(self, bt, n0=0):
-        v = bt.view()
-        return Tensor(v.p + n0 * v.n_stride * bt.esz, v.n_stride, v.cb_stride)
+    _NORM_OPS = {'fwd': (_lib.OP_BNORM_FWD, _lib.OP_INORM_FWD), 'bwd': (_lib.OP_BNORM_BWD, _lib.OP_INORM_BWD),
+                 'jvp': (_lib.OP_BNORM_JVP, _lib.OP_INORM_JVP), 'second': (_lib.OP_BNORM_SECOND, _lib.OP_INORM_SECOND)}
+
+    def norm_op(self, i, kind, N, dgamma=None, dbeta=None, **tensors):
+        """the normalisation op of layer i on the first N images for the pass `kind` ('fwd', 'bwd', 'jvp', 'second'): the BatchNorm op (on the conv
+        output zs[i], with group / gamma / beta) or the InstanceNorm op (forward: zs[i]; the others: the saved activation acts[i]).  tensors: what differs
+        from site to site (ga / gx, t / out, accumulate); dgamma / dbeta: where a BatchNorm op adds its parameter gradients (InstanceNorm has none)."""
+        L, P = self.net.layers[i], self.net.params
+        batch = L['norm'] == 'batch'
+        ho, wo = self.dims[i + 1]
+        args = dict(N=N, C=L['cout'], H=ho, W=wo, slope=SLOPE, stats=self.stats[i].data_ptr(), **tensors)
+        if kind == 'fwd':
+            args.update(x=self.zs[i].view(), y=self.acts[i].view(), eps=BN_EPS if batch else IN_EPS)
+        else:
+            args['x' if batch else 'a'] = (self.zs[i] if batch else self.acts[i]).view()
+        if batch:
+            args.update(group=self.group, gamma=P.ptr(L['bn'] + 'weight'), beta=P.ptr(L['bn'] + 'bias'))
+            if kind == 'bwd':
+                args.update(dgamma=dgamma, dbeta=dbeta, pscale=1.0)
+            elif kind == 'second':
+                args.update(dgamma=dgamma, pscale=1.0)
+        return make_op(self._NORM_OPS[kind][0 if batch else 1], **args)
 
     def _build_fwd(self, N):
         net, P, pack = self.net, self.net.params, self.net.pack
@@ -313,12 +431,7 @@ class _DPlan:
             if L['norm']:
                 ops.add(conv_op(pack, L['fwd'], src.view(), True, L['cin_pad'], hi, wi, ho, wo, N, bias=bias, kh=L['kh'], stride=L['stride'],
                                 pad=L['pad'], out_f32=self.zs[i].view()))
-                if L['norm'] == 'batch':
-                    ops.add(make_op(_lib.OP_BNORM_FWD, x=self.zs[i].view(), N=N, C=L['cout'], H=ho, W=wo, group=self.group, eps=BN_EPS, slope=SLOPE,
-                                    gamma=P.ptr(L['bn'] + 'weight'), beta=P.ptr(L['bn'] + 'bias'), y=self.acts[i].view(), stats=self.stats[i].data_ptr()))
-                else:
-                    ops.add(make_op(_lib.OP_INORM_FWD, x=self.zs[i].view(), N=N, C=L['cout'], H=ho, W=wo, eps=IN_EPS, slope=SLOPE, y=self.acts[i].view(),
-                                    stats=self.stats[i].data_ptr()))
+                ops.add(self.norm_op(i, 'fwd', N))
             else:
                 ops.add(conv_op(pack, L['fwd'], src.view(), True, L['cin_pad'], hi, wi, ho, wo, N, bias=bias, kh=L['kh'], stride=L['stride'],
                                 pad=L['pad'], act=0 if L.get('last') else 1, slope=SLOPE, out_f32=self.acts[i].view()))
@@ -352,14 +465,9 @@ class _DPlan:
             L = net.layers[i]
             (hi, wi), (ho, wo) = self.dims[i], self.dims[i + 1]
             gz = self.gz[i]
-            if L['norm'] == 'batch':  # dL/da -> dL/dz through BatchNorm (per-half statistics) + LeakyReLU; dgamma / dbeta in the discriminator step
-                ops.add(make_op(_lib.OP_BNORM_BWD, x=self.zs[i].view(), ga=self.ga[i].view(), N=N, C=L['cout'], H=ho, W=wo, group=self.group, slope=SLOPE,
-                                gamma=P.ptr(L['bn'] + 'weight'), beta=P.ptr(L['bn'] + 'bias'), stats=self.stats[i].data_ptr(), gx=gz.view(),
-                                dgamma=P.ptr(L['bn'] + 'weight', P.grad) if wgrad else None, dbeta=P.ptr(L['bn'] + 'bias', P.grad) if wgrad else None,
-                                pscale=1.0))
-            elif L['norm']:  # dL/da -> dL/dz through InstanceNorm + LeakyReLU
-                ops.add(make_op(_lib.OP_INORM_BWD, a=self.acts[i].view(), ga=self.ga[i].view(), N=N, C=L['cout'], H=ho, W=wo, slope=SLOPE,
-                                stats=self.stats[i].data_ptr(), gx=gz.view()))
+            if L['norm']:  # dL/da -> dL/dz through the norm (BatchNorm: per-half statistics) + LeakyReLU; dgamma / dbeta in the discriminator step
+                pg = (P.ptr(L['bn'] + 'weight', P.grad), P.ptr(L['bn'] + 'bias', P.grad)) if (wgrad and L['norm'] == 'batch') else (None, None)
+                ops.add(self.norm_op(i, 'bwd', N, ga=self.ga[i].view(), gx=gz.view(), dgamma=pg[0], dbeta=pg[1]))
             inp = self.x if i == 0 else self.acts[i - 1]
             if wgrad:
                 split = None
@@ -504,12 +612,6 @@ class VGGFeatureHIP:
         return self.plans[k]
 
 
-def _nview_t(bt, n0):
-    """dasr_tensor view of images [n0:] of a blocked tensor"""
-    v = bt.view()
-    return Tensor(v.p + n0 * v.n_stride * bt.esz, v.n_stride, v.cb_stride)
-
-
 class _VGGPlan:
     def __init__(self, net, N, n_g, H, W):
         self.net, self.N, self.n_g = net, N, n_g
@@ -536,8 +638,8 @@ class _VGGPlan:
                 fwd.add(conv_op(pack, net.pk[idx], src.view(), True, ceil_div(cin, 16) * 16, h, w, h, w, ng,
                                 bias=P.ptr('features.%d.bias' % idx), act=1 if relu else 0, slope=0.0, out_f32=out.view()))
                 if split:   # the no-gradient images: one f16 pass
-                    fwd.add(conv_op(pack, net.pk[(idx, 'r')], _nview_t(src, n_g), True, ceil_div(cin, 16) * 16, h, w, h, w, N - n_g,
-                                    bias=P.ptr('features.%d.bias' % idx), act=1 if relu else 0, slope=0.0, out_f32=_nview_t(out, n_g)))
+                    fwd.add(conv_op(pack, net.pk[(idx, 'r')], src.view(n0=n_g), True, ceil_div(cin, 16) * 16, h, w, h, w, N - n_g,
+                                    bias=P.ptr('features.%d.bias' % idx), act=1 if relu else 0, slope=0.0, out_f32=out.view(n0=n_g)))
             else:
                 h, w = h // 2, w // 2
                 out = BTensor(N, cout, h, w, True, dev)
@@ -575,7 +677,7 @@ class _VGGPlan:
 
     def input_copy_op(self, src_view, n0, n, H, W):
         """op that writes `n` images of a blocked f32 tensor (<= 16 channels) into x[n0 : n0 + n] (DSN: no input normalisation)"""
-        dst = Tensor(self.x.view().p + n0 * self.x.view().n_stride * self.x.esz, self.x.view().n_stride, self.x.view().cb_stride)
+        dst = self.x.view(n0=n0)
         if self.net.f16s or self.net.split:
             return make_op(_lib.OP_CVT_F16, x=src_view, N=n, C=16, H=H, W=W, scale=1.0, y=dst, form=int(self.net.split))
         return make_op(_lib.OP_AXPBY, x=src_view, a=1.0, N=n, C=16, H=H, W=W, out_f32=dst, gamma=1.0)
@@ -614,9 +716,9 @@ class _VGGPlan:
                                 out_f32=out.view() if last else None, out_bf16=None if last else out.view(), out16_f16=0 if last else 1,
                                 in_wrap=2 * kin, out16_lo=0 if last else c16(cout) // 16))
                 if one_pass:   # the no-gradient images: one f16 pass over the hi planes, hi planes out (their lo planes stay zero)
-                    fwd.add(conv_op(pack, net.pk[(idx, 'r')], _nview_t(src, n_g), False, c16(cin), h, w, h, w, N - n_g, bias=bias,
-                                    act=1 if relu else 0, slope=0.0, out_f32=_nview_t(out, n_g) if last else None,
-                                    out_bf16=None if last else _nview_t(out, n_g), out16_f16=0 if last else 1))
+                    fwd.add(conv_op(pack, net.pk[(idx, 'r')], src.view(n0=n_g), False, c16(cin), h, w, h, w, N - n_g, bias=bias,
+                                    act=1 if relu else 0, slope=0.0, out_f32=out.view(n0=n_g) if last else None,
+                                    out_bf16=None if last else out.view(n0=n_g), out16_f16=0 if last else 1))
                     fwd.ops[-1].set('tag', 7)
             else:
                 h, w = h // 2, w // 2

@@ -24,7 +24,7 @@ import torch
 
 from . import _lib
 from .engine import BTensor, ParamStore, PackRegistry, OpList, conv_op, ceil_div
-from ._lib import Tensor, make_op
+from ._lib import make_op
 
 SHIFT = (-.030, -.088, -.188)     # ScalingLayer, networks_basic.py:94-101
 SCALE = (.458, .448, .450)
@@ -283,8 +283,7 @@ class _LPIPSPlan:
 
     def input_op(self, img_view, n0, n_imgs):
         """blocked f32 image (3 channels in plane 0, values in [0,1]) -> scaled space-to-depth input of images [n0, n0 + n_imgs)"""
-        v = self.x.view()
-        return self._s2d(img_view, n_imgs, Tensor(v.p + n0 * v.n_stride * 4, v.n_stride, v.cb_stride), 0)
+        return self._s2d(img_view, n_imgs, self.x.view(n0=n0), 0)
 
     def adjoint_op(self, gimg_view):
         """dL/dx of the n fake images ACCUMULATED into channels 0..2 of a blocked f32 image gradient"""

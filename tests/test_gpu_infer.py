@@ -146,9 +146,11 @@ def test_filter_high_visual_matches_reference_filter(golden_dir):
     from oracle import nets
     from dasr_amd import options
     from dasr_amd.dasr_model import DASR_Model
+    from dasr_amd.gan_nets import FreqSplit
     m = DASR_Model.__new__(DASR_Model)
     m.opt = options.dict_to_nonedict({'train': {'fs_kernel_size': 9}})
     m.device, m.fs = dev, 'wavelet'
+    m.freq = FreqSplit.srn(m.fs, m.opt['train']['fs_kernel_size'], False, dev)   # what __init__ builds from the same options
     x = torch.rand(2, 3, 40, 56, generator=torch.Generator().manual_seed(3))
     want = nets.FilterHigh(kernel_size=9, gaussian=True)(x)
     got = m.filter_high(x.to(dev)).cpu()
