@@ -27,7 +27,7 @@ import torch
 from . import _lib
 from ._lib import make_op
 from .engine import (BTensor, ParamStore, PackRegistry, OpList, WgradGroup, WgradGroup3, Workspace, conv_op, ceil_div, ensure_runtime_ready, _stream,
-                     patch, set_reduce_scale, dp_world)
+                     patch, set_reduce_scale, dp_world, F32, SPLIT)
 from .gan_nets import (NLayerDiscriminatorHIP, BatchNormDiscriminatorHIP, VGGFeatureHIP, FreqSplit, VGG16_CFG, fsd_spec, dsn_nld_spec, fold_batchnorm_fsd,
                        gaussian_kernel2d)
 from .models import AdamHIP
@@ -202,7 +202,7 @@ class _GPlan:
         if b16:
             import math
             B16 = lambda: BTensor(N, 64, H, W, False, dev, f16=True)
-            BS = lambda C_: BTensor(N, 2 * ceil_div(C_, 16) * 16, H, W, False, dev, f16=True)   # split tensor: hi planes, then remainder planes
+            BS = lambda C_: SPLIT.alloc(N, C_, H, W, dev)   # split tensor: hi planes, then remainder planes
             if f16w:   # (view() of a split tensor = its hi planes: the 16-bit shadow)
                 self.x_s = BS(16)
                 self.s16 = [BS(64) for _ in range(nb)]
@@ -228,9 +228,9 @@ class _GPlan:
         f = OpList()
         f.add(make_op(_lib.OP_NCHW2B, src=self.x_nchw.data_ptr(), N=N, C=3, H=H, W=W, dst_f32=self.x_in.view()))
         if f16w and nb:
-            f.add(make_op(_lib.OP_CVT_F16, x=self.x_in.view(), N=N, C=16, H=H, W=W, scale=1.0, y=self.x_s.view(), form=1))
-            f.add(conv_op(pack, pk['in_s'], self.x_s.view(), False, 48, H, W, H, W, N, bias=sp('block_input.0.bias'), act=1,
-                          slope_ptr=sp('block_input.1.weight'), out_f32=self.s[0].view(), out_bf16=self.s16[0].view(), out16_f16=1, in_wrap=2, out16_lo=4))
+            f.add(make_op(_lib.OP_CVT_F16, x=self.x_in.view(), N=N, C=16, H=H, W=W, scale=1.0, y=self.x_s.view(), form=SPLIT.cvt_form))
+            f.add(conv_op(pack, pk['in_s'], Hin=H, Win=W, Hout=H, Wout=W, N=N, **SPLIT.conv_in(self.x_s, 16), bias=sp('block_input.0.bias'), act=1,
+                          slope_ptr=sp('block_input.1.weight'), out_f32=self.s[0].view(), **SPLIT.conv_out(self.s16[0], 64)))
         else:
             f.add(conv_op(pack, pk['in'], self.x_in.view(), True, 16, H, W, H, W, N, bias=sp('block_input.0.bias'), act=1,
                           slope_ptr=sp('block_input.1.weight'), out_f32=self.s[0].view(), **(sh(self.s16[0]) if (b16 and nb) else {})))
@@ -245,12 +245,13 @@ class _GPlan:
                 continue
             if f16w:
                 last_blk = k + 1 == nb
-                f.add(conv_op(pack, pk['r%d_1_s' % k], self.s16[k].view(), False, 192, H, W, H, W, N, bias=sp(pre + 'conv1.bias'), act=1,
-                              slope_ptr=sp(pre + 'prelu.weight'), out_bf16=self.h16[k].view(), out16_f16=1, in_wrap=8, out16_lo=4))
-                f.add(conv_op(pack, pk['r%d_2_s' % k], self.h16[k].view(), False, 192, H, W, H, W, N, bias=sp(pre + 'conv2.bias'),
-                              res1=self.s16[k].view(), beta1=1.0, res1_lo=4, in_wrap=8,
-                              out_f32=self.s[nb].view() if last_blk else None, out_bf16=None if last_blk else self.s16[k + 1].view(),
-                              out16_f16=1, out16_lo=0 if last_blk else 4))
+                hw = dict(Hin=H, Win=W, Hout=H, Wout=W, N=N)
+                f.add(conv_op(pack, pk['r%d_1_s' % k], **hw, **SPLIT.conv_in(self.s16[k], 64), bias=sp(pre + 'conv1.bias'), act=1,
+                              slope_ptr=sp(pre + 'prelu.weight'), **SPLIT.conv_out(self.h16[k], 64)))
+                # (the last block writes the f32 s[nb]; out16_f16 stays set on that launch: inherited)
+                out = dict(F32.conv_out(self.s[nb], 64), out16_f16=1) if last_blk else SPLIT.conv_out(self.s16[k + 1], 64)
+                f.add(conv_op(pack, pk['r%d_2_s' % k], **hw, **SPLIT.conv_in(self.h16[k], 64), bias=sp(pre + 'conv2.bias'),
+                              beta1=1.0, **SPLIT.conv_res(self.s16[k], 64), **out))
                 continue
             f.add(conv_op(pack, pk['r%d_1' % k], self.s[k].view(), True, 64, H, W, H, W, N, bias=sp(pre + 'conv1.bias'), act=1,
                           slope_ptr=sp(pre + 'prelu.weight'), out_f32=self.h[k].view(), **sh(self.h16[k] if b16 else None)))

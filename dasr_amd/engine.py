@@ -4,6 +4,7 @@ NC16HW16 activation buffers, packed-weight registry and recorded op lists that l
 PyTorch is used only as the device allocator / stream owner; all arithmetic runs in the HIP library.
 """
 import ctypes as C
+import math
 from collections import OrderedDict
 
 import torch
@@ -68,6 +69,47 @@ class BTensor:
 
 
 NULL_T = Tensor(None, 0, 0)
+
+
+class StorageForm:
+    """How a plan stores an activation or gradient tensor of C channels (K = ceil(C / 16) planes), and what the ops that touch such a tensor pass.
+    Three instances: F32; F16; SPLIT = K planes of f16 `hi` followed by K planes of f16 remainders (22 mantissa bits, 4 bytes per element like
+    f32), which a conv reads as 3K virtual chunks [hi | hi | lo].  view() of a split tensor is its hi planes, so an op of the F16 form runs on them."""
+
+    def __init__(self, code, f32=False, split=False):
+        self.code = code                # dtype code of dasr_affine4's output and of OP_MAXPOOL: 1 f32, 2 f16, 3 split
+        self.f32, self.split = f32, split
+        self.cvt_form = int(split)      # `form` of the OP_CVT_F16 that converts an f32 tensor into this form
+
+    def alloc(self, N, C_, H, W, device):
+        return BTensor(N, 2 * ceil_div(C_, 16) * 16 if self.split else C_, H, W, self.f32, device, f16=not self.f32)
+
+    def conv_in(self, t, C_, n0=0):
+        """conv_op arguments of `t` (images [n0:]) as the input; in_wrap: 2K input planes before the hi planes repeat"""
+        K = ceil_div(C_, 16)
+        return dict(inp=t.view(n0=n0), in_f32=self.f32, cin=(3 if self.split else 1) * 16 * K, in_wrap=2 * K if self.split else 0)
+
+    def conv_out(self, t, C_, n0=0):
+        """conv_op arguments of `t` as the output; out16_lo: the remainder planes start K planes after the hi planes"""
+        if self.f32:
+            return dict(out_f32=t.view(n0=n0))
+        return dict(out_bf16=t.view(n0=n0), out16_f16=1, out16_lo=ceil_div(C_, 16) if self.split else 0)
+
+    def conv_res(self, t, C_):
+        """conv_op arguments of `t` as the residual input"""
+        return dict(res1=t.view(), res1_lo=ceil_div(C_, 16) if self.split else 0)
+
+    def pool_bwd(self, grad):
+        """dtype code of an OP_MAXPOOL_BWD that reads activations of this form and gradients of form `grad`"""
+        return {(1, 1): 1, (2, 2): 2, (3, 3): 3, (3, 2): 5}[self.code, grad.code]
+
+
+F32, F16, SPLIT = StorageForm(1, f32=True), StorageForm(2), StorageForm(3, split=True)
+
+
+def grad_prescale(count):
+    """power-of-two pre-scale of the gradient of a mean loss over `count` elements (~1 / count -> ~2^-3) before its f16 rounding: exact to undo"""
+    return float(2.0 ** max(0, int(math.floor(math.log2(max(1, count)))) - 3))
 
 
 # --------------------------------------------------------------------------------------------------
@@ -372,7 +414,7 @@ def conv_op(pack, ref, inp, in_f32, cin, Hin, Win, Hout, Wout, N, bias=None, kh=
     p.in_scale = in_scale if (ref.prec in (2, 4) and in_f32) else 0.0   # power-of-two pre-scale of an f32 gradient input before its f16 rounding
     p.out16_f16 = int(out16_f16)
     p.res1_lo = int(res1_lo)   # res1 is a split 16-bit tensor: its remainder planes start res1_lo planes after the hi planes
-    p.in_wrap, p.out16_lo = int(in_wrap), int(out16_lo)   # split 16-bit tensors (SplitTensor): 2K input planes before the hi planes repeat; K' output planes
+    p.in_wrap, p.out16_lo = int(in_wrap), int(out16_lo)   # split 16-bit tensors (StorageForm SPLIT): 2K input planes before the hi planes repeat; K' output planes
     return o
 
 
@@ -657,7 +699,6 @@ class GradScale:
 
     def set_gscale_from(self, g_t0_absmax):
         """g_t0_absmax: max |dL/d(trunk output)| (host float); headroom * gscale * that is brought to ~1.  Returns the scale."""
-        import math
         a = self.headroom * float(g_t0_absmax)
         s = 1.0 if not (a > 0.0 and math.isfinite(a)) else float(2.0 ** max(-60, min(60, -int(math.ceil(math.log2(a))))))
         self.steps_since_calib = 0

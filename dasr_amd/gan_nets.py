@@ -9,7 +9,7 @@ between the losses and the generator gradient, where the 1e-2 gradient tolerance
 import torch
 
 from . import _lib
-from .engine import (BTensor, ParamStore, PackRegistry, OpList, WgradGroup, Workspace, conv_op, ceil_div)
+from .engine import (BTensor, ParamStore, PackRegistry, OpList, WgradGroup, Workspace, conv_op, ceil_div, F32, F16, SPLIT, grad_prescale)
 from ._lib import make_op
 
 SLOPE = 0.2
@@ -572,6 +572,12 @@ class VGGFeatureHIP:
         # mse_target (feature_criterion l2, the DSN's VGG16 MSE): the gradient is 2 (f_fake - f_target) / n, the target's rounding error enters it in
         # FIRST order, so the target half keeps the precision of the gradient half unless the environment variable asks for the one-pass form.
         self.nograd_prec = int(os.environ.get('DASR_VGG_NOGRAD_PREC', '0' if mse_target else '2')) if self.prec in (3, 4, 5) else 0
+        # the storage forms a plan records with: activations up to the last conv, gradients below it, and what the launch of the no-gradient images
+        # reads and writes (of split tensors the hi planes only: their lo planes stay zero)
+        self.act_form = SPLIT if self.split else (F16 if self.f16s else F32)
+        self.grad_form = {2: F16, 5: SPLIT}.get(self.bwd_prec, F32)
+        self.nograd_form = F16 if self.split else self.act_form
+        self.nograd_tag = 7 if self.split else 6   # time bucket of the no-gradient launches; inherited: only the split builder ever tagged them 7
         self.spec, self.layers = vgg19_spec(feature_layer, cfg)
         self.params = ParamStore(self.spec, self.device)
         self.pack = PackRegistry(self.params)
@@ -613,6 +619,10 @@ class VGGFeatureHIP:
 
 
 class _VGGPlan:
+    """One forward and one backward walk over net.layers.  How a tensor is stored and what the ops that touch it pass come from the network's
+    storage forms (engine.StorageForm): activations up to the last conv in net.act_form, gradients below it in net.grad_form.  In every form the
+    last conv writes f32, a pool behind it (vgg16.features[:31]) runs in f32, and the feature map and dL/dx are f32."""
+
     def __init__(self, net, N, n_g, H, W):
         self.net, self.N, self.n_g = net, N, n_g
         # EVERY tensor an op of this plan points at must stay referenced: the ops hold raw device pointers.  (Until round 3 the intermediate
@@ -620,31 +630,35 @@ class _VGGPlan:
         # the caching allocator did not hand it out again -- the cause of a rare non-finite-gradient failure of the DSN fixtures.)
         self._keep = []
         dev, P, pack = net.device, net.params, net.pack
-        if net.f16s:
-            return self._init_f16(N, n_g, H, W)
-        if net.split:
-            return self._init_split(N, n_g, H, W)
-        self.x_flag = 1                           # dtype code of x for dasr_affine4 (1 f32, 2 f16)
-        self.x = BTensor(N, 16, H, W, True, dev)  # normalised input
+        act, grad = net.act_form, net.grad_form
+
+        def new(form, C_, h, w):
+            self._keep.append(form.alloc(N, C_, h, w, dev))
+            return self._keep[-1]
+        self.x_flag = act.code                    # dtype code of x for dasr_affine4
+        self.x = new(act, 16, H, W)               # normalised input
         self.outs = []
+        lc = max(i for i, L in enumerate(net.layers) if L[0] == 'conv')   # last conv: the hand-off to f32
+        # the images [n_g, N) that carry no gradient: a launch of their own in net.nograd_form (see VGGFeatureHIP.__init__)
+        one_pass = net.nograd_prec not in (0, net.prec) and 0 < n_g < N
         h, w = H, W
         fwd = OpList()
         src = self.x
-        for kind, idx, cin, cout, relu in net.layers:
+        for li, (kind, idx, cin, cout, relu) in enumerate(net.layers):
+            form = act if li < lc else F32
             if kind == 'conv':
-                out = BTensor(N, cout, h, w, True, dev)
-                split = (idx, 'r') in net.pk and 0 < n_g < N
-                ng = n_g if split else N
-                fwd.add(conv_op(pack, net.pk[idx], src.view(), True, ceil_div(cin, 16) * 16, h, w, h, w, ng,
-                                bias=P.ptr('features.%d.bias' % idx), act=1 if relu else 0, slope=0.0, out_f32=out.view()))
-                if split:   # the no-gradient images: one f16 pass
-                    fwd.add(conv_op(pack, net.pk[(idx, 'r')], src.view(n0=n_g), True, ceil_div(cin, 16) * 16, h, w, h, w, N - n_g,
-                                    bias=P.ptr('features.%d.bias' % idx), act=1 if relu else 0, slope=0.0, out_f32=out.view(n0=n_g)))
+                out = new(form, cout, h, w)
+                kw = dict(Hin=h, Win=w, Hout=h, Wout=w, bias=P.ptr('features.%d.bias' % idx), act=1 if relu else 0, slope=0.0)
+                fwd.add(conv_op(pack, net.pk[idx], N=n_g if one_pass else N, **act.conv_in(src, cin), **form.conv_out(out, cout), **kw))
+                if one_pass:
+                    rform = net.nograd_form if li < lc else F32
+                    fwd.add(conv_op(pack, net.pk[(idx, 'r')], N=N - n_g, **net.nograd_form.conv_in(src, cin, n_g), **rform.conv_out(out, cout, n_g), **kw))
+                    fwd.ops[-1].set('tag', net.nograd_tag)
             else:
                 h, w = h // 2, w // 2
-                out = BTensor(N, cout, h, w, True, dev)
+                out = new(form, cout, h, w)
                 # Win: input width (odd widths: the last column is dropped)
-                fwd.add(make_op(_lib.OP_MAXPOOL, x=src.view(), N=N, C=cout, Ho=h, Wo=w, is_f32=1, y=out.view(), Win=src.W))
+                fwd.add(make_op(_lib.OP_MAXPOOL, x=src.view(), N=N, C=cout, Ho=h, Wo=w, is_f32=form.code, y=out.view(), Win=src.W))
             self.outs.append(out)
             src = out
         self.feat = src
@@ -653,184 +667,44 @@ class _VGGPlan:
         # a dgrad conv's epilogue applies the ReLU' of the layer that produced its input; a pool's backward applies the
         # ReLU' of the conv feeding the pool (every VGG pool follows a ReLU).
         n = n_g
-        self.g_feat = BTensor(N, self.feat.C, self.feat.H, self.feat.W, True, dev)
-        self.gx = BTensor(N, 16, H, W, True, dev)
-        # prec 4 (split-f16): dL/dfeat of a mean loss is ~1 / element count; a power-of-two pre-scale keeps it in f16's normal range (exact)
-        import math
-        cnt = max(1, n_g * self.feat.C * self.feat.H * self.feat.W)
-        gsc = float(2.0 ** max(0, int(math.floor(math.log2(cnt))) - 3)) if net.prec == 4 else 0.0
+        self.g_feat = new(F32, self.feat.C, self.feat.H, self.feat.W)
+        self.gx = new(F32, 16, H, W)
+        # dL/dfeat of a mean loss over n_g x C x h x w elements is ~1 / count: a power-of-two pre-scale keeps its 16-bit roundings in f16's normal range
+        prescale = grad_prescale(n_g * self.feat.C * self.feat.H * self.feat.W)
+        if grad.f32:   # prec 4 rounds f32 gradients to f16 pairs inside each conv (in_scale); the other f32 precisions do not scale
+            in_scale = prescale if net.prec == 4 else 0.0
+        else:          # 16-bit gradients: one conversion at the last conv multiplies by gscale, the conv of layer 0 divides it out
+            self.gscale, in_scale = prescale, 0.0
         bwd = OpList()
         g = self.g_feat
         for li in range(len(net.layers) - 1, -1, -1):
             kind, idx, cin, cout, relu = net.layers[li]
             inp = self.x if li == 0 else self.outs[li - 1]
-            gin = self.gx if li == 0 else BTensor(N, inp.C, inp.H, inp.W, True, dev)
-            self._keep.append(gin)
             if kind == 'conv':
-                prev_relu = li > 0 and net.layers[li - 1][0] == 'conv' and net.layers[li - 1][4]
-                bwd.add(conv_op(pack, net.pk[(idx, 'b')], g.view(), True, cout, inp.H, inp.W, inp.H, inp.W, n,
-                                mask=inp.view() if prev_relu else None, mask_f32=1, slope=0.0, out_f32=gin.view(), in_scale=gsc))
+                if li == lc and not grad.f32:   # f32 gradient of the last conv's output -> pre-scaled tensor of the gradient form
+                    gs = new(grad, cout, g.H, g.W)
+                    bwd.add(make_op(_lib.OP_CVT_F16, x=g.view(), N=n, C=cout, H=g.H, W=g.W, scale=self.gscale, y=gs.view(), form=grad.cvt_form))
+                    g = gs
+                gin = self.gx if li == 0 else new(grad, cin, inp.H, inp.W)
+                if li == 0 and not grad.f32:   # dL/d(normalised input): f32, un-scaled  (no mask; slope stays at conv_op's default: inherited)
+                    kw = dict(alpha=1.0 / self.gscale)
+                else:   # mask = sign of the forward activation; of a 16-bit one: of its hi plane (a non-zero value never rounds to a zero of the other sign)
+                    prev_relu = li > 0 and net.layers[li - 1][0] == 'conv' and net.layers[li - 1][4]
+                    kw = dict(mask=inp.view() if prev_relu else None, mask_f32=int(act.f32), slope=0.0, in_scale=in_scale)
+                bwd.add(conv_op(pack, net.pk[(idx, 'b')], Hin=inp.H, Win=inp.W, Hout=inp.H, Wout=inp.W, N=n, **grad.conv_in(g, cout),
+                                **(F32 if li == 0 else grad).conv_out(gin, cin), **kw))
             else:
-                bwd.add(make_op(_lib.OP_MAXPOOL_BWD, x=inp.view(), gy=g.view(), N=n, C=cout, Ho=g.H, Wo=g.W, is_f32=1, relu_mask=1, gx=gin.view(), Win=inp.W))
+                aform, gform = (F32, F32) if li > lc else (act, grad)
+                gin = new(gform, cout, inp.H, inp.W)
+                bwd.add(make_op(_lib.OP_MAXPOOL_BWD, x=inp.view(), gy=g.view(), N=n, C=cout, Ho=g.H, Wo=g.W, is_f32=aform.pool_bwd(gform), relu_mask=1,
+                                gx=gin.view(), Win=inp.W))
             g = gin
         self.bwd = bwd.tag(8)
 
     def input_copy_op(self, src_view, n0, n, H, W):
         """op that writes `n` images of a blocked f32 tensor (<= 16 channels) into x[n0 : n0 + n] (DSN: no input normalisation)"""
-        dst = self.x.view(n0=n0)
-        if self.net.f16s or self.net.split:
-            return make_op(_lib.OP_CVT_F16, x=src_view, N=n, C=16, H=H, W=W, scale=1.0, y=dst, form=int(self.net.split))
-        return make_op(_lib.OP_AXPBY, x=src_view, a=1.0, N=n, C=16, H=H, W=W, out_f32=dst, gamma=1.0)
+        dst, form = self.x.view(n0=n0), self.net.act_form
+        if form.f32:
+            return make_op(_lib.OP_AXPBY, x=src_view, a=1.0, N=n, C=16, H=H, W=W, out_f32=dst, gamma=1.0)
+        return make_op(_lib.OP_CVT_F16, x=src_view, N=n, C=16, H=H, W=W, scale=1.0, y=dst, form=form.cvt_form)
 
-    def _init_split(self, N, n_g, H, W):
-        """split-f16 storage (prec 5): every activation up to the last conv and every gradient below it is a SPLIT tensor -- K planes of f16 `hi`
-        followed by K planes of f16 remainders (22 mantissa bits; gradients pre-scaled by gscale) -- and every 3x3 conv is one launch of the
-        LDS-DMA dense-conv kernel over 3K virtual chunks.  The images [n_g, N) that carry no gradient run one f16 pass over their hi planes
-        (nograd_prec 2, see __init__).  The last conv writes f32, a pool behind it (vgg16.features[:31]) runs in f32, dL/dx is f32."""
-        import math
-        net = self.net
-        dev, P, pack = net.device, net.params, net.pack
-        c16 = lambda c: ceil_div(c, 16) * 16
-        def kept(t):
-            self._keep.append(t)
-            return t
-        Bs = lambda C_, h, w: kept(BTensor(N, 2 * c16(C_), h, w, False, dev, f16=True))   # planes [0, K) hi, [K, 2K) lo
-        Bf = lambda C_, h, w: kept(BTensor(N, C_, h, w, True, dev))
-        self.x_flag = 3
-        self.x = Bs(16, H, W)
-        self.outs = []
-        h, w = H, W
-        fwd = OpList()
-        src, src_c = self.x, 16
-        nl = len(net.layers)
-        lc = max(i for i, L in enumerate(net.layers) if L[0] == 'conv')   # last conv: the hand-off to f32
-        one_pass = bool(net.nograd_prec) and 0 < n_g < N
-        ng = n_g if one_pass else N
-        for li, (kind, idx, cin, cout, relu) in enumerate(net.layers):
-            if kind == 'conv':
-                last = li == lc
-                out = Bf(cout, h, w) if last else Bs(cout, h, w)
-                kin = c16(cin) // 16
-                bias = P.ptr('features.%d.bias' % idx)
-                fwd.add(conv_op(pack, net.pk[idx], src.view(), False, 3 * c16(cin), h, w, h, w, ng, bias=bias, act=1 if relu else 0, slope=0.0,
-                                out_f32=out.view() if last else None, out_bf16=None if last else out.view(), out16_f16=0 if last else 1,
-                                in_wrap=2 * kin, out16_lo=0 if last else c16(cout) // 16))
-                if one_pass:   # the no-gradient images: one f16 pass over the hi planes, hi planes out (their lo planes stay zero)
-                    fwd.add(conv_op(pack, net.pk[(idx, 'r')], src.view(n0=n_g), False, c16(cin), h, w, h, w, N - n_g, bias=bias,
-                                    act=1 if relu else 0, slope=0.0, out_f32=out.view(n0=n_g) if last else None,
-                                    out_bf16=None if last else out.view(n0=n_g), out16_f16=0 if last else 1))
-                    fwd.ops[-1].set('tag', 7)
-            else:
-                h, w = h // 2, w // 2
-                out = Bf(cout, h, w) if li > lc else Bs(cout, h, w)
-                # Win: input width (odd widths: the last column is dropped)
-                fwd.add(make_op(_lib.OP_MAXPOOL, x=src.view(), N=N, C=cout, Ho=h, Wo=w, is_f32=1 if li > lc else 3, y=out.view(), Win=src.W))
-            self.outs.append(out)
-            src = out
-        self.feat = src
-        self.fwd = fwd.tag(6)
-        n = n_g
-        self.g_feat = Bf(self.feat.C, self.feat.H, self.feat.W)
-        self.gx = Bf(16, H, W)
-        # dL/dfeat of a mean loss over n_g x C x h x w elements is ~1 / count: scaled to ~2^-3 before it is split (exact power of two)
-        cnt = max(1, n_g * self.feat.C * self.feat.H * self.feat.W)
-        self.gscale = float(2.0 ** max(0, int(math.floor(math.log2(cnt))) - 3))
-        bwd = OpList()
-        g = self.g_feat
-        gsplit = net.bwd_prec == 5
-        Bg = Bs if gsplit else (lambda C_, h_, w_: kept(BTensor(N, C_, h_, w_, False, dev, f16=True)))
-        for li in range(nl - 1, -1, -1):
-            kind, idx, cin, cout, relu = net.layers[li]
-            inp = self.x if li == 0 else self.outs[li - 1]
-            if kind == 'conv':
-                if li == lc:   # f32 gradient of the last conv's output -> pre-scaled split (or plain f16) tensor
-                    gs = Bg(cout, g.H, g.W)
-                    bwd.add(make_op(_lib.OP_CVT_F16, x=g.view(), N=n, C=cout, H=g.H, W=g.W, scale=self.gscale, y=gs.view(), form=int(gsplit)))
-                    g = gs
-                prev_relu = li > 0 and net.layers[li - 1][0] == 'conv' and net.layers[li - 1][4]
-                kg = c16(cout) // 16
-                hh, ww = g.H, g.W
-                gcin, gwrap = (3 * c16(cout), 2 * kg) if gsplit else (c16(cout), 0)
-                if li == 0:   # dL/d(normalised input): f32, un-scaled
-                    bwd.add(conv_op(pack, net.pk[(idx, 'b')], g.view(), False, gcin, hh, ww, hh, ww, n, alpha=1.0 / self.gscale,
-                                    out_f32=self.gx.view(), in_wrap=gwrap))
-                    break
-                gin = Bg(cin, hh, ww)
-                # mask = sign of the forward activation = sign of its hi plane (a non-zero value never rounds to a zero of the other sign)
-                bwd.add(conv_op(pack, net.pk[(idx, 'b')], g.view(), False, gcin, hh, ww, hh, ww, n,
-                                mask=inp.view() if prev_relu else None, mask_f32=0, slope=0.0, out_bf16=gin.view(), out16_f16=1,
-                                in_wrap=gwrap, out16_lo=c16(cin) // 16 if gsplit else 0))
-            else:
-                f32 = li > lc
-                gin = Bf(cout, inp.H, inp.W) if f32 else Bg(cout, inp.H, inp.W)
-                bwd.add(make_op(_lib.OP_MAXPOOL_BWD, x=inp.view(), gy=g.view(), N=n, C=cout, Ho=g.H, Wo=g.W, is_f32=1 if f32 else (3 if gsplit else 5),
-                                relu_mask=1, gx=gin.view(), Win=inp.W))
-            g = gin
-        self.bwd = bwd.tag(8)
-
-    def _init_f16(self, N, n_g, H, W):
-        """f16 storage: every activation up to the last conv (and, backward, every gradient below it, pre-scaled by gscale) is an f16 tensor;
-        convs run on the LDS-DMA dense-conv kernel with the f16 MFMA.  The last conv writes f32, a pool behind it (vgg16.features[:31]) runs
-        in f32: the feature map and dL/dx are f32 like in the other modes."""
-        import math
-        net = self.net
-        dev, P, pack = net.device, net.params, net.pack
-        def kept(t):
-            self._keep.append(t)
-            return t
-        Bh = lambda C_, h, w: kept(BTensor(N, C_, h, w, False, dev, f16=True))
-        Bf = lambda C_, h, w: kept(BTensor(N, C_, h, w, True, dev))
-        self.x_flag = 2
-        self.x = Bh(16, H, W)
-        self.outs = []
-        h, w = H, W
-        fwd = OpList()
-        src = self.x
-        nl = len(net.layers)
-        lc = max(i for i, L in enumerate(net.layers) if L[0] == 'conv')   # last conv: the hand-off to f32
-        for li, (kind, idx, cin, cout, relu) in enumerate(net.layers):
-            if kind == 'conv':
-                out = Bf(cout, h, w) if li == lc else Bh(cout, h, w)
-                fwd.add(conv_op(pack, net.pk[idx], src.view(), False, ceil_div(cin, 16) * 16, h, w, h, w, N, bias=P.ptr('features.%d.bias' % idx),
-                                act=1 if relu else 0, slope=0.0, out_f32=out.view() if li == lc else None, out_bf16=None if li == lc else out.view(),
-                                out16_f16=0 if li == lc else 1))
-            else:
-                h, w = h // 2, w // 2
-                out = Bf(cout, h, w) if li > lc else Bh(cout, h, w)
-                # Win: input width (odd widths: the last column is dropped)
-                fwd.add(make_op(_lib.OP_MAXPOOL, x=src.view(), N=N, C=cout, Ho=h, Wo=w, is_f32=1 if li > lc else 2, y=out.view(), Win=src.W))
-            self.outs.append(out)
-            src = out
-        self.feat = src
-        self.fwd = fwd.tag(6)
-        n = n_g
-        self.g_feat = Bf(self.feat.C, self.feat.H, self.feat.W)
-        self.gx = Bf(16, H, W)
-        # dL/dfeat of a mean loss over n_g x C x h x w elements is ~1 / count: scaled to ~2^-3 before its f16 rounding (exact power of two)
-        cnt = max(1, n_g * self.feat.C * self.feat.H * self.feat.W)
-        self.gscale = float(2.0 ** max(0, int(math.floor(math.log2(cnt))) - 3))
-        bwd = OpList()
-        g = self.g_feat
-        for li in range(nl - 1, -1, -1):
-            kind, idx, cin, cout, relu = net.layers[li]
-            inp = self.x if li == 0 else self.outs[li - 1]
-            if kind == 'conv':
-                if li == lc:   # f32 gradient of the last conv's output -> pre-scaled f16
-                    g16 = Bh(g.C, g.H, g.W)
-                    bwd.add(make_op(_lib.OP_CVT_F16, x=g.view(), N=n, C=g.C, H=g.H, W=g.W, scale=self.gscale, y=g16.view()))
-                    g = g16
-                prev_relu = li > 0 and net.layers[li - 1][0] == 'conv' and net.layers[li - 1][4]
-                if li == 0:   # dL/d(normalised input): f32, un-scaled
-                    bwd.add(conv_op(pack, net.pk[(idx, 'b')], g.view(), False, cout, inp.H, inp.W, inp.H, inp.W, n, alpha=1.0 / self.gscale,
-                                    out_f32=self.gx.view()))
-                    break
-                gin = Bh(inp.C, inp.H, inp.W)
-                bwd.add(conv_op(pack, net.pk[(idx, 'b')], g.view(), False, cout, inp.H, inp.W, inp.H, inp.W, n,
-                                mask=inp.view() if prev_relu else None, mask_f32=0, slope=0.0, out_bf16=gin.view(), out16_f16=1))
-            else:
-                f32 = li > lc
-                gin = Bf(inp.C, inp.H, inp.W) if f32 else Bh(inp.C, inp.H, inp.W)
-                bwd.add(make_op(_lib.OP_MAXPOOL_BWD, x=inp.view(), gy=g.view(), N=n, C=cout, Ho=g.H, Wo=g.W, is_f32=1 if f32 else 2, relu_mask=1, gx=gin.view(),
-                                Win=inp.W))
-            g = gin
-        self.bwd = bwd.tag(8)

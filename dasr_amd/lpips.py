@@ -23,7 +23,7 @@ from collections import OrderedDict
 import torch
 
 from . import _lib
-from .engine import BTensor, ParamStore, PackRegistry, OpList, conv_op, ceil_div
+from .engine import BTensor, ParamStore, PackRegistry, OpList, conv_op, ceil_div, grad_prescale
 from ._lib import make_op
 
 SHIFT = (-.030, -.088, -.188)     # ScalingLayer, networks_basic.py:94-101
@@ -247,7 +247,7 @@ class _LPIPSPlan:
         self.ghead = [BTensor(n, r.C, r.H, r.W, True, dev) for r in self.relu]
         self.gx = BTensor(n, 48, Hs, Ws, True, dev)
         # split-f16: the head gradients (~1 / (n * pixels)) are pre-scaled by a power of two into f16's normal range (exact, undone on the accumulator)
-        gsc = float(2.0 ** max(0, int(math.floor(math.log2(max(1, n * H * W // 16)))) - 3)) if PREC == 4 else 0.0
+        gsc = grad_prescale(n * H * W // 16) if PREC == 4 else 0.0
         bwd = OpList()
         g = self.ghead[4]                                   # total gradient at relu5 = its head gradient
         for li in range(4, 0, -1):

@@ -13,7 +13,7 @@ import torch
 
 from . import _lib
 from .engine import (BTensor, ParamStore, PackRegistry, OpList, WgradGroup, WgradGroup3, Workspace, conv_op, ceil_div, SLOPE, ConvChain, GradScale,
-                     set_reduce_scale)
+                     set_reduce_scale, grad_prescale)
 from ._lib import Op, Tensor, make_op
 
 GC = 32  # growth channels are hard-wired to 32 in the reference (architecture.py:183)
@@ -439,8 +439,7 @@ class _Plan:
         self.grad = net.params.grad if (replica == 0 or inference) else torch.zeros_like(net.params.grad)
         # power-of-two pre-scale of the HR-tail gradients before their f16 rounding (prec 2): dL/dSR of a mean loss is ~1 / (N 3 H W) ~ 1e-7,
         # far below f16's normal range; scaled to ~2^-3.  Exact (power of two), undone in the conv epilogue / the wgrad reduction.
-        import math
-        self.gscale = float(2.0 ** max(0, int(math.floor(math.log2(max(1, N * 3 * 16 * h * w)))) - 3))
+        self.gscale = grad_prescale(N * 3 * 16 * h * w)
         P, pack, pk = net.params, net.pack, net.pk
         H2, W2, H4, W4 = 2 * h, 2 * w, 4 * h, 4 * w
         sc = nf + 4 * GC  # dense-slab channels

@@ -21,7 +21,7 @@ import torch
 
 from . import _lib
 from ._lib import make_op
-from .engine import BTensor, ParamStore, PackRegistry, OpList, Workspace, conv_op, NULL_T, GradScale
+from .engine import BTensor, ParamStore, PackRegistry, OpList, Workspace, conv_op, NULL_T, GradScale, grad_prescale
 from .rrdbnet import RRDBNetHIP, _Plan as _RRDBPlan
 
 logger = logging.getLogger('base')
@@ -137,7 +137,7 @@ class _Plan(_RRDBPlan):
         self.defer, self.shared_store = False, False
         self.store = store if store is not None else _TrunkScale(net.rdb_f16 and not inference)
         self.grad = net.params.grad if (replica == 0 or inference) else torch.zeros_like(net.params.grad)
-        self.gscale = float(2.0 ** max(0, int(math.floor(math.log2(max(1, N * 3 * 16 * h * w)))) - 3))   # f16 HR tail: as rrdbnet._Plan
+        self.gscale = grad_prescale(N * 3 * 16 * h * w)   # f16 HR tail: as rrdbnet._Plan
         self.fused = net.use_fused(inference)
         self.chain = None
         H2, W2, H4, W4 = 2 * h, 2 * w, 4 * h, 4 * w

@@ -2,6 +2,7 @@
 
     python scripts/plan_fingerprint.py [--root DIR]             one line per op list of every configuration below (needs a GPU: the models build there)
     python scripts/plan_fingerprint.py --steps 2 [--root DIR]   two seeded steps of four configurations: parameters and logged values, bit for bit
+    python scripts/plan_fingerprint.py --vgg [--root DIR]       the VGG19-34 / VGG16-30 plans in every precision, recorded on the host (no GPU, no library)
 
 --root DIR: the directory whose `dasr_amd` package is fingerprinted (default: this checkout), e.g. an export of another commit with its built library.
 The script reads plans only through OpList.ops, _lib.Op and _lib.OP_ARGS, so the same file runs on both sides of a refactor; equal output = equal
@@ -228,6 +229,37 @@ def dsn_plans(torch):
         torch.cuda.empty_cache()
 
 
+VGG_NETS = [('vgg19_34', 34, None), ('vgg16_30', 30, 'VGG16_CFG')]
+VGG_PRECS = [(5, 2), (5, 5), (4, None), (3, None), (2, None), (1, None)]
+VGG_SHAPES = [(3, 2, 40, 40),   # split batch; an odd 5 x 5 map in front of a pool
+              (2, 2, 32, 48),   # no no-gradient half; the smallest size five pools allow
+              (2, 1, 32, 32),   # the smallest size VGG16-30's five pools allow
+              (2, 0, 32, 32)]   # no gradient image at all
+
+
+def vgg_plans(torch):
+    """the perceptual-network plans of every storage form, recorded on the host (device='cpu': no library, no GPU)"""
+    from dasr_amd import gan_nets
+    from dasr_amd.engine import BTensor
+    for net_name, layer, cfg in VGG_NETS:
+        for prec, bwd_prec in VGG_PRECS:
+            for nograd in (None, '0'):
+                os.environ.pop('DASR_VGG_NOGRAD_PREC', None)
+                if nograd is not None:
+                    os.environ['DASR_VGG_NOGRAD_PREC'] = nograd
+                for mse in (False, True):
+                    V = gan_nets.VGGFeatureHIP(layer, device='cpu', cfg=getattr(gan_nets, cfg) if cfg else None, prec=prec, bwd_prec=bwd_prec, mse_target=mse)
+                    for N, n_g, H, W in VGG_SHAPES:
+                        name = 'vgg/%s_prec%d_bwd%s_nograd%s_%s/%dx%dx%dx%d' % (net_name, prec, bwd_prec or '-', nograd or '-', 'mse' if mse else 'l1', N, n_g, H, W)
+                        P = V.plan(N, n_g, H, W)
+                        src = BTensor(2, 16, H, W, True, 'cpu')
+                        copy = types.SimpleNamespace(ops=[P.input_copy_op(src.view(), 1, 1, H, W)])
+                        gscale = getattr(P, 'gscale', None)
+                        emit(name, Canon(_LIB, [V, P, src]), [('fwd', P.fwd), ('bwd', P.bwd), ('input_copy', copy)],
+                             [('x_flag', P.x_flag), ('gscale', None if gscale is None else float(gscale).hex())])
+    os.environ.pop('DASR_VGG_NOGRAD_PREC', None)
+
+
 def sha(t):
     return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
 
@@ -279,6 +311,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--root', default=REPO, help='directory of the dasr_amd package to fingerprint (default: this checkout)')
     ap.add_argument('--steps', type=int, default=0, help='run this many training steps of the four step configurations instead of hashing plans')
+    ap.add_argument('--vgg', action='store_true', help='hash the perceptual-network plans of every storage form instead, recorded on the host (no GPU)')
     a = ap.parse_args()
     for p in (REPO, os.path.abspath(a.root)):   # (the oracle's fixtures come from this checkout when --root has none)
         if p in sys.path:
@@ -290,7 +323,9 @@ def main():
     global _LIB
     _LIB = _lib
     print('# dasr_amd from %s' % os.path.relpath(os.path.dirname(dasr_amd.__file__), REPO))
-    if a.steps:
+    if a.vgg:
+        vgg_plans(torch)
+    elif a.steps:
         steps(torch, a.steps)
     else:
         srn_plans(torch)

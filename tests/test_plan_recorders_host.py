@@ -1,9 +1,10 @@
-"""CPU tests of the three plan recorders: BTensor.view(c0, n0), gan_nets.FreqSplit and _DPlan.norm_op.  The expected argument values are written out as
-literals: they are what the trainers recorded at every site before the recorders existed.  Everything records on device='cpu'; no kernel runs."""
+"""CPU tests of the four plan recorders: BTensor.view(c0, n0), gan_nets.FreqSplit, _DPlan.norm_op and engine.StorageForm with the one _VGGPlan builder
+that consults it.  The expected argument values are written out as literals: they are what the trainers recorded at every site before the recorders
+existed.  Everything records on device='cpu'; no kernel runs."""
 import pytest
 import torch
 
-from dasr_amd import _lib, gan_nets
+from dasr_amd import _lib, engine, gan_nets
 from dasr_amd._lib import Tensor
 from dasr_amd.engine import BTensor, NULL_T
 from dasr_amd.gan_nets import FreqSplit
@@ -226,3 +227,117 @@ def test_discriminator_plans_record_their_norm_ops_through_the_recorder(norm):
             if batch:
                 want = (P.ptr(bn + 'weight', P.grad), P.ptr(bn + 'bias', P.grad)) if wgrad else (None, 0)
                 assert (o.get('dgamma'), o.get('dbeta'), o.get('pscale')) == want + (1.0,)
+
+
+# ---- engine.StorageForm -------------------------------------------------------------------------------------------
+# form -> per C in (3, 64, 512): planes of alloc, (in_f32, cin, in_wrap), out16_lo, res1_lo; then dtype, OP_CVT_F16 form, affine / pool code
+FORMS = {
+    'F32': ([(1, (True, 16, 0), None, 0), (4, (True, 64, 0), None, 0), (32, (True, 512, 0), None, 0)], torch.float32, 0, 1),
+    'F16': ([(1, (False, 16, 0), 0, 0), (4, (False, 64, 0), 0, 0), (32, (False, 512, 0), 0, 0)], torch.float16, 0, 2),
+    'SPLIT': ([(2, (False, 48, 2), 1, 1), (8, (False, 192, 8), 4, 4), (64, (False, 1536, 64), 32, 32)], torch.float16, 1, 3),
+}
+
+
+@pytest.mark.parametrize('name', sorted(FORMS))
+def test_storage_form_answers_what_the_builders_wrote_out(name):
+    form = getattr(engine, name)
+    rows, dtype, cvt, code = FORMS[name]
+    assert (form.cvt_form, form.code) == (cvt, code)
+    for C_, (planes, inp, out_lo, res_lo) in zip((3, 64, 512), rows):
+        t = form.alloc(3, C_, 4, 6, 'cpu')
+        assert tuple(t.t.shape) == (3, planes, 4, 6, 16) and t.t.dtype == dtype and t.f32 == (name == 'F32') and not bool(t.t.any())
+        a = form.conv_in(t, C_, 2)
+        assert sorted(a) == ['cin', 'in_f32', 'in_wrap', 'inp'] and _t(a['inp']) == _t(t.view(n0=2)) and _t(form.conv_in(t, C_)['inp']) == _t(t.view())
+        assert (a['in_f32'], a['cin'], a['in_wrap']) == inp
+        o = form.conv_out(t, C_, 1)
+        if name == 'F32':
+            assert sorted(o) == ['out_f32'] and _t(o['out_f32']) == _t(t.view(n0=1))
+        else:
+            assert sorted(o) == ['out16_f16', 'out16_lo', 'out_bf16'] and _t(o['out_bf16']) == _t(t.view(n0=1))
+            assert (o['out16_f16'], o['out16_lo']) == (1, out_lo)
+        r = form.conv_res(t, C_)
+        assert sorted(r) == ['res1', 'res1_lo'] and _t(r['res1']) == _t(t.view()) and r['res1_lo'] == res_lo
+
+
+def test_storage_form_backward_pool_codes():
+    F32, F16, SPLIT = engine.F32, engine.F16, engine.SPLIT
+    assert (F32.pool_bwd(F32), F16.pool_bwd(F16), SPLIT.pool_bwd(SPLIT), SPLIT.pool_bwd(F16)) == (1, 2, 3, 5)
+    for act, grad in ((F32, F16), (F16, SPLIT), (F16, F32)):   # combinations no kernel has
+        with pytest.raises(KeyError):
+            act.pool_bwd(grad)
+
+
+@pytest.mark.parametrize('count', [1, 7, 8, 2 ** 20 - 1, 2 ** 20, 3 * 2 ** 31])
+def test_grad_prescale_is_the_written_out_formula(count):
+    import math
+    want = float(2.0 ** max(0, int(math.floor(math.log2(max(1, count)))) - 3))
+    assert engine.grad_prescale(count) == want
+    assert engine.grad_prescale(0) == 1.0
+
+
+# ---- _VGGPlan -----------------------------------------------------------------------------------------------------
+def _reachable_tensors(*roots):
+    """[(first byte, end)] of the storage of every torch tensor reachable from `roots` through dasr_amd objects, lists, tuples and dicts"""
+    spans, seen, stack = [], set(), list(roots)
+    while stack:
+        o = stack.pop()
+        if id(o) in seen:
+            continue
+        seen.add(id(o))
+        if isinstance(o, torch.Tensor):
+            st = o.untyped_storage()
+            spans.append((st.data_ptr(), st.data_ptr() + st.nbytes()))
+        elif isinstance(o, dict):
+            stack.extend(o.values())
+        elif isinstance(o, (list, tuple)):
+            stack.extend(o)
+        elif type(o).__module__.startswith('dasr_amd.') and hasattr(o, '__dict__'):
+            stack.extend(vars(o).values())
+    return spans
+
+
+def _pointers(o):
+    """every non-null address op `o` holds"""
+    import ctypes as C
+    if o.op == L.OP_CONV:
+        vals = [getattr(o.conv, n) for n, typ in _lib.ConvParams._fields_ if typ in (Tensor, C.c_void_p)]
+    else:
+        vals = list(o.t) + list(o.p)
+    return [p for p in (v.p if isinstance(v, Tensor) else v for v in vals) if p]
+
+
+# (prec, bwd_prec) -> (x_flag, the no-gradient images get a launch of their own, a conversion opens the backward)
+VGG_PRECS = {(5, 2): (3, True, True), (5, 5): (3, True, True), (4, None): (1, True, False), (3, None): (1, True, False),
+             (2, None): (2, False, True), (1, None): (1, False, False)}
+
+
+@pytest.mark.parametrize('prec,bwd_prec', sorted(VGG_PRECS, key=str))
+def test_vgg_plan_is_one_builder_in_every_precision(prec, bwd_prec, monkeypatch):
+    monkeypatch.delenv('DASR_VGG_NOGRAD_PREC', raising=False)
+    x_flag, one_pass, cvt = VGG_PRECS[(prec, bwd_prec)]
+    V = gan_nets.VGGFeatureHIP(3, device='cpu', cfg=[16, 'M', 32], prec=prec, bwd_prec=bwd_prec)   # conv+ReLU, pool, conv: the pool runs in the activation form
+    assert [l[0] for l in V.layers] == ['conv', 'pool', 'conv']
+    P = V.plan(2, 1, 8, 8)
+    assert not [n for n in dir(P) if n.startswith('_init_')]
+    assert P.x_flag == x_flag and hasattr(P, 'gscale') == cvt
+    conv = [L.OP_CONV] * (2 if one_pass else 1)
+    assert [o.op for o in P.fwd.ops] == conv + [L.OP_MAXPOOL] + conv
+    assert [o.op for o in P.bwd.ops] == ([L.OP_CVT_F16] if cvt else []) + [L.OP_CONV, L.OP_MAXPOOL_BWD, L.OP_CONV]
+    assert [o.get('tag') for o in P.fwd.ops] == ([6, 7 if prec == 5 else 6, 6, 6, 7 if prec == 5 else 6] if one_pass else [6, 6, 6])
+    assert (P.feat.f32, P.g_feat.f32, P.gx.f32) == (True, True, True) and tuple(P.feat.t.shape) == (2, 2, 4, 4, 16) and P.feat is P.outs[-1]
+    spans = _reachable_tensors(P, V)
+    acts = _reachable_tensors(P.x, P.outs, P.g_feat, P.gx, P._keep)   # the tensors the plan itself keeps: everything but weights and biases
+    for ol in (P.fwd, P.bwd):
+        for o in ol.ops:
+            ptrs = _pointers(o)
+            assert len(ptrs) >= 2
+            for p in ptrs:
+                assert any(a <= p < b for a, b in spans), (o.op, hex(p))
+            own = [o.conv.inp.p, o.conv.out_f32.p or o.conv.out_bf16.p] if o.op == L.OP_CONV else [t.p for t in o.t if t.p]
+            for p in own:
+                assert any(a <= p < b for a, b in acts), (o.op, hex(p))
+    kind = L.OP_AXPBY if x_flag == 1 else L.OP_CVT_F16
+    c = P.input_copy_op(X, 1, 1, 8, 8)
+    assert c.op == kind and _t(c.get('out_f32' if x_flag == 1 else 'y')) == _t(P.x.view(n0=1))
+    if x_flag != 1:
+        assert c.get('form') == int(prec == 5)
